@@ -135,7 +135,12 @@ def main():
                                                         "16 ms instead of 25 for 256 trees on an idle GPU, but 208 instead of 230 M/s beside a growing batch")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure the HBM traffic of the step kernels")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) one grow step of --queries queries and nothing else: what the counter passes profile")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0's queries) as DIR/<name>.npy, "
+                                                          "float64, at most 64 MB: every query's node count, the exchange's winners, the trees of a fixed, seeded "
+                                                          "sample of the queries (last_step_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:], args.launch_check))
     # stdout carries the one JSON line and nothing else: RCCL prints a version banner there when the first communicator is made,
@@ -341,6 +346,8 @@ def main():
             and np.array_equal(bufs[j][1][:m], eparent) and np.array_equal(bufs[j][2][:m].view(np.uint64), edist.view(np.uint64))
     if not fetch_checked:
         raise SystemExit("bench: a tree fetched beside the growing batch differs from its context's own porrt_get_tree")
+    # --dump-outputs: copied now, before the loops below reuse the contexts; written at the end
+    dump = last_step_outputs(engs, bufs, win, args.n_iter) if args.dump_outputs and rank == 0 else None
 
     # the same steps with the trees left on the device (a caller that only downloads the winner): the second figure of the line
     barrier()
@@ -542,12 +549,53 @@ def main():
                     out["config"][key] = fn(local_rank, not args.no_cpu_baseline)
                 except Exception as ex:                      # noqa: BLE001
                     out["config"][key] = {"error": "%s: %s" % (type(ex).__name__, ex)}
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            note("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(dump), sum(a.nbytes for a in dump.values()) / 1e6, args.dump_outputs))
         note("done")
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if comm is not None:
         comm.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_TREE_BYTES = 48 << 20          # --dump-outputs: the sampled trees' share of the 64 MB the files may take
+
+
+def last_step_outputs(engs, bufs, win, n_iter):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 arrays by file name.  num_nodes: every query's
+    tree size; winner_cost / winner_rank / winner_nodes: the exchange's table, one row per map; tree_*: the fetched trees of a
+    fixed, seeded sample of the queries (tree_query, ascending), as many as fit DUMP_TREE_BYTES at the trees' capacity, concatenated
+    (tree_offsets: where each begins) -- node coordinates, parents, dist_root and the node's index in its tree.  A tree longer than
+    its share keeps a seeded sample of its nodes, in index order.  Inputs and samples depend on the arguments alone."""
+    import numpy as np
+    Q = len(engs)
+    row_bytes = 5 * 8                                       # x, y, parent, dist_root, node index
+    k = int(min(Q, max(1, DUMP_TREE_BYTES // (row_bytes * (n_iter + 2)))))
+    rows_max = DUMP_TREE_BYTES // (row_bytes * k)
+    picked = np.sort(np.random.default_rng(0).choice(Q, size=k, replace=False))
+    ids, xy, parent, dist = [], [], [], []
+    for q in picked:
+        m = engs[q].num_nodes()
+        sel = np.arange(m) if m <= rows_max else np.sort(np.random.default_rng(1 + int(q)).choice(m, size=rows_max, replace=False))
+        ids.append(sel)
+        xy.append(bufs[q][0][sel])
+        parent.append(bufs[q][1][sel])
+        dist.append(bufs[q][2][sel])
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)      # noqa: E731
+    return {
+        "num_nodes": f64([e.num_nodes() for e in engs]),
+        "winner_cost": f64(win["cost"]), "winner_rank": f64(win["rank"]), "winner_nodes": f64(win["n_nodes"]),
+        "tree_query": f64(picked),
+        "tree_offsets": f64(np.concatenate([[0], np.cumsum([len(s) for s in ids])])),
+        "tree_node": f64(np.concatenate(ids)),
+        "tree_xy": f64(np.concatenate(xy)),
+        "tree_parent": f64(np.concatenate(parent)),
+        "tree_dist_root": f64(np.concatenate(dist)),
+    }
 
 
 def measure_traffic(args, Q, timeout_s=240):
