@@ -15,8 +15,11 @@
  *     po_rrt_last_error() has the text.  The reference aborts ("graph not grown up to solution", pto_c.rs:215).
  *   - samplers: the reference seeds from OS entropy (new_true_random, pto_c.rs:213); so does this library unless
  *     po_rrt_set_seed() is called.
- *   - policy refinement (PTOPolicyRefiner::refine_solution, pto_c.rs:217-218) is outside the accelerated path (SURVEY
- *     section 2: OUT OF SCOPE): the paths are the extracted policy's, refinement_s reads 0, refine_iterations is ignored.
+ *   - policy refinement (PTOPolicyRefiner::refine_solution(PartialShortCut(refine_iterations)), pto_c.rs:217-218): with
+ *     refine_iterations > 0 plan() refines as the reference does (porrt_bg_refine_policy: the same paths and expected cost, bit
+ *     for bit), get_paths_* return the refined paths and refinement_s is the measured time.  With refine_iterations == 0 plan()
+ *     returns the extracted policy as it is and refinement_s reads 0; the reference still recomposes the pieces there, which
+ *     differs only where a one-node piece branches (its successors lose their parent, pto_policy_refiner.rs:348-366).
  *   - state_dim must be 2 (all grid-backed domains of the reference are 2-D; the reference also offers 3, 7, 9 for
  *     callback domains), n_worlds at most 64.
  */

@@ -407,6 +407,33 @@ public:
         }
         return policy;
     }
+    // PTOPolicyRefiner::new(&policy, ..).refine_solution(RefinmentStrategy::PartialShortCut(n_iterations)) (pto_policy_refiner.rs:87-124)
+    // of the policy extract_policy() returned last: node states are the refined ones; a piece start the reference's recompose leaves
+    // unconnected (after a one-node piece that branches) has no parent
+    Policy refine_policy(size_t n_iterations) {
+        Policy policy;
+        const int64_t n = porrt_bg_refine_policy(ctx_.get(), n_iterations, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        if (n < 0) ctx_.check((int)n);
+        std::vector<double> xy(2 * (size_t)n);
+        std::vector<uint64_t> oid((size_t)n);
+        std::vector<int64_t> par((size_t)n);
+        std::vector<uint8_t> leaf((size_t)n);
+        const int64_t m = porrt_bg_refine_policy(ctx_.get(), n_iterations, xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)n, &policy.expected_costs);
+        if (m < 0) ctx_.check((int)m);
+        const size_t nb = porrt_bg_num_beliefs(ctx_.get());
+        std::vector<double> flat(nb * (size_t)n_worlds());
+        ctx_.check(porrt_bg_get_beliefs(ctx_.get(), flat.data()));
+        for (size_t k = 0; k < (size_t)n; ++k) {
+            PolicyNode pn;
+            pn.state = {xy[2 * k], xy[2 * k + 1]};
+            pn.belief_state.assign(flat.begin() + (oid[k] % nb) * n_worlds(), flat.begin() + (oid[k] % nb + 1) * n_worlds());
+            pn.original_node_id = (size_t)oid[k];
+            if (par[k] >= 0) { pn.parent = (size_t)par[k]; policy.nodes[(size_t)par[k]].children.push_back(k); }
+            policy.nodes.push_back(std::move(pn));
+            if (leaf[k]) policy.leafs.push_back(k);
+        }
+        return policy;
+    }
     // pto.rs:151-183
     Policy plan_belief_space(const BeliefState &start_belief_state) {
         build_belief_graph_on_device(start_belief_state);

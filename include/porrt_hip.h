@@ -238,6 +238,39 @@ int      porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, co
                                     const uint64_t *child_off, const uint32_t *child_ids, const uint64_t *parent_off, const uint32_t *parent_ids,
                                     const uint64_t *finals, uint64_t n_final, double *dist);
 
+/* ---- policy refinement: PTOPolicyRefiner::refine_solution(RefinmentStrategy::PartialShortCut(n_iterations))
+ * (src/pto_policy_refiner.rs:87-124; pto_c.rs:217-218 runs it inside plan()).  The policy is cut into pieces (Policy::decompose,
+ * common.rs:85-129: breadth-first from node 0, a piece runs until a node with 0 or >= 2 children); every piece of >= 3 nodes is
+ * shortcut with a fresh DiscreteSampler::new() (Pcg64 seed 0), n_iterations times: interpolate one joint over a random interval and
+ * keep it when every transition of the interval is valid under the piece's belief (is_transition_valid :395-423 -- state_validity,
+ * transition_validator, compute_compatibility); pieces of <= 2 nodes are left alone.  The pieces are put back together (recompose
+ * :324-393): pieces in order, each piece's nodes in path order, then the skeleton edges from the end of a piece to the starts of the
+ * pieces after it; expected_costs by common.rs:131-154 (norm2).  Deterministic: bit for bit the reference's output.
+ * Quirk kept: recompose marks a piece's first node as its start and only a LATER node as its end (`if is_start .. else if is_end`,
+ * :348-366), so a one-node piece that branches gets no skeleton edges -- the pieces after it keep parent -1 and it becomes a leaf.
+ * RefinmentStrategy::Reparent is not offered.
+ *
+ * porrt_bg_refine_policy refines the policy the last porrt_bg_extract_policy handed out (an error if there is none, or if the graph
+ * was regrown, the belief graph rebuilt or the expected costs recomputed since).  Refined node k has state xy[2k..], original id
+ * original_ids[k] (that of the policy node it came from), parent parents[k] (-1 for the root and for a piece start left unconnected
+ * by the quirk) and is a leaf (no children) iff is_leaf[k].  Returns the number of nodes; the arrays and *expected_costs are filled
+ * when cap holds them (call with cap 0 to size them: that call does no device work).  One upload, one launch (k_refine_shortcut,
+ * one wave per piece of >= 3 nodes), one download on the context's stream.  n_iterations < 2^31; iterations x distinct piece
+ * lengths <= 2^26. */
+int64_t  porrt_bg_refine_policy(porrt_ctx *ctx, uint64_t n_iterations, double *xy, uint64_t *original_ids, int64_t *parents,
+                                uint8_t *is_leaf, uint64_t cap, double *expected_costs);
+/* The same on a policy given as host arrays, checked on the context's raster with its world validities: node i has state xy[2i..],
+ * parent parents[i] (-1 for node 0, the root; children in ascending id order), original id original_ids[i] (passed through) and
+ * belief vector beliefs[belief_row[i]] (n_belief_rows x n_worlds, n_worlds = porrt_n_worlds(ctx)).  Nodes not reached from node 0
+ * belong to no piece and are dropped, as in the reference. */
+int64_t  porrt_refine_policy(porrt_ctx *ctx, uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original_ids,
+                             const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows, uint32_t n_worlds,
+                             uint64_t n_iterations, double *out_xy, uint64_t *out_original_ids, int64_t *out_parents,
+                             uint8_t *out_is_leaf, uint64_t cap, double *expected_costs);
+/* seconds of the last refinement that filled its arrays: total (host and device) and the kernel alone (HIP events; 0 when no piece
+ * has 3 nodes or n_iterations is 0) */
+int      porrt_bg_get_refine_info(const porrt_ctx *ctx, double *total_s, double *device_s);
+
 /* ---- measurement */
 typedef struct {
     uint64_t n_iter;          /* iterations run */

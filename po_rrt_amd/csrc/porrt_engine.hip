@@ -16,6 +16,7 @@
 #include "porrt_dp.hpp"
 #include "porrt_prm.hpp"
 #include "porrt_edges.hpp"
+#include "porrt_refine.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -349,6 +350,27 @@ struct porrt_ctx {
     DpState dp;                            // porrt_bg_compute_expected_costs: dist per belief node (device)
     int compute_expected_costs();
     int extract_policy();
+    // ---- policy refinement (porrt_refine.hpp): the policy porrt_bg_extract_policy last handed out, and what it was made from
+    uint64_t bg_stamp = 0;                 // belief graph builds and expected-cost runs of this context
+    bool pol_out = false;
+    uint64_t pol_tag = 0, pol_stamp = 0;   // results_tag and bg_stamp when the policy was walked
+    uint64_t raster_gen = 1, cls_host_gen = 0, refine_raster_gen = 0;      // set_grid / set_zones; the host classes and the refiner's copy
+    bool refine_raster_table = false;      //   (with or without its summed-area table)
+    void classify_raster();
+    GrowScratch refine_scratch;            // slot 0: raster, slot 1: everything else of a call
+    hipEvent_t refine_ev[2] = {nullptr, nullptr};
+    double refine_total_s = 0, refine_device_s = 0;
+    bool refine_done = false;
+    struct RefineOut {
+        std::vector<double> xy;
+        std::vector<uint64_t> original;
+        std::vector<int64_t> parent;
+        std::vector<uint8_t> leaf;
+        double cost = 0;
+    };
+    int64_t refine(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief,
+                   const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
+                   RefineOut &out);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     EdgeOrderState eo;                     // adjacency order of the last PTO graph / roadmap (device)
     std::shared_ptr<void> host_kd;         // the kd-tree of the node coordinates on the host (pre-order ranks, nearest nodes)
@@ -470,6 +492,16 @@ static inline size_t cls_bytes(size_t W, size_t H) { return cls_sat_offset(W, H)
 int porrt_ctx::build_cls() {
     if (!has_grid) return PORRT_OK;
     if (!cls_dirty) return PORRT_OK;
+    classify_raster();
+    HIPCHK(hipMemcpyAsync(d_cls.p, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
+    cls_dirty = false;
+    return PORRT_OK;
+}
+
+// the host tables behind d_cls (classes, clearance, summed-area table), made once per raster
+void porrt_ctx::classify_raster() {
+    if (cls_host_gen == raster_gen) return;
+    cls_host_gen = raster_gen;
     size_t n = (size_t)W * H;
     cls.resize(n);
     for (size_t p = 0; p < n; ++p) {
@@ -518,9 +550,6 @@ int porrt_ctx::build_cls() {
         }
         memcpy(cls.data() + sat_at, sat.data(), sat.size() * sizeof(uint32_t));
     }
-    HIPCHK(hipMemcpyAsync(d_cls.p, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
-    cls_dirty = false;
-    return PORRT_OK;
 }
 
 // heuristic_radius(n) (src/common.rs:357-369, platform libm as Rust's f64::ln/powf) turned into the exact
@@ -1683,6 +1712,7 @@ int porrt_ctx::build_belief_graph(const double *start_belief, uint32_t n_worlds_
     in.graph_tag = results_tag;
     bg_graph_tag = results_tag;
     in.stream = stream;
+    ++bg_stamp;
     std::string e;
     r = belief_graph_build(bg, in, start_belief, e);
     if (r) { bg.release(); set_err(e); }
@@ -1694,6 +1724,8 @@ int porrt_ctx::build_belief_graph(const double *start_belief, uint32_t n_worlds_
 int porrt_ctx::compute_expected_costs() {
     if (!bg.valid || bg_graph_tag != results_tag) { set_err("compute_expected_costs: build the belief graph first (porrt_build_belief_graph)"); return PORRT_ERR_INVALID; }
     HIPCHK(hipSetDevice(device));
+    ++bg_stamp;
+    dp.have_policy = false;                           // a policy walked on the costs before this run is not handed out again
     int r = download(DL_TREE | DL_MASKS);
     if (r) return r;
     const BeliefSpace &bs = bg.cache.space;
@@ -1738,7 +1770,134 @@ int porrt_ctx::extract_policy() {
     std::string e;
     int r = dp_extract_policy(dp, true, belief_of, p_of, stream, e);
     if (r) set_err(e);
+    else { pol_tag = results_tag; pol_stamp = bg_stamp; }
     return r;
+}
+
+// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of a policy given as host arrays: node k
+// has state xy[2k..], parent parents[k] (-1 for the root; children in ascending id order), original id original[k] (passed through)
+// and belief row belief[k] of beliefs (n_rows x nw) with compatibility bits compat[row].  Decomposition, draws and recomposition on
+// the host; the shortcuts of all pieces in one launch (k_refine_shortcut, porrt_refine.hpp): one upload, one launch, one download.
+// Returns the number of nodes of the refined policy; with run = false only that (no device work).
+int64_t porrt_ctx::refine(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief,
+                          const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
+                          RefineOut &out) {
+    const double t0 = now_s();
+    if (n == 0 || n >= (1ull << 31) || parents[0] != -1) { set_err("refine_policy: a policy of 1 .. 2^31 nodes whose node 0 is the root"); return PORRT_ERR_INVALID; }
+    for (uint64_t k = 0; k < n; ++k) {
+        if (belief[k] >= n_rows) { set_err("refine_policy: a belief row out of range"); return PORRT_ERR_INVALID; }
+        if (k && (parents[k] < 0 || (uint64_t)parents[k] >= n || (uint64_t)parents[k] == k)) { set_err("refine_policy: a parent out of range"); return PORRT_ERR_INVALID; }
+    }
+    if (n_iter >= (1ull << 31)) { set_err("refine_policy: at most 2^31 - 1 iterations"); return PORRT_ERR_INVALID; }
+    std::vector<std::vector<uint32_t>> pieces, skeleton;
+    refine_decompose(n, parents, pieces, skeleton);
+    for (const auto &pc : pieces)                     // decompose: assert_eq!(belief_state of the piece's first node, of this node)
+        for (uint32_t id : pc)
+            if (belief[id] != belief[pc[0]] && std::memcmp(beliefs + (size_t)belief[id] * nw, beliefs + (size_t)belief[pc[0]] * nw, nw * sizeof(double))) {
+                set_err("refine_policy: a piece whose nodes carry different beliefs (the reference asserts, common.rs:102)");
+                return PORRT_ERR_INVALID;
+            }
+    std::vector<uint32_t> src;
+    refine_recompose(pieces, skeleton, src, out.parent, out.leaf);
+    if (!run) return (int64_t)src.size();
+    if (!has_grid) { set_err("refine_policy: the refiner checks transitions on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    // piece states in path order, the long pieces' descriptors, one table of draws per distinct length
+    std::vector<double> px, py;
+    std::vector<RefinePiece> longs;
+    std::vector<std::pair<uint32_t, uint32_t>> len_at;          // (length, first draw)
+    std::unordered_map<uint32_t, uint32_t> draws_of;
+    for (const auto &pc : pieces)
+        for (uint32_t id : pc) { px.push_back(xy[2 * id]); py.push_back(xy[2 * id + 1]); }
+    for (size_t i = 0, off = 0; i < pieces.size(); off += pieces[i].size(), ++i) {
+        const uint32_t len = (uint32_t)pieces[i].size();
+        if (len <= 2 || n_iter == 0) continue;                   // partial_shortcut: nothing to do, nothing drawn
+        auto found = draws_of.find(len);
+        uint32_t at = found == draws_of.end() ? 0xFFFFFFFFu : found->second;
+        if (at == 0xFFFFFFFFu) {
+            if ((len_at.size() + 1) * n_iter > (1ull << 26)) { set_err("refine_policy: more than 2^26 draws (iterations x distinct piece lengths)"); return PORRT_ERR_CAPACITY; }
+            at = (uint32_t)(len_at.size() * n_iter);
+            len_at.push_back({len, at});
+            draws_of[len] = at;
+        }
+        longs.push_back({(uint32_t)off, len, at, belief[pieces[i][0]]});
+    }
+    refine_device_s = 0.0;
+    if (!longs.empty()) {
+        // the raster (classes and summed-area table, build_cls's tables) lives in a slot of its own, uploaded once per raster
+        classify_raster();
+        uint8_t *d_raster = nullptr;
+        HIPCHK(refine_scratch.get(0, d_raster, cls.size()));
+        if (refine_raster_gen != raster_gen) {
+            HIPCHK(hipMemcpyAsync(d_raster, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
+            refine_raster_gen = raster_gen;
+        }
+        RunConst g;
+        memset(&g, 0, sizeof g);
+        g.cls = d_raster; g.clr = d_raster + (size_t)W * H; g.sat = opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(W, H)) : nullptr;
+        g.W = W; g.H = H; g.low0 = low[0]; g.low1 = low[1]; g.ppm = ppm; g.domain = domain; g.has_grid = has_grid;
+        g.n_validities = n_validities;
+        for (int i = 0; i < n_validities; ++i) g.validities[i] = validities[i];
+        // one staging area: RunConst | pieces | compat | draws | x | y | error word
+        auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        const size_t nd = len_at.size() * n_iter, ns = px.size();
+        const size_t o_pc = up8(sizeof(RunConst)), o_cp = o_pc + up8(longs.size() * sizeof(RefinePiece)), o_dr = o_cp + up8((size_t)n_rows * 8),
+                     o_x = o_dr + up8(nd * sizeof(uint2)), o_y = o_x + ns * 8, o_err = o_y + ns * 8, bytes = o_err + 16;
+        std::vector<uint8_t> stage(bytes, 0);
+        memcpy(stage.data(), &g, sizeof g);
+        memcpy(stage.data() + o_pc, longs.data(), longs.size() * sizeof(RefinePiece));
+        memcpy(stage.data() + o_cp, compat, (size_t)n_rows * 8);
+        uint2 *dr = (uint2 *)(stage.data() + o_dr);
+        for (const auto &la : len_at) {                          // DiscreteSampler::new() per piece (pto_policy_refiner.rs:172-175)
+            Pcg64 rng;
+            rng.seed_from_u64(0);
+            const uint64_t L = la.first;
+            for (uint64_t it = 0; it < n_iter; ++it) {
+                const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
+                const uint32_t s = (uint32_t)rng.gen_range_usize(L - 2);
+                const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(L - s - 2);
+                dr[la.second + it] = make_uint2(s | (joint << 31), e);
+            }
+        }
+        memcpy(stage.data() + o_x, px.data(), ns * 8);
+        memcpy(stage.data() + o_y, py.data(), ns * 8);
+        uint8_t *d = nullptr;
+        HIPCHK(refine_scratch.get(1, d, bytes));
+        for (int k = 0; k < 2; ++k) if (!refine_ev[k]) HIPCHK(hipEventCreate(&refine_ev[k]));
+        RefineConst rc{};
+        rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = (const unsigned long long *)(d + o_cp);
+        rc.draws = (const uint2 *)(d + o_dr); rc.x = (double *)(d + o_x); rc.y = (double *)(d + o_y); rc.err = (uint32_t *)(d + o_err);
+        rc.n_pieces = (uint32_t)longs.size(); rc.n_iter = (uint32_t)n_iter;
+        HIPCHK(hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipEventRecord(refine_ev[0], stream));
+        hipLaunchKernelGGL(k_refine_shortcut, dim3(rc.n_pieces), dim3(64), 0, stream, rc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(refine_ev[1], stream));
+        HIPCHK(hipMemcpyAsync(stage.data() + o_x, d + o_x, bytes - o_x, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, refine_ev[0], refine_ev[1]));
+        refine_device_s = 1e-3 * (double)ms;
+        uint32_t err = 0;
+        memcpy(&err, stage.data() + o_err, 4);
+        if (err) { set_err("refine_policy: a shortcut reads outside the raster, a door pixel without zone id or two zones on one segment (the reference panics)"); return PORRT_ERR_RASTER; }
+        memcpy(px.data(), stage.data() + o_x, ns * 8);
+        memcpy(py.data(), stage.data() + o_y, ns * 8);
+    }
+    // recompose: the refined states in piece order (px / py are laid out in exactly that order), then the expected cost
+    const size_t m = src.size();
+    out.xy.resize(2 * m);
+    out.original.resize(m);
+    for (size_t k = 0; k < m; ++k) { out.xy[2 * k] = px[k]; out.xy[2 * k + 1] = py[k]; out.original[k] = original[src[k]]; }
+    out.cost = refine_expected_cost(out.parent, out.xy, [&](uint32_t a, uint32_t b) {       // transition_probability (common.rs:187-190)
+        const double *pb = beliefs + (size_t)belief[src[a]] * nw, *cb = beliefs + (size_t)belief[src[b]] * nw;
+        double sum = 0.0;
+        for (uint32_t w = 0; w < nw; ++w) sum = sum + (cb[w] > 0.0 ? pb[w] : 0.0);
+        return sum;
+    });
+    refine_total_s = now_s() - t0;
+    refine_done = true;
+    return (int64_t)m;
 }
 
 // PRM::init + PRM::grow_graph (prm.rs:33-109); see porrt_prm.hpp.
@@ -2766,6 +2925,8 @@ void porrt_destroy(porrt_ctx *c) {
     if (c->d_rcarr) (void)hipFree(c->d_rcarr);
     if (c->d_batch_out) (void)hipFree(c->d_batch_out);
     c->mm_scratch.free_all();
+    c->refine_scratch.free_all();
+    for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
     if (c->d_active) (void)hipFree(c->d_active);
@@ -2789,6 +2950,7 @@ int porrt_set_grid(porrt_ctx *c, const uint8_t *occ, uint32_t W, uint32_t H, con
     c->domain = domain;
     c->has_grid = true;
     c->cls_dirty = true;
+    ++c->raster_gen;
     c->n_zones = 0; c->n_worlds = 1; c->n_validities = 1; c->validities[0] = 1; c->visibility = 0.0;
     if (c->goal_kind == 2) c->goal_kind = 0;
     return PORRT_OK;
@@ -2835,6 +2997,7 @@ int porrt_set_zones(porrt_ctx *c, const uint8_t *zone_ids, double visibility) {
         c->n_validities = nz + 1;
     }
     c->cls_dirty = true;
+    ++c->raster_gen;
     return PORRT_OK;
 }
 
@@ -3434,6 +3597,7 @@ int64_t porrt_bg_extract_policy(porrt_ctx *c, uint64_t *original_ids, int64_t *p
     }
     const uint64_t n = c->dp.pol_original.size();
     if (expected_costs && hipMemcpy(expected_costs, c->dp.d_dist, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
+    c->pol_out = true;
     if (cap >= n) {
         for (uint64_t k = 0; k < n; ++k) {
             if (original_ids) original_ids[k] = c->dp.pol_original[k];
@@ -3442,6 +3606,79 @@ int64_t porrt_bg_extract_policy(porrt_ctx *c, uint64_t *original_ids, int64_t *p
         }
     }
     return (int64_t)n;
+}
+
+// copies a refined policy into the caller's arrays when cap holds it
+static void refine_copy_out(const porrt_ctx::RefineOut &o, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *expected_costs) {
+    const size_t m = o.parent.size();
+    if (xy) memcpy(xy, o.xy.data(), 2 * m * sizeof(double));
+    if (original_ids) memcpy(original_ids, o.original.data(), m * sizeof(uint64_t));
+    if (parents) memcpy(parents, o.parent.data(), m * sizeof(int64_t));
+    if (is_leaf) memcpy(is_leaf, o.leaf.data(), m);
+    if (expected_costs) *expected_costs = o.cost;
+}
+
+// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iterations)) of the policy the last porrt_bg_extract_policy handed out
+int64_t porrt_bg_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf,
+                               uint64_t cap, double *expected_costs) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        if (!c->pol_out || !c->dp.have_policy || !c->bg.valid || !c->have_results || c->pol_tag != c->results_tag || c->pol_stamp != c->bg_stamp) {
+            c->set_err("refine_policy: no policy to refine -- call porrt_bg_extract_policy after the last growth, belief graph and expected costs");
+            return PORRT_ERR_INVALID;
+        }
+        int r = c->download(porrt_ctx::DL_TREE);
+        if (r) return r;
+        const uint64_t n = c->dp.pol_original.size(), B = c->bg.B;
+        const BeliefSpace &bs = c->bg.cache.space;
+        std::vector<double> pxy(2 * n);
+        std::vector<uint32_t> belief(n);
+        for (uint64_t k = 0; k < n; ++k) {                    // build_path_piece: the belief graph node's state and belief
+            const uint64_t id = c->dp.pol_original[k], node = id / B;
+            pxy[2 * k] = c->h_nx[node]; pxy[2 * k + 1] = c->h_ny[node];
+            belief[k] = (uint32_t)(id % B);
+        }
+        porrt_ctx::RefineOut o;
+        const int64_t m = c->refine(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(),
+                                    (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, false, o);
+        if (m < 0 || cap < (uint64_t)m) return (int)m;        // sizing: no device work
+        const int64_t m2 = c->refine(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(),
+                                     (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, true, o);
+        if (m2 < 0) return (int)m2;
+        refine_copy_out(o, xy, original_ids, parents, is_leaf, expected_costs);
+        return (int)m2;
+    });
+}
+
+// the same on a policy given as host arrays, checked on the context's raster with its world validities
+int64_t porrt_refine_policy(porrt_ctx *c, uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original_ids, const uint32_t *belief_row,
+                            const double *beliefs, uint32_t n_belief_rows, uint32_t n_worlds, uint64_t n_iterations, double *out_xy,
+                            uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap, double *expected_costs) {
+    if (!c || !n || !xy || !parents || !original_ids || !belief_row || !beliefs || !n_belief_rows) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policy: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
+        std::vector<unsigned long long> compat(n_belief_rows, 0ull);     // compute_compatibility (common.rs:266-276)
+        for (uint32_t b = 0; b < n_belief_rows; ++b)
+            for (int v = 0; v < c->n_validities; ++v) {
+                bool ok = true;
+                for (uint32_t w = 0; w < n_worlds && ok; ++w) ok = !(beliefs[(size_t)b * n_worlds + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
+                if (ok) compat[b] |= 1ull << v;
+            }
+        porrt_ctx::RefineOut o;
+        const int64_t m = c->refine(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, false, o);
+        if (m < 0 || cap < (uint64_t)m) return (int)m;
+        const int64_t m2 = c->refine(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, true, o);
+        if (m2 < 0) return (int)m2;
+        refine_copy_out(o, out_xy, out_original_ids, out_parents, out_is_leaf, expected_costs);
+        return (int)m2;
+    });
+}
+
+int porrt_bg_get_refine_info(const porrt_ctx *c, double *total_s, double *device_s) {
+    if (!c || !c->refine_done) return PORRT_ERR_INVALID;
+    if (total_s) *total_s = c->refine_total_s;
+    if (device_s) *device_s = c->refine_device_s;
+    return PORRT_OK;
 }
 
 // conditional_dijkstra on an explicit graph (host arrays in, dist out): the form the reference's own tests call it in

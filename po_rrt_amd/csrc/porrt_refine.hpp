@@ -1,0 +1,227 @@
+// porrt_refine.hpp -- PTOPolicyRefiner::refine_solution(RefinmentStrategy::PartialShortCut(n)) (src/pto_policy_refiner.rs:87-124).
+//
+// The policy is cut into pieces (Policy::decompose, common.rs:85-129): breadth-first from policy node 0, a piece follows single
+// children until a node with 0 or >= 2 children; the children of a branching node start the next pieces, in children order.
+// Every piece of >= 3 nodes is shortcut on its own (partial_shortcut, pto_policy_refiner.rs:158-207): with a fresh
+// DiscreteSampler::new() (Pcg64, seed 0) per piece, n iterations of
+//     joint = gen_range(0..2), s = gen_range(0..len-2), e = s + 2 + gen_range(0..len-s-2)
+//     candidate(j) = state(j) with [joint] = a * (1 - l) + b * l,  l = (j - s) / (e - s),  a, b = [joint] of nodes s and e,  j in [s, e)
+//     commit all of [s, e) iff every transition candidate(j) -> candidate(j + 1) and candidate(e - 1) -> state(e) is valid
+// where valid = both states have a validity (state_validity) and the segment's validity (transition_validator) is compatible
+// with the piece's belief (is_transition_valid, :395-423).  The draws never depend on the commits, so they are a function of
+// the piece length alone: the host makes them once per distinct length (engine Pcg64::gen_range_usize) and uploads them.
+//
+// Device (k_refine_shortcut): one wave per piece of >= 3 nodes, all pieces of a policy in one launch.  The iterations run in
+// order inside the wave; per iteration the lanes stride over [s, e), each forms its candidate and the next one, classifies the
+// two states and the segment with the growth's own state_class / traversed_class (summed-area table first), the verdict is
+// reduced across the wave (first rejected transition in path order: the reference's `&&` stops there, so a raster fault behind
+// it is never reached), and the lanes that own the nodes commit.  Piece states live in LDS up to kRefineLdsNodes nodes;
+// longer pieces work in place in global memory (the same code through a generic pointer).
+//
+// The pieces are put back together on the host (recompose, :324-393) with the expected cost recursion of common.rs:131-154.
+// Quirk kept from the reference: recompose records a piece's start with `if is_start .. else if is_end` (:348-366), so a
+// one-node piece has a start but no end.  When such a piece branches, its skeleton edges are never added: its successor
+// pieces keep no parent (parents = -1) and the one node becomes a leaf.
+#pragma once
+#include "porrt_device.hpp"
+
+#include <cmath>
+#include <deque>
+#include <string>
+#include <vector>
+
+namespace porrt {
+
+constexpr uint32_t kRefineLdsNodes = 1024;       // piece states kept in LDS: 2 x 8 KiB per wave
+
+struct RefinePiece {
+    uint32_t off;            // first state of the piece in RefineConst::x / y
+    uint32_t len;            // nodes (>= 3)
+    uint32_t draws;          // first draw of its length in RefineConst::draws
+    uint32_t belief;         // row of RefineConst::compat
+};
+
+struct RefineConst {
+    const RunConst *rc;                  // raster, summed-area table, domain, validities
+    const RefinePiece *pieces;
+    const uint2 *draws;                  // per distinct length, n_iter entries: (s | joint << 31, e)
+    const unsigned long long *compat;    // per belief: bit v = compatible with world validity v
+    double *x, *y;                       // piece states, refined in place
+    uint32_t *err;
+    uint32_t n_pieces, n_iter;
+};
+
+// is_transition_valid (pto_policy_refiner.rs:395-423): 0 valid, 1 rejected, 2 raster fault (the reference panics there).
+// The reference evaluates both state validities and only then, when both are Some, the segment.  Here the segment is classified
+// beside the states (its loads go out with theirs: one trip to memory fewer per iteration) and its fault counts only where the
+// reference would have looked at it.
+__device__ __forceinline__ uint32_t refine_transition(const RunConst &rc, const TableGrid &grid, double fx, double fy, double tx, double ty,
+                                                      unsigned long long compat) {
+    uint32_t err = 0;
+    const int vf = class_to_validity(rc, state_class(rc, fx, fy, &err));
+    const int vt = class_to_validity(rc, state_class(rc, tx, ty, &err));
+    const uint32_t err_states = err;
+    const int v = class_to_validity(rc, traversed_class(rc, grid, fx, fy, tx, ty, &err));
+    if (err_states) return 2u;
+    if (vf < 0 || vt < 0) return 1u;
+    if (err) return 2u;
+    return (v >= 0 && ((compat >> v) & 1ull)) ? 0u : 1u;
+}
+
+// interpolate (pto_policy_refiner.rs:160-162) at lambda = (j - s) as f64 / (e - s) as f64
+__device__ __forceinline__ double refine_lerp(double a, double b, uint32_t j, uint32_t s, uint32_t e) {
+    const double lambda = (double)(j - s) / (double)(e - s);
+    return a * (1.0 - lambda) + b * lambda;
+}
+
+__global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) {
+    __shared__ double lx[kRefineLdsNodes], ly[kRefineLdsNodes];
+    const uint32_t lane = threadIdx.x;
+    const RefinePiece pc = c.pieces[blockIdx.x];
+    const RunConst &rc = *c.rc;
+    const bool in_lds = pc.len <= kRefineLdsNodes;
+    double *X = in_lds ? lx : c.x + pc.off;
+    double *Y = in_lds ? ly : c.y + pc.off;
+    if (in_lds)
+        for (uint32_t j = lane; j < pc.len; j += 64) { lx[j] = as_global(c.x)[pc.off + j]; ly[j] = as_global(c.y)[pc.off + j]; }
+    __syncthreads();
+    TableGrid grid;
+    grid.p = rc.cls; grid.W = rc.W;
+    const unsigned long long compat = as_global(c.compat)[pc.belief];
+    const uint2 *dr = c.draws + pc.draws;
+    bool fault = false;
+    uint2 ahead = make_uint2(0u, 2u);             // the draws do not depend on the commits: lane l holds the draw of iteration it0 + l
+    for (uint32_t it = 0; it < c.n_iter && !fault; ++it) {
+        if ((it & 63u) == 0u) ahead = it + lane < c.n_iter ? dr[it + lane] : make_uint2(0u, 2u);
+        const uint2 d = make_uint2((uint32_t)__shfl((int)ahead.x, (int)(it & 63u)), (uint32_t)__shfl((int)ahead.y, (int)(it & 63u)));
+        const uint32_t s = d.x & 0x7FFFFFFFu, e = d.y;
+        const bool jy = (d.x >> 31) != 0u;
+        double *J = jy ? Y : X;                   // the joint that moves
+        const double a = J[s], b = J[e];
+        bool commit = true;
+        for (uint32_t j0 = s; j0 < e; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            uint32_t st = 0;
+            if (j < e) {
+                double fx = X[j], fy = Y[j], tx = X[j + 1], ty = Y[j + 1];
+                const double cj = refine_lerp(a, b, j, s, e);
+                if (jy) fy = cj; else fx = cj;
+                if (j + 1 < e) {                  // the next candidate; the last one goes to node e itself
+                    const double cn = refine_lerp(a, b, j + 1, s, e);
+                    if (jy) ty = cn; else tx = cn;
+                }
+                st = refine_transition(rc, grid, fx, fy, tx, ty, compat);
+            }
+            const unsigned long long bad = __ballot(st != 0u);
+            if (bad) {                            // the first transition in path order decides: rejected, or a fault
+                const int first = __ffsll((long long)bad) - 1;
+                fault = __shfl((int)st, first) == 2;
+                commit = false;
+                break;
+            }
+        }
+        if (commit)
+            for (uint32_t j = s + lane; j < e; j += 64) J[j] = refine_lerp(a, b, j, s, e);
+        __syncthreads();
+    }
+    if (in_lds)
+        for (uint32_t j = lane; j < pc.len; j += 64) { as_global(c.x)[pc.off + j] = lx[j]; as_global(c.y)[pc.off + j] = ly[j]; }
+    if (fault && lane == 0) atomicOr(c.err, ERR_RASTER);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+
+// Policy::decompose (common.rs:85-129) of a policy given by its parents (children order = ascending id, the order of
+// extract_policy's add_edge calls).  pieces[i] = policy node ids in path order; skeleton[i] = the pieces its last node's
+// children start.  Nodes the walk from node 0 does not reach belong to no piece.
+static inline void refine_decompose(uint64_t n, const int64_t *parents, std::vector<std::vector<uint32_t>> &pieces,
+                                    std::vector<std::vector<uint32_t>> &skeleton) {
+    std::vector<uint32_t> child_off(n + 1, 0), child_ids;
+    for (uint64_t k = 1; k < n; ++k) if (parents[k] >= 0) ++child_off[(size_t)parents[k] + 1];
+    for (uint64_t k = 0; k < n; ++k) child_off[k + 1] += child_off[k];
+    child_ids.resize(child_off[n]);
+    std::vector<uint32_t> fill(child_off.begin(), child_off.end() - 1);
+    for (uint64_t k = 1; k < n; ++k) if (parents[k] >= 0) child_ids[fill[(size_t)parents[k]]++] = (uint32_t)k;
+    pieces.clear(); skeleton.clear();
+    std::deque<uint32_t> fifo{0};
+    uint32_t n_pieces = 0;
+    while (!fifo.empty()) {
+        const uint32_t id = fifo.front();
+        fifo.pop_front();
+        std::vector<uint32_t> ids, successors;
+        for (uint32_t cur = id;;) {
+            ids.push_back(cur);
+            const uint32_t nc = child_off[cur + 1] - child_off[cur];
+            if (nc == 0) break;                                           // final node
+            if (nc == 1) { cur = child_ids[child_off[cur]]; continue; }   // simple forward
+            for (uint32_t q = child_off[cur]; q < child_off[cur + 1]; ++q) {        // branching
+                fifo.push_back(child_ids[q]);
+                successors.push_back(++n_pieces);
+            }
+            break;
+        }
+        pieces.push_back(std::move(ids));
+        skeleton.push_back(std::move(successors));
+    }
+}
+
+// recompose (pto_policy_refiner.rs:324-393): new node k lists its piece node's id (src), its parent (-1: root, or a piece start
+// left unconnected by the one-node quirk) and whether it has no children.  Pieces in order, nodes in path order; inside a piece
+// each node is the child of the one before; then the skeleton edges, from the end of piece i to the start of each next piece.
+static inline void refine_recompose(const std::vector<std::vector<uint32_t>> &pieces, const std::vector<std::vector<uint32_t>> &skeleton,
+                                    std::vector<uint32_t> &src, std::vector<int64_t> &parent, std::vector<uint8_t> &leaf) {
+    src.clear(); parent.clear();
+    std::vector<int64_t> start(pieces.size(), -1), end(pieces.size(), -1);
+    for (size_t i = 0; i < pieces.size(); ++i)
+        for (size_t j = 0; j < pieces[i].size(); ++j) {
+            const int64_t id = (int64_t)src.size();
+            src.push_back(pieces[i][j]);
+            parent.push_back(j == 0 ? -1 : id - 1);
+            if (j == 0) start[i] = id;                               // is_start ...
+            else if (j + 1 == pieces[i].size()) end[i] = id;         // ... else if is_end: a one-node piece has no end
+        }
+    for (size_t i = 0; i < skeleton.size(); ++i)
+        for (uint32_t nxt : skeleton[i])
+            if (end[i] >= 0 && start[nxt] >= 0) parent[(size_t)start[nxt]] = end[i];
+    leaf.assign(src.size(), 1);
+    for (int64_t p : parent) if (p >= 0) leaf[(size_t)p] = 0;
+}
+
+// Policy::compute_expected_costs_to_goals (common.rs:131-154) from node 0: sum over the children in order of
+// p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
+// Children of a recomposed node are in ascending id order.  Evaluated with an explicit stack (a piece can be long).
+template <class ProbOf>
+static inline double refine_expected_cost(const std::vector<int64_t> &parent, const std::vector<double> &xy, ProbOf q_of) {
+    const size_t n = parent.size();
+    if (n == 0) return 0.0;
+    std::vector<uint32_t> off(n + 1, 0), ids;
+    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ++off[(size_t)parent[k] + 1];
+    for (size_t k = 0; k < n; ++k) off[k + 1] += off[k];
+    ids.resize(off[n]);
+    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ids[fill[(size_t)parent[k]]++] = (uint32_t)k;
+    struct Frame { uint32_t id, next; double p, acc, term; };
+    std::vector<Frame> st{{0u, off[0], 1.0, 0.0, 0.0}};
+    double ret = 0.0;
+    while (true) {
+        Frame &f = st.back();
+        if (f.next < off[f.id + 1]) {
+            const uint32_t c = ids[f.next++];
+            const double q = q_of(f.id, c);
+            double dx = xy[2 * c] - xy[2 * f.id], d2 = 0.0;
+            d2 += dx * dx;
+            dx = xy[2 * c + 1] - xy[2 * f.id + 1];
+            d2 += dx * dx;
+            f.term = f.p * q * std::sqrt(d2);
+            const double pq = f.p * q;
+            st.push_back({c, off[c], pq, 0.0, 0.0});
+            continue;
+        }
+        ret = f.acc;
+        st.pop_back();
+        if (st.empty()) return ret;
+        st.back().acc += st.back().term + ret;
+    }
+}
+
+} // namespace porrt

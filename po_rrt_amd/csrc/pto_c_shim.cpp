@@ -108,7 +108,7 @@ int po_rrt_set_seed(CPlanningProblem *p, uint64_t c, uint64_t d) { if (!p) retur
 int po_rrt_set_device(CPlanningProblem *p, int device, uint32_t K) { if (!p || !K) return PORRT_ERR_INVALID; p->device = device; p->batch_K = K; return PORRT_OK; }
 
 // plan_inner! (pto_c.rs:208-224): PTO::new, grow_graph, plan_belief_space (build_belief_graph, expected costs, policy),
-// save_planning_metrics, save_paths -- without the refiner.
+// PTOPolicyRefiner::refine_solution(PartialShortCut(refine_iterations)) when refine_iterations > 0, save_planning_metrics, save_paths.
 int plan(CPlanningProblem *p, double *start, size_t n) {
     if (!p || !start) return PORRT_ERR_INVALID;
     const auto t0 = std::chrono::steady_clock::now();
@@ -154,12 +154,28 @@ int plan(CPlanningProblem *p, double *start, size_t n) {
     const uint64_t N = porrt_num_nodes(c), B = porrt_bg_num_beliefs(c);
     std::vector<double> xy(2 * N);
     if ((r = porrt_get_tree(c, xy.data(), nullptr, nullptr))) return leave(r, "get_tree");
+    // node k of the policy the paths are read from is at xy[2 * at[k]..]: the graph node of the policy node, or the refined state
+    std::vector<uint64_t> at((size_t)np);
+    for (int64_t k = 0; k < np; ++k) at[(size_t)k] = oid[(size_t)k] / B;
+    double refine_s = 0.0;
+    int64_t nr = np;
+    if (p->refine_iterations > 0) {                  // pto_c.rs:217-218
+        const auto tr = std::chrono::steady_clock::now();
+        nr = porrt_bg_refine_policy(c, p->refine_iterations, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        if (nr < 0) return leave((int)nr, "refine_solution");
+        xy.resize(2 * (size_t)nr);
+        oid.resize((size_t)nr); par.resize((size_t)nr); leaf.resize((size_t)nr); at.resize((size_t)nr);
+        const int64_t nr2 = porrt_bg_refine_policy(c, p->refine_iterations, xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)nr, &cost);
+        if (nr2 != nr) return leave(nr2 < 0 ? (int)nr2 : PORRT_ERR_INVALID, "refine_solution");
+        refine_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tr).count();
+        for (int64_t k = 0; k < nr; ++k) at[(size_t)k] = (uint64_t)k;
+    }
     // save_paths (pto_c.rs:274-304): leaf -> root, reversed
-    for (int64_t k = 0; k < np; ++k) {
+    for (int64_t k = 0; k < nr; ++k) {
         if (!leaf[(size_t)k]) continue;
         std::vector<std::array<double, 2>> path;
         for (int64_t cur = k; cur >= 0; cur = par[(size_t)cur]) {
-            const uint64_t node = oid[(size_t)cur] / B;
+            const uint64_t node = at[(size_t)cur];
             path.push_back({xy[2 * node], xy[2 * node + 1]});
         }
         std::vector<std::array<double, 2>> rev(path.rbegin(), path.rend());
@@ -171,7 +187,7 @@ int plan(CPlanningProblem *p, double *start, size_t n) {
     p->graph_growth_s = m.total_s;
     p->belief_space_expansion_s = bsec[0];
     p->dynamic_programming_s = dp_total;
-    p->refinement_s = 0.0;
+    p->refinement_s = refine_s;
     p->total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     p->err.clear();
     porrt_destroy(c);

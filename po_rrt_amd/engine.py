@@ -32,6 +32,7 @@ SYMBOLS = [
     "porrt_build_belief_graph", "porrt_bg_num_beliefs", "porrt_bg_num_nodes", "porrt_bg_num_edges", "porrt_bg_get_beliefs",
     "porrt_bg_get_observable_zones", "porrt_bg_get_node_types", "porrt_bg_get_children", "porrt_bg_get_parents", "porrt_bg_get_seconds",
     "porrt_bg_compute_expected_costs", "porrt_bg_get_expected_costs", "porrt_bg_expected_cost_of", "porrt_bg_get_dp_info", "porrt_bg_get_dp_sweep_rows", "porrt_bg_extract_policy", "porrt_conditional_dijkstra",
+    "porrt_bg_refine_policy", "porrt_refine_policy", "porrt_bg_get_refine_info",
     "porrt_comm_unique_id", "porrt_comm_create", "porrt_comm_destroy", "porrt_comm_last_error", "porrt_exchange_best", "porrt_exchange_num_nodes",
     "porrt_exchange_get_tree", "porrt_exchange_decide", "porrt_exchange_agree", "porrt_tree_device",
     "porrt_host_pin", "porrt_host_unpin", "porrt_exchange_tables", "porrt_comm_test_new_ops", "porrt_comm_usable", "porrt_comm_set_timeout_ms", "porrt_comm_test_new", "porrt_comm_test_fail", "porrt_comm_test_aborts",
@@ -134,6 +135,10 @@ def load_library():
     sig("porrt_bg_extract_policy", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
     sig("porrt_conditional_dijkstra", C.c_int, C.c_int, C.c_uint64, _f64p, _u32p, _f64p, C.c_uint32, C.c_uint32, _u8p, _u64p, _u32p, _u64p, _u32p,
         _u64p, C.c_uint64, _f64p)
+    sig("porrt_bg_refine_policy", C.c_int64, vp, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_refine_policy", C.c_int64, vp, C.c_uint64, _f64p, _i64p, _u64p, _u32p, _f64p, C.c_uint32, C.c_uint32, C.c_uint64,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_bg_get_refine_info", C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double))
     sig("porrt_best_cost_batch", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_double))
     sig("porrt_get_metrics", C.c_int, vp, C.POINTER(Metrics))
     sig("porrt_set_option", C.c_int, vp, C.c_char_p, C.c_int64)
@@ -469,6 +474,37 @@ class Engine:
         oid, par, leaf = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
         self._l.porrt_bg_extract_policy(self._c, oid.ctypes.data_as(C.c_void_p), par.ctypes.data_as(C.c_void_p), leaf.ctypes.data_as(C.c_void_p), n, C.byref(cost))
         return (oid, par, leaf), cost.value
+
+    # ---- policy refinement (PTOPolicyRefiner::refine_solution(PartialShortCut(n)), pto_policy_refiner.rs:87-124)
+    def _refined(self, call):
+        cost = C.c_double(0.0)
+        n = call(None, None, None, None, 0, None)
+        if n < 0:
+            self._chk(int(n))
+        xy, oid, par, leaf = np.zeros((n, 2)), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
+        self._chk(int(call(xy.ctypes.data_as(C.c_void_p), oid.ctypes.data_as(C.c_void_p), par.ctypes.data_as(C.c_void_p),
+                           leaf.ctypes.data_as(C.c_void_p), n, C.byref(cost))))
+        return (xy, oid, par, leaf), cost.value
+
+    def refine_policy(self, n_iterations):
+        """the policy of the last extract_policy, partially shortcut n_iterations times per piece:
+        (states [n, 2], original belief node ids, parents (-1 = root or a piece left unconnected), leaf flags), expected cost"""
+        return self._refined(lambda xy, oid, par, leaf, cap, cost: self._l.porrt_bg_refine_policy(self._c, int(n_iterations), xy, oid, par, leaf, cap, cost))
+
+    def refine_policy_explicit(self, xy, parents, original_ids, belief_row, beliefs, n_iterations):
+        """the same on a policy given as arrays (children in ascending id order), checked on this context's raster"""
+        xy = _f64(xy).reshape(-1, 2)
+        par = np.ascontiguousarray(parents, dtype=np.int64)
+        oid = np.ascontiguousarray(original_ids, dtype=np.uint64)
+        row = np.ascontiguousarray(belief_row, dtype=np.uint32)
+        bel = _f64(beliefs).reshape(len(beliefs), -1)
+        return self._refined(lambda oxy, ooid, opar, oleaf, cap, cost: self._l.porrt_refine_policy(
+            self._c, len(par), xy, par, oid, row, bel, bel.shape[0], bel.shape[1], int(n_iterations), oxy, ooid, opar, oleaf, cap, cost))
+
+    def refine_info(self):
+        a, b = C.c_double(0), C.c_double(0)
+        self._chk(self._l.porrt_bg_get_refine_info(self._c, C.byref(a), C.byref(b)))
+        return dict(total_s=a.value, device_s=b.value)
 
     def dp_info(self):
         a, b, n = C.c_double(0), C.c_double(0), C.c_uint32(0)
