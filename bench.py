@@ -19,8 +19,14 @@ with exit code 3 when fewer than N devices are visible).  Every rank plans its o
 queries (different RNG seeds, at N > 1 spread over the nine maps map_benchmark_like_{a..i}; no data-path collective:
 weak scaling) and the job ends with ONE exchange behind the C ABI (porrt_exchange_best: ncclAllGather of the best path
 cost per map and rank, ncclBroadcast of the winning trees).
-Rank 0 prints one JSON line.  `roofline` is measured live with HIP events around the search and connect kernels;
-`cpu_baseline` times the single-thread C restatement of the reference loop (oracle/) on the host.
+Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps (and the exchange), writes --dump-outputs and prints the line: `value`,
+`ms_per_step` and the configuration.  Everything else is measured with --full only (each part can be left out again by its
+--no-* option): the check of the fetched trees against the contexts' own copies, `value_trees_on_device` (the timed steps a
+second time), `single_query`, `roofline` (HIP events around the search and connect kernels, and the two rocprofv3 --pmc child
+runs for its `traffic`), `cpu_baseline` (the single-thread C restatement of the reference loop, oracle/, on the host) and the
+rows after the growth in `config` (TAMP queries, map_4 POMDP, belief space, PRM, multi-modal PRM).
 """
 import argparse
 import json
@@ -124,16 +130,19 @@ def main():
     ap.add_argument("--n-iter", type=int, default=111500, help="iterations per query (~100k-node tree)")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--queries", type=int, default=256, help="independent queries advanced together per step and GPU (on the device 244 M/s at 128, 253 at 256, 261 at 384, 264 at 512 at the end of round 4: 256 keeps the default run short and 95 GB of HBM in use)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event roofline pass")
-    ap.add_argument("--no-single-query", action="store_true", help="skip the single-query (latency mode) reference run")
-    ap.add_argument("--no-belief", action="store_true", help="skip the belief-space expansion measurement (SURVEY 8f.1)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline: the fetch check, the loop with the trees left "
+                                                        "on the device, the single query, the roofline pass and its counter runs, the CPU baselines, "
+                                                        "the rows after the growth (the --no-* options below leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event roofline pass")
+    ap.add_argument("--no-single-query", action="store_true", help="with --full: skip the single-query (latency mode) reference run")
+    ap.add_argument("--no-belief", action="store_true", help="with --full: skip the rows after the growth (belief space, SURVEY 8f.1, and the others)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="engine option for every context (porrt_set_option), e.g. group_lanes=32")
     ap.add_argument("--profile-steps", type=int, default=2, help="extra steps run with per-kernel HIP events for `roofline`")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, rendezvous over gloo and stop (no GPU needed)")
     ap.add_argument("--pin", action="store_true", help="fetch the trees by one kernel writing into the caller's arrays, pinned once (porrt_host_pin), instead of staging copies: "
                                                         "16 ms instead of 25 for 256 trees on an idle GPU, but 208 instead of 230 M/s beside a growing batch")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure the HBM traffic of the step kernels")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 --pmc child runs that measure the HBM traffic of the step kernels")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) one grow step of --queries queries and nothing else: what the counter passes profile")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (rank 0's queries) as DIR/<name>.npy, "
                                                           "float64, at most 64 MB: every query's node count, the exchange's winners, the trees of a fixed, seeded "
@@ -333,46 +342,51 @@ def main():
         win_nodes = len(wparent)
     barrier()
     elapsed = time.perf_counter() - t0
-    note("timed region %.3f s; checks and the second loop (trees left on the device)" % elapsed)
+    note("timed region %.3f s" % elapsed + ("; checks and the second loop (trees left on the device)" if args.full else ""))
 
-    # outside the timed region: what the last overlapped fetch left in the caller's arrays against the contexts' own porrt_get_tree,
-    # for the first and last member of each launch sequence (the fetch ran on a thread beside the growing batch of the other set;
-    # tests/test_gpu_parity_r3.py::test_trees_fetched_beside_a_growing_batch checks every member and the oracle)
-    fetch_checked = True
-    for j in sorted({0, max(Q_launch - 1, 0), min(Q_launch, Q - 1), Q - 1}):
-        exy, eparent, edist = engs[j].tree()
-        m = len(eparent)
-        fetch_checked = fetch_checked and m == engs[j].num_nodes() and np.array_equal(bufs[j][0][:m].view(np.uint64), exy.view(np.uint64)) \
-            and np.array_equal(bufs[j][1][:m], eparent) and np.array_equal(bufs[j][2][:m].view(np.uint64), edist.view(np.uint64))
-    if not fetch_checked:
-        raise SystemExit("bench: a tree fetched beside the growing batch differs from its context's own porrt_get_tree")
+    # --full, outside the timed region: what the last overlapped fetch left in the caller's arrays against the contexts' own
+    # porrt_get_tree, for the first and last member of each launch sequence (the fetch ran on a thread beside the growing batch of
+    # the other set; tests/test_gpu_parity_r3.py::test_trees_fetched_beside_a_growing_batch checks every member and the oracle)
+    fetch_checked = None
+    if args.full:
+        fetch_checked = True
+        for j in sorted({0, max(Q_launch - 1, 0), min(Q_launch, Q - 1), Q - 1}):
+            exy, eparent, edist = engs[j].tree()
+            m = len(eparent)
+            fetch_checked = fetch_checked and m == engs[j].num_nodes() and np.array_equal(bufs[j][0][:m].view(np.uint64), exy.view(np.uint64)) \
+                and np.array_equal(bufs[j][1][:m], eparent) and np.array_equal(bufs[j][2][:m].view(np.uint64), edist.view(np.uint64))
+        if not fetch_checked:
+            raise SystemExit("bench: a tree fetched beside the growing batch differs from its context's own porrt_get_tree")
     # --dump-outputs: copied now, before the loops below reuse the contexts; written at the end
     dump = last_step_outputs(engs, bufs, win, args.n_iter) if args.dump_outputs and rank == 0 else None
 
-    # the same steps with the trees left on the device (a caller that only downloads the winner): the second figure of the line
-    barrier()
-    t1 = time.perf_counter()
-    nodes_dev, _ = timed_steps(50_000, False)
-    barrier()
-    elapsed_dev = time.perf_counter() - t1
+    # --full: the same steps with the trees left on the device (a caller that only downloads the winner): the second figure of the line
+    times, work = [elapsed], [float(agg["nodes"])]
+    if args.full:
+        barrier()
+        t1 = time.perf_counter()
+        nodes_dev, _ = timed_steps(50_000, False)
+        barrier()
+        times.append(time.perf_counter() - t1)
+        work.append(float(nodes_dev))
 
     # max over ranks of the timed region, sum over ranks of the work
     if world > 1:
-        t_el = torch.tensor([elapsed, elapsed_dev], dtype=torch.float64, device="cuda")
+        t_el = torch.tensor(times, dtype=torch.float64, device="cuda")
         dist.all_reduce(t_el, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_dev = float(t_el[0].item()), float(t_el[1].item())
-        t_nodes = torch.tensor([float(agg["nodes"]), float(nodes_dev)], dtype=torch.float64, device="cuda")
+        times = [float(t) for t in t_el.tolist()]
+        t_nodes = torch.tensor(work, dtype=torch.float64, device="cuda")
         dist.all_reduce(t_nodes, op=dist.ReduceOp.SUM)
-        total_nodes, total_nodes_dev = float(t_nodes[0].item()), float(t_nodes[1].item())
-    else:
-        total_nodes, total_nodes_dev = float(agg["nodes"]), float(nodes_dev)
+        work = [float(w) for w in t_nodes.tolist()]
+    elapsed, total_nodes = times[0], work[0]
     engs = sets[0]
     eng = engs[0]
 
     # latency mode for reference: the same query alone (porrt_grow, one context), outside the timed region
     single = None
-    note("single query, roofline pass")
-    if rank == 0 and not args.no_single_query:
+    if args.full:
+        note("single query, roofline pass")
+    if rank == 0 and args.full and not args.no_single_query:
         eng.set_sampler((-1.0, -1.0), (1.0, 1.0), 777)
         cases.grow(eng, case, K=args.batch)
         ts = []
@@ -387,7 +401,7 @@ def main():
     # roofline pass: the same step again with HIP events around the search and connect kernels (eager launches on the
     # engine's own stream; the timed region above replays the steps as a hipGraph, which cannot carry events)
     prof = dict(scan_s=0.0, scan_pairs=0.0, scan_bytes=0.0, scan_launches=0, device_s=0.0, connect_s=0.0, nodes=0.0)
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         eng.set_option("profile", 1)
         for s in range(args.profile_steps):
             run_step(s)
@@ -413,11 +427,12 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             **({"rehearsal": True} if rehearse else {}),
-            "value_trees_on_device": total_nodes_dev / elapsed_dev,
+            "full": args.full,
+            **({"value_trees_on_device": work[1] / times[1]} if args.full else {}),
             "value_note": "value counts the device-to-host copy of EVERY tree (SURVEY 8d): the %d trees of a step are fetched (porrt_get_trees, %.1f ms per "
-                          "step on average) while the next step grows on a second set of contexts, and the last fetch is inside the timed region; "
-                          "value_trees_on_device is the same loop with the trees left on the GPU (only the exchange's winner is fetched)"
-                          % (Q, 1e3 * t_download_total / max(args.steps, 1)),
+                          "step on average) while the next step grows on a second set of contexts, and the last fetch is inside the timed region"
+                          % (Q, 1e3 * t_download_total / max(args.steps, 1))
+                          + ("; value_trees_on_device is the same loop with the trees left on the GPU (only the exchange's winner is fetched)" if args.full else ""),
             "single_query": single,
             "config": {
                 "workload": "map_benchmark-like 200x200 synthetic map (reference raster is a Git-LFS pointer), 2D RRT* "
@@ -538,10 +553,10 @@ def main():
                                       "(they are not the bound: DESIGN.md section 6)"},
                 "share_of_device_time": (prof["scan_s"] + prof["connect_s"]) / max(prof["device_s"], 1e-12),
             }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             note("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(case, args)
-        if not args.no_belief and world == 1:
+        if args.full and not args.no_belief and world == 1:
             # the rows after the growth are extras of the line: a failure there must not cost the headline measurement
             for key, fn in (("tamp_queries", tamp_queries), ("map4_pomdp", map4_pomdp), ("belief_space", belief_space), ("prm_roadmap", prm_roadmap), ("mm_prm", mm_prm)):
                 note("row " + key)

@@ -1,10 +1,10 @@
 #!/bin/bash
 # developer probe (GPU box): durations of the side-chain kernels by group index over one bench step
 R=${GRAFT_REPO_ROOT:-/root/repo}
-OUT=$R/gpurun_out/ct
+OUT=${PORRT_OUT:-$R/out}/ct
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python3 $R/bench.py --steps 1 --warmup 2 --no-cpu-baseline --no-single-query --no-belief --no-pmc --no-profile --opt batch_streams=1 > /dev/null 2> $OUT/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python3 $R/bench.py --full --steps 1 --warmup 2 --no-cpu-baseline --no-single-query --no-belief --no-pmc --no-profile --opt batch_streams=1 > /dev/null 2> $OUT/err.txt
 T=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python3 - $T <<'PY'
 import csv, sys, collections

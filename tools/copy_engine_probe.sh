@@ -5,10 +5,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 run() {   # label, then VAR=val ...
   local label=$1; shift
-  local d=$R/gpurun_out/cep_$label
+  local d=${PORRT_OUT:-$R/out}/cep_$label
   rm -rf $d; mkdir -p $d
   ( for kv in "$@"; do export "$kv"; done
-    timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $d/trace -o t -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-single-query --no-belief --no-pmc --no-profile > $d/bench.json 2> $d/bench.err )
+    timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $d/trace -o t -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-single-query --no-belief --no-pmc --no-profile > $d/bench.json 2> $d/bench.err )
   local s=$(find $d/trace -name '*kernel_stats.csv' | head -1)
   python3 - "$label" "$s" $d/bench.json <<'PY'
 import csv, json, sys
