@@ -10,6 +10,7 @@
 #pragma once
 #include "porrt_hip.h"
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cctype>
@@ -495,6 +496,63 @@ public:
 private:
     Context ctx_;
     State start_{0.0, 0.0};
+};
+
+// map_shelves_tamp_prm.rs:285-494.  plan() = grow_mm_prm, build_belief_graph, compute_expected_costs_to_goals, extract_policy
+// (:310-326), all but the mode tree's bookkeeping on the device; refine_policy(n) = the reference driver's
+// PTOPolicyRefiner::refine_solution(PartialShortCut(n)) of that policy (main.rs:546-575).
+class MapShelfDomainTampPRM {
+public:
+    MapShelfDomainTampPRM(const ContinuousSampler &cs, const DiscreteSampler &ds, const MapShelfDomain &m, int device = 0) : ctx_(device) {
+        ctx_.set_domain(m);
+        ctx_.check(porrt_set_sampler(ctx_.get(), cs.low.data(), cs.up.data(), cs.seed));
+        ctx_.check(porrt_set_discrete_seed(ctx_.get(), ds.seed));
+    }
+    Policy plan(State start, const BeliefState &initial_belief_state, double max_step, double search_radius, size_t n_iter_per_belief) {
+        const int64_t r = porrt_mm_plan(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(), max_step,
+                                        search_radius, n_iter_per_belief);
+        if (r < 0) ctx_.check((int)r);
+        return fetch(false, 0);
+    }
+    Policy refine_policy(size_t n_iterations) { return fetch(true, n_iterations); }
+    const Context &context() const { return ctx_; }
+private:
+    Policy fetch(bool refined, size_t n_iterations) {
+        Policy policy;
+        auto call = [&](double *xy, uint64_t *oid, int64_t *par, uint8_t *leaf, uint64_t cap) {
+            return refined ? porrt_mm_refine_policy(ctx_.get(), n_iterations, xy, oid, par, leaf, cap, &policy.expected_costs)
+                           : porrt_mm_extract_policy(ctx_.get(), oid, par, leaf, xy, cap, &policy.expected_costs);
+        };
+        const int64_t n = call(nullptr, nullptr, nullptr, nullptr, 0);
+        if (n < 0) ctx_.check((int)n);
+        std::vector<double> xy(2 * (size_t)n);
+        std::vector<uint64_t> oid((size_t)n);
+        std::vector<int64_t> par((size_t)n);
+        std::vector<uint8_t> leaf((size_t)n);
+        const int64_t m = call(xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)n);
+        if (m < 0) ctx_.check((int)m);
+        const size_t n_modes = porrt_mm_num_modes(ctx_.get()), nw = (size_t)porrt_n_worlds(ctx_.get());
+        std::vector<uint64_t> off(n_modes + 1);
+        ctx_.check(porrt_mm_bg_get_graph(ctx_.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, off.data(), nullptr));
+        std::vector<BeliefState> beliefs(n_modes, BeliefState(nw));
+        for (size_t k = 0; k < n_modes; ++k) {
+            double rp = 0;
+            uint64_t nn = 0, ne = 0, nf = 0;
+            ctx_.check(porrt_mm_get_mode(ctx_.get(), k, beliefs[k].data(), &rp, &nn, &ne, &nf));
+        }
+        for (size_t k = 0; k < (size_t)n; ++k) {
+            PolicyNode pn;
+            pn.state = {xy[2 * k], xy[2 * k + 1]};
+            const size_t mode = (size_t)(std::upper_bound(off.begin(), off.end(), oid[k]) - off.begin()) - 1;
+            pn.belief_state = beliefs[mode];
+            pn.original_node_id = (size_t)oid[k];
+            if (par[k] >= 0) { pn.parent = (size_t)par[k]; policy.nodes[(size_t)par[k]].children.push_back(k); }
+            policy.nodes.push_back(std::move(pn));
+            if (leaf[k]) policy.leafs.push_back(k);
+        }
+        return policy;
+    }
+    Context ctx_;
 };
 
 } // namespace po_rrt

@@ -341,6 +341,49 @@ int      porrt_mm_get_transition(const porrt_ctx *ctx, uint64_t t, uint32_t *zon
 int      porrt_mm_get_transition_pairs(const porrt_ctx *ctx, uint64_t t, uint64_t *pairs /* 2 * n_pairs */);
 int      porrt_mm_get_seconds(const porrt_ctx *ctx, double *host_s, double *roadmap_s, double *device_s);
 
+/* ---- the rest of MapShelfDomainTampPRM::plan (map_shelves_tamp_prm.rs:310-326) on the modes of the last porrt_grow_mm_prm.
+ * porrt_mm_build_belief_graph: build_belief_graph (:395-473) on the device.  Belief node id = mode_offsets[m] + roadmap node
+ * (node 0 = the planning start); every node carries its mode's belief and the belief id of that belief (its index in
+ * reachable_belief_states, the key get_best_expected_children clusters by, belief_graph.rs:229-236); observation edges (transition
+ * pairs, in order; their from nodes become Observation nodes) come before action edges (roadmap children of the nodes that are not
+ * Observation nodes, PTONode::children order); children and parents lists are in add_edge order.  Finals: each mode's
+ * final_node_ids, in mode order.  A pair naming a node its mode does not have (the reference panics) is PORRT_ERR_INVALID.
+ * porrt_mm_bg_get_graph: any pointer may be NULL; child_off / parent_off hold num_nodes + 1 entries, mode_offsets num_modes + 1. */
+int      porrt_mm_build_belief_graph(porrt_ctx *ctx);
+uint64_t porrt_mm_bg_num_nodes(const porrt_ctx *ctx);
+uint64_t porrt_mm_bg_num_edges(const porrt_ctx *ctx);
+uint64_t porrt_mm_bg_num_finals(const porrt_ctx *ctx);
+int      porrt_mm_bg_get_graph(const porrt_ctx *ctx, uint64_t *child_off, uint32_t *child_ids, uint64_t *parent_off, uint32_t *parent_ids,
+                               uint8_t *types, uint32_t *belief_ids, uint64_t *mode_offsets, uint64_t *finals);
+/* compute_expected_costs_to_goals (:475-477): conditional_dijkstra (belief_graph.rs:89-175) with norm2 and transition_probability
+ * (common.rs:187-190), bit for bit, by the general sweeps.  Option "mm_levels" = 1: modes finished level by level instead (fewest
+ * possible worlds first, a workgroup per mode; same bits, measured slower) when every observation shrinks the possible worlds and
+ * "dp_sweeps" is off.  Option "mm_lds_nodes": the largest mode that relaxes in LDS there (the others relax on global memory). */
+int      porrt_mm_compute_expected_costs(porrt_ctx *ctx);
+int      porrt_mm_get_expected_costs(const porrt_ctx *ctx, double *out /* num_nodes */);
+/* extract_policy (:479-485, belief_graph.rs:177-263) from belief node 0: returns the policy's node count (or a negative error) and
+ * fills the arrays when cap holds them (cap 0: sizing): belief node ids, parents (-1 = root), leaf flags, states (2 per node), and
+ * the root's expected cost.  An infinite root cost, or a walk that returns to a node on its own path, is an error (the reference
+ * does not terminate there). */
+int64_t  porrt_mm_extract_policy(porrt_ctx *ctx, uint64_t *belief_node_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap,
+                                 double *expected_cost);
+/* PTOPolicyRefiner::refine_solution(PartialShortCut(n_iterations)) (pto_policy_refiner.rs:87-124) of the policy the last
+ * porrt_mm_extract_policy walked -- the reference driver's PartialShortCut(1500) after plan (main.rs:546-575).  Same outputs and
+ * sizing as porrt_bg_refine_policy. */
+int64_t  porrt_mm_refine_policy(porrt_ctx *ctx, uint64_t n_iterations, double *xy, uint64_t *belief_node_ids, int64_t *parents, uint8_t *is_leaf,
+                                uint64_t cap, double *expected_cost);
+/* plan (:310-326): porrt_grow_mm_prm, porrt_mm_build_belief_graph, porrt_mm_compute_expected_costs, porrt_mm_extract_policy; returns the
+ * policy's node count (fetch it with porrt_mm_extract_policy).  A new porrt_grow_mm_prm makes graph, costs and policy stale: using them
+ * is an error. */
+int64_t  porrt_mm_plan(porrt_ctx *ctx, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                       double search_radius, uint64_t n_iter_per_belief);
+/* seconds of the last steps, up to n of: grow (porrt_mm_plan), build, build on the device, expected costs, on the device, policy walk,
+ * refine, refine on the device */
+int      porrt_mm_get_plan_seconds(const porrt_ctx *ctx, double *out, uint32_t n);
+/* the last expected-cost run: levels, launches (level schedule: one per level; general sweeps: sweeps), sweeps (level schedule: summed
+ * over the modes), 1 = level schedule */
+int      porrt_mm_get_dp_info(const porrt_ctx *ctx, uint32_t *levels, uint32_t *launches, uint64_t *sweeps, int *level_schedule);
+
 /* ---- on-disk formats either side of the path (host code; no GPU needed).
  * porrt_read_pgm: the raster MapShelfDomain::open / Map::open load (image::open -> ImageLuma8,
  * map_shelves_io.rs:88-103, map_io.rs:90-105): P2 / P5 (P1 / P4 as 0 / 255), '#' comments in the header, samples as

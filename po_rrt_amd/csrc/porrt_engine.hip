@@ -170,6 +170,8 @@ struct GrowScratch {
     void free_all() { for (auto &sl : slots) if (sl.first) (void)hipFree(sl.first); slots.clear(); }
 };
 
+#include "porrt_mmplan.hpp"
+
 struct porrt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -382,6 +384,12 @@ struct porrt_ctx {
     int grow_mm_prm(const double start[2], const double *initial_belief, uint32_t n_worlds_in, double max_step, double search_radius, uint64_t n_iter_per_belief);
     int roadmaps_of_modes(double max_step, double search_radius);
     int roadmap_of_points(const std::vector<double> &xy, double max_step, double search_radius, std::vector<uint32_t> &efrom, std::vector<uint32_t> &eto, double &dev_s);
+    MmPlanState mmp;                       // porrt_mm_*: the mode-product belief graph, its expected costs and policy (porrt_mmplan.hpp)
+    GrowScratch mmp_scratch;
+    int mm_upload_roadmaps();
+    int mm_build_belief_graph();
+    int mm_compute_expected_costs();
+    int mm_extract_policy();
     int64_t prm_plan_path(const double start[2], const double goal[2], double *path_xy, uint64_t cap);
     int read_best_cost(double *cost, uint64_t *final_id);
     porrt_ctx *batch_leader = nullptr;     // set by porrt_grow_batch: the context whose RunConst array holds this one
@@ -2163,6 +2171,7 @@ int porrt_ctx::roadmaps_of_modes(double max_step, double search_radius) {
         mm.modes[mi].efrom.assign(hfrom.begin() + e0, hfrom.begin() + e1);
         mm.modes[mi].eto.assign(hto.begin() + e0, hto.begin() + e1);
     }
+    mm.dev_edges = true;                                 // slots 0, 1, 6, 9 of mm_scratch: x, y, edge offsets, neighbours (porrt_mm_build_belief_graph)
     return PORRT_OK;
 }
 
@@ -2170,6 +2179,8 @@ int porrt_ctx::grow_mm_prm(const double start[2], const double *initial_belief, 
                            uint64_t n_iter_per_belief) {
     using namespace mmprm;
     mm.clear();
+    ++mm.gen;                                    // a belief graph, costs and policy of the modes before are stale now
+    mmp.release();
     if (!has_grid || domain != PORRT_DOMAIN_SHELF || n_zones == 0) { set_err("multi-modal PRM: a shelf domain with zones (porrt_set_grid + porrt_set_zones)"); return PORRT_ERR_INVALID; }
     if (!start || !initial_belief || n_worlds_in != (uint32_t)n_worlds) { set_err("multi-modal PRM: start / belief of n_worlds entries"); return PORRT_ERR_INVALID; }
     if (!(max_step > 0.0) || !(search_radius > 0.0)) { set_err("bad PRM parameters"); return PORRT_ERR_INVALID; }
@@ -2312,6 +2323,223 @@ int porrt_ctx::grow_mm_prm(const double start[2], const double *initial_belief, 
     mm.roadmap_s = now_s() - t1;
     have_results = false;                        // the context's single-graph getters do not describe a mode tree
     mm.valid = true;
+    return PORRT_OK;
+}
+
+// The roadmaps' nodes and forward edges into the slots roadmaps_of_modes leaves them in, from the host copies (after the developer
+// switch PORRT_MM_ONE_BY_ONE, which builds them elsewhere).
+int porrt_ctx::mm_upload_roadmaps() {
+    size_t NT = 0, E = 0;
+    for (const MmMode &m : mm.modes) { NT += m.xy.size() / 2; E += m.efrom.size(); }
+    std::vector<double> hx(NT), hy(NT);
+    std::vector<unsigned long long> hoff(NT + 1, 0);
+    std::vector<uint32_t> hfrom(E);
+    size_t at = 0, ea = 0;
+    for (const MmMode &m : mm.modes) {
+        const size_t n = m.xy.size() / 2;
+        std::vector<uint32_t> deg(n, 0);
+        for (uint32_t t : m.eto) { if (t >= n) { set_err("mm_build_belief_graph: a roadmap edge names a missing node"); return PORRT_ERR_INVALID; } ++deg[t]; }
+        for (size_t t = 0; t < n; ++t) { hx[at + t] = m.xy[2 * t]; hy[at + t] = m.xy[2 * t + 1]; hoff[at + t + 1] = hoff[at + t] + deg[t]; }
+        std::copy(m.efrom.begin(), m.efrom.end(), hfrom.begin() + ea);          // (grouped by new node already: the reference's order)
+        at += n; ea += m.efrom.size();
+    }
+    double *dx = nullptr, *dy = nullptr;
+    unsigned long long *doff = nullptr;
+    uint32_t *dfrom = nullptr;
+    HIPCHK(mm_scratch.get(0, dx, NT)); HIPCHK(mm_scratch.get(1, dy, NT)); HIPCHK(mm_scratch.get(6, doff, NT + 1)); HIPCHK(mm_scratch.get(9, dfrom, E));
+    HIPCHK(hipMemcpyAsync(dx, hx.data(), NT * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dy, hy.data(), NT * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(doff, hoff.data(), (NT + 1) * 8, hipMemcpyHostToDevice, stream));
+    if (E) HIPCHK(hipMemcpyAsync(dfrom, hfrom.data(), E * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    mm.dev_edges = true;
+    return PORRT_OK;
+}
+
+// MapShelfDomainTampPRM::build_belief_graph (map_shelves_tamp_prm.rs:395-473) on the device; see porrt_mmplan.hpp.
+int porrt_ctx::mm_build_belief_graph() {
+    MmPlanState &s = mmp;
+    s.release();
+    if (!mm.valid) { set_err("mm_build_belief_graph: grow the modes first (porrt_grow_mm_prm)"); return PORRT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    const double t0 = now_s();
+    const uint32_t nw = mm.nw, M = (uint32_t)mm.modes.size();
+    // per mode: first node, belief id (belief_states_to_id[hash(belief)], :400), belief row, number of possible worlds
+    BeliefSpace bs;
+    bs.domain = domain; bs.nz = n_zones; bs.nw = nw; bs.validities = validities;
+    {
+        std::string e;
+        const int r = bs.reach_from(mm.modes[0].belief.data(), e);
+        if (r) { set_err(e); return r; }
+    }
+    s.nw = nw; s.n_modes = M;
+    s.mode_off.assign(M + 1, 0); s.mode_bid.assign(M, 0); s.support.assign(M, 0); s.beliefs.assign((size_t)M * nw, 0.0);
+    uint64_t NT = 0;
+    for (uint32_t m = 0; m < M; ++m) {
+        const MmMode &md = mm.modes[m];
+        const auto f = bs.by_hash.find(BeliefSpace::hash_of(md.belief.data(), nw));
+        if (f == bs.by_hash.end()) { set_err("mm_build_belief_graph: a mode's belief is not a reachable belief state (the reference panics, :400)"); return PORRT_ERR_INVALID; }
+        s.mode_bid[m] = f->second;
+        for (uint32_t w = 0; w < nw; ++w) { s.beliefs[(size_t)m * nw + w] = md.belief[w]; s.support[m] += md.belief[w] > 0.0 ? 1u : 0u; }
+        s.mode_off[m] = (uint32_t)NT;
+        NT += md.xy.size() / 2;
+        if (NT >= 0x7FFFFFFFull) { set_err("mm_build_belief_graph: more than 2^31 belief nodes"); return PORRT_ERR_CAPACITY; }
+    }
+    s.mode_off[M] = (uint32_t)NT;
+    s.NT = NT;
+    s.finals.clear();
+    for (uint32_t m = 0; m < M; ++m)                                  // final_belief_node_ids (:413-416)
+        for (uint64_t f : mm.modes[m].finals) {
+            if (f >= mm.modes[m].xy.size() / 2) { set_err("mm_build_belief_graph: a final node missing in its mode (the reference panics, :415)"); return PORRT_ERR_INVALID; }
+            s.finals.push_back(s.mode_off[m] + f);
+        }
+    // the transitions' pairs end to end (a copy per transition), and whether every transition loses possible worlds
+    const uint32_t T = (uint32_t)mm.tr.size();
+    std::vector<uint32_t> tr_off(T + 1, 0), tr_from(T), tr_to(T);
+    std::vector<unsigned long long> pairs;
+    s.support_shrinks = true;
+    for (uint32_t t = 0; t < T; ++t) {
+        const MmTransition &tr = mm.tr[t];
+        tr_off[t] = (uint32_t)(pairs.size() / 2); tr_from[t] = tr.from; tr_to[t] = tr.to;
+        pairs.insert(pairs.end(), tr.pairs.begin(), tr.pairs.end());
+        if (!(s.support[tr.to] < s.support[tr.from])) s.support_shrinks = false;
+    }
+    const uint64_t P = pairs.size() / 2;
+    tr_off[T] = (uint32_t)P;
+    if (P + NT >= 0xFFFFFFFFull) { set_err("mm_build_belief_graph: too many observation pairs"); return PORRT_ERR_CAPACITY; }
+    if (!mm.dev_edges) { const int r = mm_upload_roadmaps(); if (r) return r; }
+    double *dx = nullptr, *dy = nullptr;
+    unsigned long long *doff = nullptr;
+    uint32_t *dfrom = nullptr;
+    HIPCHK(mm_scratch.get(0, dx, NT)); HIPCHK(mm_scratch.get(1, dy, NT)); HIPCHK(mm_scratch.get(6, doff, NT + 1));
+    unsigned long long E = 0;
+    HIPCHK(hipMemcpy(&E, doff + NT, sizeof E, hipMemcpyDeviceToHost));
+    HIPCHK(mm_scratch.get(9, dfrom, E));
+    GrowScratch &sc = mmp_scratch;
+    MmBgConst g{};
+    g.NT = (uint32_t)NT; g.n_modes = M; g.n_tr = T; g.P = (uint32_t)P;
+    uint32_t *d_mode_off, *d_bid_m, *d_tr_off, *d_tr_from, *d_tr_to, *d_mode_of, *d_bid, *cnt_c, *cnt_p, *cur_c, *cur_p, *d_err;
+    unsigned long long *d_pairs, *child_off, *par_off, *d_tot;
+    uint8_t *d_types;
+    double *d_beliefs;
+    HIPCHK(sc.get(0, d_mode_off, M + 1)); HIPCHK(sc.get(1, d_bid_m, M)); HIPCHK(sc.get(2, d_pairs, 2 * P)); HIPCHK(sc.get(3, d_tr_off, T + 1));
+    HIPCHK(sc.get(4, d_tr_from, T)); HIPCHK(sc.get(5, d_tr_to, T)); HIPCHK(sc.get(6, d_types, NT)); HIPCHK(sc.get(7, d_mode_of, NT));
+    HIPCHK(sc.get(8, d_bid, NT)); HIPCHK(sc.get(9, cnt_c, 4 * NT)); HIPCHK(sc.get(13, child_off, NT + 1)); HIPCHK(sc.get(14, par_off, NT + 1));
+    HIPCHK(sc.get(15, d_tot, (NT + kScanTile - 1) / kScanTile + 2)); HIPCHK(sc.get(22, d_beliefs, (size_t)M * nw)); HIPCHK(sc.get(23, d_err, 1));
+    cnt_p = cnt_c + NT; cur_c = cnt_p + NT; cur_p = cur_c + NT;
+    g.mode_off = d_mode_off; g.mode_bid = d_bid_m; g.edge_off = doff; g.efrom = dfrom; g.pairs = d_pairs; g.tr_off = d_tr_off; g.tr_from = d_tr_from;
+    g.tr_to = d_tr_to; g.types = d_types; g.mode_of = d_mode_of; g.bid = d_bid; g.cnt_c = cnt_c; g.cnt_p = cnt_p; g.cur_c = cur_c; g.cur_p = cur_p;
+    g.child_off = child_off; g.par_off = par_off; g.err = d_err;
+    ScopedEvents<2> evs;
+    HIPCHK(evs.create());
+    HIPCHK(hipMemcpyAsync(d_mode_off, s.mode_off.data(), (M + 1) * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_bid_m, s.mode_bid.data(), M * 4, hipMemcpyHostToDevice, stream));
+    if (P) HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), P * 16, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_tr_off, tr_off.data(), (T + 1) * 4, hipMemcpyHostToDevice, stream));
+    if (T) {
+        HIPCHK(hipMemcpyAsync(d_tr_from, tr_from.data(), T * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_tr_to, tr_to.data(), T * 4, hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipMemcpyAsync(d_beliefs, s.beliefs.data(), (size_t)M * nw * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(evs.e[0], stream));
+    HIPCHK(hipMemsetAsync(cnt_c, 0, 4 * NT * sizeof(uint32_t), stream));
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(uint32_t), stream));
+    const dim3 block(256), ngrid((unsigned)((NT + 255) / 256)), pgrid((unsigned)((P + 255) / 256));
+    hipLaunchKernelGGL(k_mmbg_nodes, ngrid, block, 0, stream, g);
+    if (P) hipLaunchKernelGGL(k_mmbg_pairs<false>, pgrid, block, 0, stream, g);
+    hipLaunchKernelGGL(k_mmbg_roadmap<false>, ngrid, block, 0, stream, g);
+    bg_scan(cnt_c, NT, d_tot, child_off, stream);
+    bg_scan(cnt_p, NT, d_tot, par_off, stream);
+    unsigned long long tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&tot[0], child_off + NT, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&tot[1], par_off + NT, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (tot[0] != tot[1]) { set_err("mm_build_belief_graph: children and parents lists disagree"); return PORRT_ERR_DEVICE; }
+    if (tot[0] >= 0xFFFFFFFFull) { set_err("mm_build_belief_graph: more than 2^32 edges"); return PORRT_ERR_CAPACITY; }
+    const unsigned long long NE = tot[0];
+    uint32_t *ckey, *pkey, *child_id, *par_id;
+    HIPCHK(sc.get(16, ckey, 2 * NE)); HIPCHK(sc.get(18, pkey, 2 * NE)); HIPCHK(sc.get(20, child_id, NE)); HIPCHK(sc.get(21, par_id, NE));
+    g.ckey = ckey; g.cval = ckey + NE; g.pkey = pkey; g.pval = pkey + NE;
+    if (P) hipLaunchKernelGGL(k_mmbg_pairs<true>, pgrid, block, 0, stream, g);
+    hipLaunchKernelGGL(k_mmbg_roadmap<true>, ngrid, block, 0, stream, g);
+    const dim3 sgrid((unsigned)((NT + 3) / 4));
+    hipLaunchKernelGGL(k_eo_segsort, sgrid, block, 0, stream, (const unsigned long long *)child_off, (const uint32_t *)g.ckey, (const uint32_t *)g.cval, (uint32_t)NT, child_id);
+    hipLaunchKernelGGL(k_eo_segsort, sgrid, block, 0, stream, (const unsigned long long *)par_off, (const uint32_t *)g.pkey, (const uint32_t *)g.pval, (uint32_t)NT, par_id);
+    HIPCHK(hipEventRecord(evs.e[1], stream));
+    uint32_t h_err = 0;
+    HIPCHK(hipMemcpyAsync(&h_err, d_err, sizeof h_err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (h_err & MM_ERR_PAIR) { set_err("mm_build_belief_graph: an observation pair names a node its mode does not have (the reference panics, :426-427)"); return PORRT_ERR_INVALID; }
+    if (h_err & MM_ERR_EDGE) { set_err("mm_build_belief_graph: a roadmap edge names a missing node"); return PORRT_ERR_INVALID; }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    DpConst c{};
+    c.n = NT; c.B = 1; c.nw = nw; c.nx = dx; c.ny = dy; c.bvec = d_mode_of; c.beliefs = d_beliefs; c.types = d_types;
+    c.child_off = child_off; c.par_off = par_off; c.child_id = child_id; c.par_id = par_id;
+    s.c = c;
+    s.d_mode_off = d_mode_off; s.d_bid = d_bid;
+    s.n_edges = NE;
+    s.t_build_device = 1e-3 * (double)ms;
+    s.t_build = now_s() - t0;
+    s.gen = mm.gen;
+    s.valid = true;
+    return PORRT_OK;
+}
+
+// compute_expected_costs_to_goals (:475-477): conditional_dijkstra by the general sweeps (porrt_dp.hpp, explicit layout), or by level
+// (porrt_mmplan.hpp) with option "mm_levels" when every observation shrinks the possible worlds and "dp_sweeps" is off -- measured
+// slower than the sweeps, kept as an option
+int porrt_ctx::mm_compute_expected_costs() {
+    MmPlanState &s = mmp;
+    if (!mm.valid || !s.valid || s.gen != mm.gen) { set_err("mm_compute_expected_costs: build the belief graph of the last porrt_grow_mm_prm first (porrt_mm_build_belief_graph)"); return PORRT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    s.costs_gen = s.policy_gen = ~0ull;
+    s.dp.have_policy = false;
+    const double t0 = now_s();
+    std::string e;
+    int r;
+    if (s.support_shrinks && s.use_levels && !opt_dp_sweeps) {
+        uint8_t *mark = nullptr;
+        uint32_t *modes = nullptr;
+        unsigned long long *sweeps = nullptr;
+        HIPCHK(mmp_scratch.get(24, mark, 2 * s.NT)); HIPCHK(mmp_scratch.get(25, modes, s.n_modes)); HIPCHK(mmp_scratch.get(26, sweeps, 4));
+        r = mm_run_levels(s, s.c, s.finals, mark, mark + s.NT, modes, sweeps, stream, e);
+    } else {
+        r = dp_run(s.dp, s.c, false, s.finals, stream, e);
+        s.levels = 0; s.launches = s.dp.sweeps; s.level_sweeps = 0; s.max_mode_sweeps = 0;
+    }
+    if (r) { set_err(e); return r; }
+    s.t_costs = now_s() - t0;
+    s.t_costs_device = s.dp.t_device;
+    s.costs_gen = s.gen;
+    return PORRT_OK;
+}
+
+// extract_policy (:479-485, belief_graph.rs:177-263) from belief node 0, clustered by belief id; the nodes' states with it
+int porrt_ctx::mm_extract_policy() {
+    MmPlanState &s = mmp;
+    if (!mm.valid || !s.valid || s.gen != mm.gen || s.costs_gen != s.gen || !s.dp.valid) {
+        set_err("mm_extract_policy: compute the expected costs of the last belief graph first (porrt_mm_compute_expected_costs)");
+        return PORRT_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(device));
+    const double t0 = now_s();
+    auto belief_of = [&s](uint64_t i) { return s.mode_bid[mm_mode_of(s, i)]; };
+    auto p_of = [&s](uint64_t parent, uint64_t child) { return mm_transition_probability(s, mm_mode_of(s, parent), mm_mode_of(s, child)); };
+    std::string e;
+    const int r = dp_extract_policy(s.dp, false, belief_of, p_of, stream, e);
+    if (r) { set_err(e); return r; }
+    const size_t n = s.dp.pol_original.size();
+    s.pol_xy.resize(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t id = s.dp.pol_original[k];
+        const uint32_t m = mm_mode_of(s, id);
+        const uint64_t local = id - s.mode_off[m];
+        s.pol_xy[2 * k] = mm.modes[m].xy[2 * local]; s.pol_xy[2 * k + 1] = mm.modes[m].xy[2 * local + 1];
+    }
+    s.t_extract = now_s() - t0;
+    s.policy_gen = s.gen;
     return PORRT_OK;
 }
 
@@ -2925,6 +3153,7 @@ void porrt_destroy(porrt_ctx *c) {
     if (c->d_rcarr) (void)hipFree(c->d_rcarr);
     if (c->d_batch_out) (void)hipFree(c->d_batch_out);
     c->mm_scratch.free_all();
+    c->mmp_scratch.free_all();
     c->refine_scratch.free_all();
     for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
@@ -3681,6 +3910,125 @@ int porrt_bg_get_refine_info(const porrt_ctx *c, double *total_s, double *device
     return PORRT_OK;
 }
 
+// ---- the rest of MapShelfDomainTampPRM::plan on the modes of the last porrt_grow_mm_prm (porrt_mmplan.hpp)
+int porrt_mm_build_belief_graph(porrt_ctx *c) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int { return c->mm_build_belief_graph(); });
+}
+static bool mm_graph_ok(const porrt_ctx *c) { return c && c->mm.valid && c->mmp.valid && c->mmp.gen == c->mm.gen; }
+uint64_t porrt_mm_bg_num_nodes(const porrt_ctx *c) { return mm_graph_ok(c) ? c->mmp.NT : 0; }
+uint64_t porrt_mm_bg_num_edges(const porrt_ctx *c) { return mm_graph_ok(c) ? c->mmp.n_edges : 0; }
+uint64_t porrt_mm_bg_num_finals(const porrt_ctx *c) { return mm_graph_ok(c) ? c->mmp.finals.size() : 0; }
+int porrt_mm_bg_get_graph(const porrt_ctx *cc, uint64_t *child_off, uint32_t *child_ids, uint64_t *parent_off, uint32_t *parent_ids, uint8_t *types,
+                          uint32_t *belief_ids, uint64_t *mode_offsets, uint64_t *finals) {
+    porrt_ctx *c = const_cast<porrt_ctx *>(cc);
+    if (!mm_graph_ok(c)) return PORRT_ERR_INVALID;
+    const MmPlanState &s = c->mmp;
+    const size_t N = s.NT, E = s.n_edges;
+    if (hipSetDevice(c->device) != hipSuccess) return PORRT_ERR_DEVICE;
+    hipError_t e = hipSuccess;
+    auto get = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes && e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
+    get(child_off, s.c.child_off, (N + 1) * 8); get(child_ids, s.c.child_id, E * 4);
+    get(parent_off, s.c.par_off, (N + 1) * 8); get(parent_ids, s.c.par_id, E * 4);
+    get(types, s.c.types, N); get(belief_ids, s.d_bid, N * 4);
+    if (e != hipSuccess) return PORRT_ERR_DEVICE;
+    if (mode_offsets) for (size_t m = 0; m <= s.n_modes; ++m) mode_offsets[m] = s.mode_off[m];
+    if (finals) for (size_t k = 0; k < s.finals.size(); ++k) finals[k] = s.finals[k];
+    return PORRT_OK;
+}
+int porrt_mm_compute_expected_costs(porrt_ctx *c) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int { return c->mm_compute_expected_costs(); });
+}
+int porrt_mm_get_expected_costs(const porrt_ctx *c, double *out) {
+    if (!mm_graph_ok(c) || !out || c->mmp.costs_gen != c->mmp.gen || !c->mmp.dp.valid) return PORRT_ERR_INVALID;
+    if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(out, c->mmp.dp.d_dist, c->mmp.NT * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
+    return PORRT_OK;
+}
+int64_t porrt_mm_extract_policy(porrt_ctx *c, uint64_t *ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap, double *expected_cost) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        MmPlanState &s = c->mmp;
+        if (!(s.policy_gen == s.gen && s.dp.have_policy && mm_graph_ok(c) && s.costs_gen == s.gen)) {
+            const int r = c->mm_extract_policy();
+            if (r) return r;
+        }
+        const uint64_t n = s.dp.pol_original.size();
+        if (expected_cost && hipMemcpy(expected_cost, s.dp.d_dist, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
+        if (cap >= n) {
+            for (uint64_t k = 0; k < n; ++k) {
+                if (ids) ids[k] = s.dp.pol_original[k];
+                if (parents) parents[k] = s.dp.pol_parent[k];
+                if (is_leaf) is_leaf[k] = s.dp.pol_leaf[k];
+            }
+            if (xy) memcpy(xy, s.pol_xy.data(), 2 * n * sizeof(double));
+        }
+        return (int)n;
+    });
+}
+int64_t porrt_mm_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, uint64_t *ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap,
+                               double *expected_cost) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        MmPlanState &s = c->mmp;
+        if (!mm_graph_ok(c) || s.costs_gen != s.gen || s.policy_gen != s.gen || !s.dp.have_policy) {
+            c->set_err("mm_refine_policy: no policy to refine -- call porrt_mm_extract_policy after the last porrt_grow_mm_prm, belief graph and expected costs");
+            return PORRT_ERR_INVALID;
+        }
+        const uint64_t n = s.dp.pol_original.size();
+        const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
+        std::vector<uint32_t> row(n);
+        for (uint64_t k = 0; k < n; ++k) row[k] = mm_mode_of(s, s.dp.pol_original[k]);
+        std::vector<unsigned long long> compat(M, 0ull);              // compute_compatibility (common.rs:266-276) of every mode's belief
+        for (uint32_t m = 0; m < M; ++m)
+            for (int v = 0; v < c->n_validities; ++v) {
+                bool ok = true;
+                for (uint32_t w = 0; w < nw && ok; ++w) ok = !(s.beliefs[(size_t)m * nw + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
+                if (ok) compat[m] |= 1ull << v;
+            }
+        porrt_ctx::RefineOut o;
+        const int64_t m = c->refine(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
+                                    compat.data(), n_iterations, false, o);
+        if (m < 0 || cap < (uint64_t)m) return (int)m;                // sizing: no device work
+        const int64_t m2 = c->refine(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
+                                     compat.data(), n_iterations, true, o);
+        if (m2 < 0) return (int)m2;
+        s.t_refine = c->refine_total_s; s.t_refine_device = c->refine_device_s;
+        refine_copy_out(o, xy, ids, parents, is_leaf, expected_cost);
+        return (int)m2;
+    });
+}
+// MapShelfDomainTampPRM::plan (:310-326): grow, belief graph, expected costs, policy; returns the policy's node count
+int64_t porrt_mm_plan(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step, double search_radius,
+                      uint64_t n_iter_per_belief) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        const double t0 = now_s();
+        int r = c->grow_mm_prm(start, initial_belief, n_worlds, max_step, search_radius, n_iter_per_belief);
+        c->mmp.t_grow = now_s() - t0;
+        if (r) return r;
+        if ((r = c->mm_build_belief_graph()) || (r = c->mm_compute_expected_costs()) || (r = c->mm_extract_policy())) return r;
+        return (int)c->mmp.dp.pol_original.size();
+    });
+}
+// seconds of the last steps: grow (porrt_mm_plan only), build, build on the device, expected costs, on the device, policy walk, refine, on the device
+int porrt_mm_get_plan_seconds(const porrt_ctx *c, double *out, uint32_t n) {
+    if (!c || !out) return PORRT_ERR_INVALID;
+    const MmPlanState &s = c->mmp;
+    const double v[8] = {s.t_grow, s.t_build, s.t_build_device, s.t_costs, s.t_costs_device, s.t_extract, s.t_refine, s.t_refine_device};
+    for (uint32_t k = 0; k < n && k < 8; ++k) out[k] = v[k];
+    return PORRT_OK;
+}
+int porrt_mm_get_dp_info(const porrt_ctx *c, uint32_t *levels, uint32_t *launches, uint64_t *sweeps, int *level_schedule) {
+    if (!mm_graph_ok(c) || c->mmp.costs_gen != c->mmp.gen) return PORRT_ERR_INVALID;
+    const MmPlanState &s = c->mmp;
+    if (levels) *levels = s.levels;
+    if (launches) *launches = s.launches;
+    if (sweeps) *sweeps = s.dp.layered ? s.level_sweeps : s.dp.sweeps;
+    if (level_schedule) *level_schedule = s.dp.layered ? 1 : 0;
+    return PORRT_OK;
+}
+
 // conditional_dijkstra on an explicit graph (host arrays in, dist out): the form the reference's own tests call it in
 int porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows,
                                uint32_t n_worlds, const uint8_t *types, const uint64_t *child_off, const uint32_t *child_ids,
@@ -3801,6 +4149,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "graph")) c->opt_graph = value != 0;
     else if (!strcmp(name, "group_lanes")) { if (value != -1 && value != 0 && value != 16 && value != 32 && value != 64) { c->set_err("group_lanes: -1 (auto), 0, 16, 32 or 64"); return PORRT_ERR_INVALID; } c->opt_group_req = (int)value; }
     else if (!strcmp(name, "dp_sweeps")) c->opt_dp_sweeps = value != 0;
+    else if (!strcmp(name, "mm_levels")) c->mmp.use_levels = value != 0;
+    else if (!strcmp(name, "mm_lds_nodes")) c->mmp.lds_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, kMmLdsNodes));
     else if (!strcmp(name, "box_table")) { c->opt_box_table = value != 0; c->cls_dirty = true; }
     else if (!strcmp(name, "gtrack_side")) c->opt_gtrack_side = value != 0;
     else if (!strcmp(name, "pipeline")) {

@@ -35,7 +35,9 @@ struct MmState {
     std::vector<MmMode> modes;
     std::vector<MmTransition> tr;
     double host_s = 0, roadmap_s = 0, device_s = 0;
-    void clear() { valid = false; modes.clear(); tr.clear(); }
+    uint64_t gen = 0;                            // growths of this context: what a belief graph built on the modes belongs to
+    bool dev_edges = false;                      // the roadmaps' nodes and forward edges are still on the device (roadmaps_of_modes)
+    void clear() { valid = false; dev_edges = false; modes.clear(); tr.clear(); }
 };
 
 namespace mmprm {

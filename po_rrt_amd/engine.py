@@ -38,6 +38,9 @@ SYMBOLS = [
     "porrt_host_pin", "porrt_host_unpin", "porrt_exchange_tables", "porrt_comm_test_new_ops", "porrt_comm_usable", "porrt_comm_set_timeout_ms", "porrt_comm_test_new", "porrt_comm_test_fail", "porrt_comm_test_aborts",
     "porrt_grow_mm_prm", "porrt_mm_num_modes", "porrt_mm_num_transitions", "porrt_mm_num_beliefs", "porrt_mm_get_mode", "porrt_mm_get_mode_graph",
     "porrt_mm_get_transition", "porrt_mm_get_transition_pairs", "porrt_mm_get_seconds",
+    "porrt_mm_build_belief_graph", "porrt_mm_bg_num_nodes", "porrt_mm_bg_num_edges", "porrt_mm_bg_num_finals", "porrt_mm_bg_get_graph",
+    "porrt_mm_compute_expected_costs", "porrt_mm_get_expected_costs", "porrt_mm_extract_policy", "porrt_mm_refine_policy", "porrt_mm_plan",
+    "porrt_mm_get_plan_seconds", "porrt_mm_get_dp_info",
     "porrt_read_pgm", "porrt_read_pgm_mem", "porrt_graph_write_json", "porrt_graph_save_json", "porrt_graph_load_json", "porrt_graph_file_free",
     "porrt_graph_file_num_nodes", "porrt_graph_file_num_children", "porrt_graph_file_num_parents", "porrt_graph_file_num_validities",
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
@@ -171,6 +174,17 @@ def load_library():
     sig("porrt_mm_get_transition", C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_uint64))
     sig("porrt_mm_get_transition_pairs", C.c_int, vp, C.c_uint64, C.c_void_p)
     sig("porrt_mm_get_seconds", C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+    sig("porrt_mm_build_belief_graph", C.c_int, vp)
+    for nm in ("nodes", "edges", "finals"):
+        sig("porrt_mm_bg_num_" + nm, C.c_uint64, vp)
+    sig("porrt_mm_bg_get_graph", C.c_int, vp, *([C.c_void_p] * 8))
+    sig("porrt_mm_compute_expected_costs", C.c_int, vp)
+    sig("porrt_mm_get_expected_costs", C.c_int, vp, _f64p)
+    sig("porrt_mm_extract_policy", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_mm_refine_policy", C.c_int64, vp, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_mm_plan", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64)
+    sig("porrt_mm_get_plan_seconds", C.c_int, vp, _f64p, C.c_uint32)
+    sig("porrt_mm_get_dp_info", C.c_int, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int))
     sig("porrt_read_pgm", C.c_int, C.c_char_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
     sig("porrt_read_pgm_mem", C.c_int, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
     sig("porrt_graph_write_json", C.c_int, C.c_char_p, C.c_uint64, _f64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, C.c_uint64, C.c_uint64, _u8p)
@@ -544,6 +558,71 @@ class Engine:
         h, r, d = C.c_double(0), C.c_double(0), C.c_double(0)
         self._chk(self._l.porrt_mm_get_seconds(self._c, C.byref(h), C.byref(r), C.byref(d)))
         return dict(host_s=h.value, roadmap_s=r.value, device_s=d.value)
+
+    # ---- the rest of MapShelfDomainTampPRM::plan (map_shelves_tamp_prm.rs:310-326) on the modes of the last grow_mm_prm
+    def mm_build_belief_graph(self):
+        """build_belief_graph (:395-473) on the device"""
+        self._chk(self._l.porrt_mm_build_belief_graph(self._c))
+
+    def mm_belief_graph(self):
+        """dict(types, belief_ids, children=(off, ids), parents=(off, ids), mode_offsets, finals) of the last mm_build_belief_graph"""
+        L = self._l
+        N, E, F = L.porrt_mm_bg_num_nodes(self._c), L.porrt_mm_bg_num_edges(self._c), L.porrt_mm_bg_num_finals(self._c)
+        M = L.porrt_mm_num_modes(self._c)
+        coff, poff = np.zeros(N + 1, dtype=np.uint64), np.zeros(N + 1, dtype=np.uint64)
+        cid, pid = np.zeros(max(E, 1), dtype=np.uint32), np.zeros(max(E, 1), dtype=np.uint32)
+        types, bid = np.zeros(max(N, 1), dtype=np.uint8), np.zeros(max(N, 1), dtype=np.uint32)
+        moff, fin = np.zeros(M + 1, dtype=np.uint64), np.zeros(max(F, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(L.porrt_mm_bg_get_graph(self._c, p(coff), p(cid), p(poff), p(pid), p(types), p(bid), p(moff), p(fin)))
+        return dict(types=types[:N], belief_ids=bid[:N], children=(coff, cid[:E]), parents=(poff, pid[:E]), mode_offsets=moff, finals=fin[:F])
+
+    def mm_compute_expected_costs(self):
+        self._chk(self._l.porrt_mm_compute_expected_costs(self._c))
+
+    def mm_expected_costs(self, compute=True):
+        """compute_expected_costs_to_goals (:475-477) on the device (unless compute=False: the last ones); dist per belief node"""
+        if compute:
+            self.mm_compute_expected_costs()
+        d = np.zeros(self._l.porrt_mm_bg_num_nodes(self._c))
+        self._chk(self._l.porrt_mm_get_expected_costs(self._c, d))
+        return d
+
+    def mm_extract_policy(self):
+        """extract_policy (:479-485): (belief node ids, parents (-1 = root), leaf flags, states [n, 2]), expected cost of the root"""
+        cost = C.c_double(0.0)
+        n = self._l.porrt_mm_extract_policy(self._c, None, None, None, None, 0, C.byref(cost))
+        if n < 0:
+            self._chk(int(n))
+        oid, par, leaf, xy = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8), np.zeros((n, 2))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(int(self._l.porrt_mm_extract_policy(self._c, p(oid), p(par), p(leaf), p(xy), n, C.byref(cost))))
+        return (oid, par, leaf, xy), cost.value
+
+    def mm_refine_policy(self, n_iterations):
+        """PartialShortCut(n_iterations) of the last mm_extract_policy: (states, belief node ids, parents, leaf flags), expected cost"""
+        return self._refined(lambda xy, oid, par, leaf, cap, cost: self._l.porrt_mm_refine_policy(self._c, int(n_iterations), xy, oid, par, leaf, cap, cost))
+
+    def plan_mm_prm(self, start, belief, max_step, search_radius, n_iter_per_belief, refine_iterations=0):
+        """MapShelfDomainTampPRM::plan (:310-326), then PartialShortCut(refine_iterations) when > 0 (main.rs:546-575):
+        ((belief node ids, parents, leaf flags, states), expected cost)"""
+        b = _f64(belief)
+        self._chk(int(self._l.porrt_mm_plan(self._c, _f64(start), b, len(b), max_step, search_radius, n_iter_per_belief)))
+        if refine_iterations > 0:
+            (xy, oid, par, leaf), cost = self.mm_refine_policy(refine_iterations)
+            return (oid, par, leaf, xy), cost
+        return self.mm_extract_policy()
+
+    def mm_plan_seconds(self):
+        v = np.zeros(8)
+        self._chk(self._l.porrt_mm_get_plan_seconds(self._c, v, 8))
+        keys = ("grow_s", "build_s", "build_device_s", "costs_s", "costs_device_s", "extract_s", "refine_s", "refine_device_s")
+        return dict(zip(keys, v.tolist()))
+
+    def mm_dp_info(self):
+        lv, la, sw, ls = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_int(0)
+        self._chk(self._l.porrt_mm_get_dp_info(self._c, C.byref(lv), C.byref(la), C.byref(sw), C.byref(ls)))
+        return dict(levels=lv.value, launches=la.value, sweeps=sw.value, level_schedule=bool(ls.value))
 
     def save_graph_json(self, path):
         """the PTO graph / PRM roadmap of the last grow as the reference's PTOGraph JSON (pto_graph.rs:22-118)"""

@@ -139,6 +139,22 @@ def benchmark_zone_ids(n):
     return z, goals
 
 
+def benchmark_free_zone_ids(n):
+    """zone k = a 5 x 5 pixel square on free ground in front of a shelf of map_benchmark_like (inside the disks benchmark_like clears
+    around its goals, then four more free spots for 12), so every zone's centroid -- the multi-modal PRM's goal node of that world,
+    map_shelves_tamp_prm.rs:190-196 -- is a free pixel that a roadmap can reach."""
+    spots = [(-0.9, -0.5), (-0.9, 0.0), (-0.9, 0.5), (-0.5, 0.9), (0.5, 0.9), (0.9, 0.5), (0.9, 0.0), (0.9, -0.5)]
+    pos = {4: [(-0.9, 0.0), (-0.5, 0.9), (0.5, 0.9), (0.9, 0.0)], 6: [spots[k] for k in (0, 2, 3, 4, 5, 7)], 8: spots,
+           12: spots + [(-0.5 / 0.92, -0.8 / 0.92), (0.5 / 0.92, -0.8 / 0.92), (-0.3 / 0.92, 0.5 / 0.92), (0.3 / 0.92, 0.5 / 0.92)]}[n]
+    occ = benchmark_like(0)
+    z = np.full((H, W), 255, np.uint8)
+    for k, (gx, gy) in enumerate(pos):
+        i, j = to_pixel(0.92 * gx, 0.92 * gy)
+        assert (occ[i - 2:i + 3, j - 2:j + 3] == 255).all(), "zone %d is not on free ground" % k
+        z[i - 2:i + 3, j - 2:j + 3] = k
+    return z
+
+
 def map1_2_goals_like():
     """Two shelf goals on the right, a dividing wall (pto.rs:466-479)."""
     a = np.full((H, W), 255, np.uint8)
@@ -327,8 +343,13 @@ def paper_zone_ids(occ, rects):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--paper-map", action="store_true", help="re-extract the raster embedded in the reference's map_4 svg")
+    ap.add_argument("--free-zones", action="store_true", help="write only the free-centroid zone rasters of map_benchmark_like")
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    for n in (4, 6, 8, 12):
+        write_pgm(os.path.join(OUT, "map_benchmark_like_%d_free_zone_ids.pgm" % n), benchmark_free_zone_ids(n))
+    if args.free_zones:
+        return
     write_pgm(os.path.join(OUT, "map0_like.pgm"), map0_like())
     write_pgm(os.path.join(OUT, "map_benchmark_like.pgm"), benchmark_like(0))
     for idx, letter in enumerate("abcdefghi"):
