@@ -350,6 +350,8 @@ struct DpState {
     size_t n = 0;
     uint32_t sweeps = 0;
     unsigned long long sweep_rows = 0;                // rows (belief nodes) the sweeps passed over, summed over the sweeps
+    uint32_t levels = 0;                              // layered evaluation: levels of the last run (0 = the general sweeps ran)
+    uint64_t wide_levels = 0;                         //   bit k: level k (k-th smallest number of possible worlds) ran k_dp_level_sweep<1>
     double t_total = 0, t_device = 0;
     std::vector<void *> owned;                        // scratch of the last run (flags, finals); dist lives in a grow-only slot
     size_t dist_cap = 0;
@@ -473,6 +475,8 @@ static int dp_run(DpState &st, DpConst c, bool implicit, const std::vector<unsig
     st.n = n;
     st.last = c;
     st.layered = false;
+    st.levels = 0;
+    st.wide_levels = 0;
     st.sweeps = sweeps;
     st.sweep_rows = sweep_rows;
     st.t_device = 1e-3 * (double)ms;
@@ -481,8 +485,12 @@ static int dp_run(DpState &st, DpConst c, bool implicit, const std::vector<unsig
     return PORRT_OK;
 }
 
+constexpr uint64_t kDpWideRows = 2u << 20;             // a level of at least this many rows (N * W) sweeps wide (option "dp_wide_rows")
+
 // Level-by-level evaluation on the context's belief graph (see above).  Needs what the build left on the device.
-static int dp_run_layered(DpState &st, BeliefGraphState &bg, DpConst c, const std::vector<unsigned long long> &finals, hipStream_t s, std::string &err) {
+// wide_rows: levels of N * W >= wide_rows run k_dp_level_sweep<1>, the others k_dp_level_sweep<4> -- the item buffer is sized by the same test.
+static int dp_run_layered(DpState &st, BeliefGraphState &bg, DpConst c, const std::vector<unsigned long long> &finals, hipStream_t s, std::string &err,
+                          uint64_t wide_rows = kDpWideRows) {
     st.release();
     const double t0 = bg_now();
     const size_t N = bg.N, B = bg.B, n = N * B;
@@ -559,7 +567,7 @@ static int dp_run_layered(DpState &st, BeliefGraphState &bg, DpConst c, const st
         size_t max_items = 0;
         for (auto &lv : levels) {
             const size_t W = lv.second - lv.first, rows = N * W;
-            const size_t items = rows < (2u << 20) ? (rows * 4 + 255) / 256 : N * ((W + 255) / 256);
+            const size_t items = rows < wide_rows ? (rows * 4 + 255) / 256 : N * ((W + 255) / 256);
             max_items = items > max_items ? items : max_items;
         }
         if (st.item_cap < max_items) {
@@ -573,10 +581,13 @@ static int dp_run_layered(DpState &st, BeliefGraphState &bg, DpConst c, const st
         DP_HIP(hipMemsetAsync(st.d_item[0], 0, st.item_cap, s));
         DP_HIP(hipMemsetAsync(st.d_item[1], 0, st.item_cap, s));
     }
-    for (auto &lv : levels) {
+    uint64_t wide_levels = 0;
+    for (size_t li = 0; li < levels.size(); ++li) {
+        const auto &lv = levels[li];
         const uint32_t p0 = lv.first, W = lv.second - lv.first;
         const dim3 grid((unsigned)(((size_t)N * W + 255) / 256)), block(256);
-        const bool split = (size_t)N * W < (2u << 20);                                 // small level: latency bound
+        const bool split = (size_t)N * W < wide_rows;                                  // small level: latency bound
+        if (!split && li < 64) wide_levels |= 1ull << li;
         const dim3 sgrid(split ? (unsigned)(((size_t)N * W * 4 + 255) / 256) : (unsigned)(N * ((W + 255) / 256)));
         hipLaunchKernelGGL(k_dp_level_init, grid, block, 0, s, L, p0, W, st.d_dirty[0], st.d_item[sweeps & 1u], split ? 4u : 1u, sweeps);
         // Groups of sweeps between two looks from the host at "did the group's last sweep still improve something".  Levels of one graph
@@ -616,6 +627,8 @@ static int dp_run_layered(DpState &st, BeliefGraphState &bg, DpConst c, const st
     st.last = c;
     st.sweeps = sweeps;
     st.sweep_rows = sweep_rows;
+    st.levels = (uint32_t)levels.size();
+    st.wide_levels = wide_levels;
     st.layered = true;
     st.t_device = 1e-3 * (double)ms;
     st.t_total = bg_now() - t0;

@@ -269,6 +269,7 @@ struct porrt_ctx {
     uint32_t gt_par = 0;
     bool opt_box_table = true;             // "box_table": a segment whose end pixels' bounding box is all free is not walked (summed-area table; 0 = always walk)
     bool opt_dp_sweeps = false;            // "dp_sweeps": expected costs by whole-graph sweeps instead of layer by layer
+    uint64_t opt_dp_wide_rows = kDpWideRows;   // "dp_wide_rows": a level of the layered costs with N * W >= this sweeps wide (0 = every level)
     uint32_t opt_cand_cap = 2048;
     uint64_t edge_per_node = 256, tie_pool_mult = 16;      // pool sizes: grown and the run replayed when one overflows (as the neighbour lists)
     // ---- device buffers
@@ -1756,7 +1757,7 @@ int porrt_ctx::compute_expected_costs() {
     std::string e;
     // layers solved one after the other when observations always shrink the set of possible worlds (always, in the
     // reference's domains; checked by the build), the general sweeps otherwise or on request (option "dp_sweeps")
-    if (bg.support_shrinks && !opt_dp_sweeps) r = dp_run_layered(dp, bg, c, finals, stream, e);
+    if (bg.support_shrinks && !opt_dp_sweeps) r = dp_run_layered(dp, bg, c, finals, stream, e, opt_dp_wide_rows);
     else r = dp_run(dp, c, true, finals, stream, e);
     if (r) set_err(e);
     return r;
@@ -4138,6 +4139,9 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "kd_lca_steps")) *value = (int64_t)c->counters.lca_next;      // this context's own need: 1 + the last step with a tie that took the structure
     else if (!strcmp(name, "compactions")) *value = c->n_compactions;               // how often the last batch this context led gathered its running rows
     else if (!strcmp(name, "kd_built_after")) *value = c->kd_built_after;           // 1: a tie of the last grow needed the whole kd structure, built after the steps
+    else if (!strcmp(name, "dp_wide_rows")) *value = (int64_t)c->opt_dp_wide_rows;
+    else if (!strcmp(name, "dp_levels")) *value = c->dp.valid ? (int64_t)c->dp.levels : 0;          // levels of the last layered costs (0: the general sweeps ran)
+    else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
 }
@@ -4149,6 +4153,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "graph")) c->opt_graph = value != 0;
     else if (!strcmp(name, "group_lanes")) { if (value != -1 && value != 0 && value != 16 && value != 32 && value != 64) { c->set_err("group_lanes: -1 (auto), 0, 16, 32 or 64"); return PORRT_ERR_INVALID; } c->opt_group_req = (int)value; }
     else if (!strcmp(name, "dp_sweeps")) c->opt_dp_sweeps = value != 0;
+    else if (!strcmp(name, "dp_wide_rows")) c->opt_dp_wide_rows = (uint64_t)std::max<int64_t>(0, value);
     else if (!strcmp(name, "mm_levels")) c->mmp.use_levels = value != 0;
     else if (!strcmp(name, "mm_lds_nodes")) c->mmp.lds_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, kMmLdsNodes));
     else if (!strcmp(name, "box_table")) { c->opt_box_table = value != 0; c->cls_dirty = true; }
