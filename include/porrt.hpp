@@ -555,4 +555,48 @@ private:
     Context ctx_;
 };
 
+enum class TampSearch { AStar, BranchAndBound, BranchAndBoundMultipleViewPoints };   // map_shelves_tamp_rrt.rs:67-71
+
+// MapShelfDomainTampRRT (map_shelves_tamp_rrt.rs:135-291): plan(.., TampSearch::BranchAndBound) on the device
+// (porrt_tamp_rrt_plan).  AStar and BranchAndBoundMultipleViewPoints throw: their expansion order cannot be
+// pinned.  The stream mode, wave width and pool size are the context's options tamp_streams / tamp_wave / tamp_pool.
+class MapShelfDomainTampRRT {
+public:
+    MapShelfDomainTampRRT(const ContinuousSampler &cs, const DiscreteSampler &ds, const MapShelfDomain &m, double goal_radius, int device = 0)
+        : ctx_(device), goal_radius_(goal_radius) {
+        ctx_.set_domain(m);
+        ctx_.check(porrt_set_sampler(ctx_.get(), cs.low.data(), cs.up.data(), cs.seed));
+        ctx_.check(porrt_set_discrete_seed(ctx_.get(), ds.seed));
+    }
+    Policy plan(State start, const BeliefState &initial_belief_state, double max_step, double search_radius, size_t n_iter_min,
+                size_t n_iter_max, TampSearch search, uint32_t batch_K = 128) {
+        if (search != TampSearch::BranchAndBound) throw std::runtime_error("MapShelfDomainTampRRT: only TampSearch::BranchAndBound is supported");
+        const int64_t r = porrt_tamp_rrt_plan(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(), max_step,
+                                              search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
+        if (r < 0) ctx_.check((int)r);
+        const size_t n = (size_t)r, nw = initial_belief_state.size();
+        std::vector<double> xy(2 * n), bel(n * nw);
+        std::vector<int64_t> par(n);
+        std::vector<uint8_t> leaf(n);
+        Policy policy;
+        const int64_t m = porrt_tamp_rrt_policy(ctx_.get(), xy.data(), par.data(), leaf.data(), bel.data(), n, &policy.expected_costs);
+        if (m < 0) ctx_.check((int)m);
+        for (size_t k = 0; k < n; ++k) {
+            PolicyNode pn;
+            pn.state = {xy[2 * k], xy[2 * k + 1]};
+            pn.belief_state.assign(bel.begin() + (ptrdiff_t)(k * nw), bel.begin() + (ptrdiff_t)((k + 1) * nw));
+            pn.original_node_id = 0;
+            policy.nodes.push_back(std::move(pn));
+            if (par[k] >= 0) { policy.nodes[k].parent = (size_t)par[k]; policy.nodes[(size_t)par[k]].children.push_back(k); }
+            if (leaf[k]) policy.leafs.push_back(k);
+        }
+        return policy;
+    }
+    porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
+    const Context &context() const { return ctx_; }
+private:
+    Context ctx_;
+    double goal_radius_;
+};
+
 } // namespace po_rrt

@@ -55,7 +55,9 @@ enum {
     PORRT_ERR_NO_DEVICE = -6,
     PORRT_ERR_IO = -7,              /* a file could not be opened / written (the reference panics: "Impossible to open image") */
     PORRT_ERR_PEER = -8,            /* porrt_exchange_best: another rank of the collective failed; no rank went on */
-    PORRT_ERR_NOMEM = -9            /* a host allocation failed (std::bad_alloc never crosses the boundary) */
+    PORRT_ERR_NOMEM = -9,           /* a host allocation failed (std::bad_alloc never crosses the boundary) */
+    PORRT_ERR_NO_PATH = -10         /* porrt_tamp_rrt_plan: a query found no path (the reference panics: "no observation path found!" /
+                                       "no pickup path found!"); porrt_tamp_rrt_get_info names the search node, the zone and the query */
 };
 
 enum { PORRT_DOMAIN_SHELF = 0, PORRT_DOMAIN_DOOR = 1 };   /* MapShelfDomain / Map */
@@ -486,6 +488,45 @@ typedef struct porrt_tree_device_view_s {
     uint64_t n_nodes;
 } porrt_tree_device_view;
 porrt_tree_device_view porrt_tree_device(const porrt_ctx *ctx);
+
+/* ---- MapShelfDomainTampRRT::plan(.., TampSearch::BranchAndBound) (map_shelves_tamp_rrt.rs:159-291) on the
+ * context's shelf map and zones: a depth-first branch and bound over zone orders whose edges are two RRT* queries each (to see the
+ * zone: ObservationGoal; then to the zone's position: SquareGoal of half-width goal_radius), grown on the device with batch_K, then
+ * build_policy (:619-663): every path of the best chain shortcut (:565-617, 100 iterations) and the policy's expected cost.
+ * Options: "tamp_streams" 0 = one continuous stream across the search in the reference's order (the context's own; set back to
+ * its value at entry on return), 1 (default) = one stream per search edge, seeded from the context's sampler seed and the edge's
+ * zone prefix (splitmix64), which makes the result independent of the expansion order; "tamp_wave" (mode 1) search nodes popped at
+ * once, their queries grown together; "tamp_pool" worker contexts that grow them (made on first use, freed with this context);
+ * "tamp_search" 0 = BranchAndBound, 1 = AStar and 2 = BranchAndBoundMultipleViewPoints are refused (PORRT_ERR_INVALID).
+ * The shuffles draw from the context's discrete sampler, which runs on across plans.  The context's goal is replaced.
+ * Returns the policy's node count, PORRT_ERR_INVALID (n_worlds != zones, a prior whose sum is not within 0.001 of 1),
+ * PORRT_ERR_NO_PATH, or another error. */
+typedef struct {
+    double   search_cost;        /* best expected cost of the search, before the shortcut */
+    double   expected_cost;      /* the policy's, after it */
+    uint64_t search_nodes, queries, waves, pruned;     /* pruned = children not pushed */
+    uint32_t n_order;            /* zones of the best leaf, in the order they are visited */
+    uint32_t zone_order[64];
+    int64_t  fail_node;          /* PORRT_ERR_NO_PATH: the search node whose query found no path (-1 otherwise) */
+    int32_t  fail_zone;          /*   its zone */
+    int32_t  fail_query;         /*   0 = observation, 1 = pickup */
+    double   total_s, grow_s, path_s, shortcut_s, search_s, pool_s, goals_s;   /* seconds: wall, growth, best paths, shortcut, host
+                                    search, worker creation, setting the queries' samplers and goals */
+    uint32_t streams, wave, pool, pad;
+} porrt_tamp_info;
+int64_t  porrt_tamp_rrt_plan(porrt_ctx *ctx, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                             double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K);
+/* the last plan's policy: n = node count; xy n*2, parents n (-1 = root), is_leaf n, beliefs n x n_worlds.  With cap < n only the
+ * count (and the cost) is returned.  Any pointer may be NULL. */
+int64_t  porrt_tamp_rrt_policy(const porrt_ctx *ctx, double *xy, int64_t *parents, uint8_t *is_leaf, double *beliefs, uint64_t cap,
+                               double *expected_cost);
+int      porrt_tamp_rrt_get_info(const porrt_ctx *ctx, porrt_tamp_info *out);
+/* the best path of every context of the last porrt_grow_batch (or porrt_grow) on the device (k_best_cost + k_best_path: no tree is
+ * downloaded); the paths concatenated root first into xy (cap states), lens[q] = 0 for "No solution found", costs[q] (may be NULL;
+ * +inf without a solution).  PORRT_ERR_CAPACITY if one path has more than 1024 states or xy holds fewer than their sum. */
+int      porrt_best_paths(porrt_ctx *const *ctxs, uint32_t n_ctx, double *xy, uint64_t cap, uint64_t *lens, double *costs);
+/* the planner's shortcut on explicit paths, on the device: path i = states [offsets[i], offsets[i + 1]) of xy (n x 2); out like xy */
+int      porrt_tamp_shortcut_paths(porrt_ctx *ctx, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out);
 
 #ifdef __cplusplus
 }

@@ -3247,6 +3247,41 @@ __global__ __launch_bounds__(1024) void k_best_cost(const RunConst *__restrict__
     }
 }
 
+// The best path of every row of a batch (the TAMP search's queries), after k_best_cost on the same rows:
+// the winner that kernel chose (first minimum in final-node order) is walked from its final node to the root and its states are
+// written root first into a shared arena, compacted by an atomic cursor, with length, cost and end state per row.  No tree leaves
+// the device.  status: 0 = path at off, 1 = no final node, 2 = k_best_cost's scratch overflowed (the caller walks on the host),
+// 3 = longer than the row's slot (never truncated).
+struct BestPath {
+    double cost, end_x, end_y;
+    uint32_t len, off, status, pad;
+};
+
+__global__ __launch_bounds__(64) void k_best_path_reset(const RunConst *__restrict__ rcp) {
+    if (threadIdx.x == 0) *rcp[blockIdx.y].bc_cursor = 0;
+}
+
+__global__ __launch_bounds__(64) void k_best_path(const RunConst *__restrict__ rcp, uint32_t row0, uint32_t slot, double2 *__restrict__ arena,
+                                                  uint32_t *__restrict__ cursor, BestPath *__restrict__ out) {
+    if (threadIdx.x) return;
+    const RunConst &rc = rcp[blockIdx.y];
+    const BestCost r = *rc.bc_out;
+    BestPath o;
+    memcpy(&o.cost, &r.cost_bits, 8);
+    o.end_x = o.end_y = 0.0; o.len = 0; o.off = 0; o.pad = 0;
+    o.status = r.overflow ? 2u : (r.final_id == 0xFFFFFFFFu ? 1u : (r.path_len > slot ? 3u : 0u));
+    if (o.status == 0u) {
+        o.len = r.path_len;
+        o.off = atomicAdd(cursor, r.path_len);
+        auto gpar = as_global(rc.parent);
+        auto gx = as_global(rc.nx), gy = as_global(rc.ny);
+        o.end_x = gx[r.final_id]; o.end_y = gy[r.final_id];
+        uint32_t q = r.path_len;
+        for (int p = (int)r.final_id; p >= 0 && q > 0; p = gpar[p]) arena[o.off + --q] = make_double2(gx[p], gy[p]);
+    }
+    out[row0 + blockIdx.y] = o;
+}
+
 // ---- the rows' own step schedules (porrt_grow_batch with per-member n_iter_min / n_iter_max and the reference's loop condition)
 // The plan of a row, a function of (n_iter_min, n_iter_max, K) alone: steps of K iterations up to n_iter_min (the last one
 // shorter), where the condition `i < n_iter_min || (no solution && i < n_iter_max)` (rrt.rs:109, pto.rs:67) is first looked at,

@@ -387,6 +387,13 @@ struct porrt_ctx {
     int roadmap_of_points(const std::vector<double> &xy, double max_step, double search_radius, std::vector<uint32_t> &efrom, std::vector<uint32_t> &eto, double &dev_s);
     MmPlanState mmp;                       // porrt_mm_*: the mode-product belief graph, its expected costs and policy (porrt_mmplan.hpp)
     GrowScratch mmp_scratch;
+    // ---- MapShelfDomainTampRRT (porrt_tamp.hpp): the planner's sampler seed (h_0 of the per-edge streams), its state and options
+    uint64_t s_seed = 0;
+    std::shared_ptr<void> tamp;            //   TampState: worker pool, last policy and info
+    int opt_tamp_streams = 1;              // "tamp_streams": 0 = one stream across the search (the reference's), 1 = one stream per search edge
+    uint32_t opt_tamp_wave = 128;          // "tamp_wave": search nodes popped per wave (tamp_streams = 1; 128: fastest measured)
+    uint32_t opt_tamp_pool = 512;          // "tamp_pool": worker contexts (queries of one porrt_grow_batch)
+    int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints) are refused
     int mm_upload_roadmaps();
     int mm_build_belief_graph();
     int mm_compute_expected_costs();
@@ -3105,6 +3112,8 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
     return PORRT_ERR_CAPACITY;
 }
 
+#include "porrt_tamp.hpp"
+
 extern "C" {
 
 porrt_ctx *porrt_create(int device) {
@@ -3132,6 +3141,7 @@ porrt_ctx *porrt_create(int device) {
 
 void porrt_destroy(porrt_ctx *c) {
     if (!c) return;
+    c->tamp.reset();                          // the TAMP planner's worker contexts and buffers
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (hipStream_t st : c->sub_streams) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -3238,6 +3248,7 @@ int porrt_set_sampler(porrt_ctx *c, const double low[2], const double up[2], uin
     for (int i = 0; i < 2; ++i) { c->s_low[i] = low[i]; c->s_up[i] = up[i]; }
     c->crng.seed_from_u64(seed);
     c->drng.seed_from_u64(seed);
+    c->s_seed = seed;
     c->has_inj = false; c->inj_xy.clear(); c->inj_pos = 0;
     c->has_inj_worlds = false; c->inj_worlds.clear(); c->inj_wpos = 0;
     return PORRT_OK;
@@ -4072,6 +4083,76 @@ int porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const u
     return r;
 }
 
+// ---- MapShelfDomainTampRRT::plan(.., BranchAndBound) (porrt_tamp.hpp)
+int64_t porrt_tamp_rrt_plan(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                            double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() {
+        const int64_t n = tamp_plan(c, start, initial_belief, n_worlds, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K);
+        out = n;
+        return n < 0 ? (int)n : (int)PORRT_OK;
+    });
+    return r < 0 ? r : out;
+}
+
+int64_t porrt_tamp_rrt_policy(const porrt_ctx *cc, double *xy, int64_t *parents, uint8_t *is_leaf, double *beliefs, uint64_t cap, double *expected_cost) {
+    if (!cc || !cc->tamp) return PORRT_ERR_INVALID;
+    const TampState &T = *(const TampState *)cc->tamp.get();
+    if (!T.valid) { const_cast<porrt_ctx *>(cc)->set_err("tamp: no policy (porrt_tamp_rrt_plan first, and it must have succeeded)"); return PORRT_ERR_INVALID; }
+    const uint64_t n = T.parents.size();
+    if (expected_cost) *expected_cost = T.info.expected_cost;
+    if (cap < n) return (int64_t)n;
+    if (xy) memcpy(xy, T.xy.data(), 2 * n * sizeof(double));
+    if (parents) memcpy(parents, T.parents.data(), n * sizeof(int64_t));
+    if (is_leaf) memcpy(is_leaf, T.leaf.data(), n);
+    if (beliefs) memcpy(beliefs, T.beliefs.data(), n * T.nw * sizeof(double));
+    return (int64_t)n;
+}
+
+int porrt_tamp_rrt_get_info(const porrt_ctx *cc, porrt_tamp_info *out) {
+    if (!cc || !out) return PORRT_ERR_INVALID;
+    if (!cc->tamp) { memset(out, 0, sizeof *out); out->fail_node = -1; out->fail_zone = -1; out->fail_query = -1; return PORRT_OK; }
+    *out = ((const TampState *)cc->tamp.get())->info;
+    return PORRT_OK;
+}
+
+int porrt_best_paths(porrt_ctx *const *ctxs, uint32_t n_ctx, double *xy, uint64_t cap, uint64_t *lens, double *costs) {
+    if (!ctxs || !n_ctx || !lens) return PORRT_ERR_INVALID;
+    for (uint32_t q = 0; q < n_ctx; ++q) if (!ctxs[q]) return PORRT_ERR_INVALID;
+    porrt_ctx *c = ctxs[0];
+    return abi_guard([&]() {
+        std::vector<std::vector<double>> paths;
+        std::vector<double> cs;
+        std::vector<char> ok;
+        const int r = tamp_gather(c, tamp_state(c), ctxs, n_ctx, paths, cs, ok);
+        if (r < 0) return r;
+        uint64_t at = 0;
+        for (uint32_t q = 0; q < n_ctx; ++q) {
+            lens[q] = ok[q] ? paths[q].size() / 2 : 0;
+            if (costs) costs[q] = ok[q] ? cs[q] : std::numeric_limits<double>::infinity();
+            if (xy && at + lens[q] <= cap) memcpy(xy + 2 * at, paths[q].data(), paths[q].size() * sizeof(double));
+            at += lens[q];
+        }
+        return at <= cap || !xy ? (int)PORRT_OK : (int)PORRT_ERR_CAPACITY;
+    });
+}
+
+int porrt_tamp_shortcut_paths(porrt_ctx *c, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out) {
+    if (!c || !offsets || !out || (!xy && offsets[n_paths])) return PORRT_ERR_INVALID;
+    if (!c->has_grid) { c->set_err("tamp_shortcut: the shortcut checks segments on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
+    if (offsets[0] != 0) { c->set_err("tamp_shortcut: offsets[0] must be 0"); return PORRT_ERR_INVALID; }
+    for (uint64_t i = 0; i < n_paths; ++i) if (offsets[i + 1] < offsets[i]) { c->set_err("tamp_shortcut: offsets must not decrease"); return PORRT_ERR_INVALID; }
+    return abi_guard([&]() {
+        std::vector<double> v(xy, xy + 2 * offsets[n_paths]);
+        std::vector<uint64_t> off(offsets, offsets + n_paths + 1);
+        const int r = tamp_shortcut_device(c, tamp_state(c), v, off, nullptr);
+        if (r < 0) return r;
+        memcpy(out, v.data(), v.size() * sizeof(double));
+        return (int)PORRT_OK;
+    });
+}
+
 int porrt_get_metrics(const porrt_ctx *c, porrt_metrics *out) {
     if (!c || !out) return PORRT_ERR_INVALID;
     *out = c->metrics;
@@ -4141,6 +4222,10 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "kd_built_after")) *value = c->kd_built_after;           // 1: a tie of the last grow needed the whole kd structure, built after the steps
     else if (!strcmp(name, "dp_wide_rows")) *value = (int64_t)c->opt_dp_wide_rows;
     else if (!strcmp(name, "dp_levels")) *value = c->dp.valid ? (int64_t)c->dp.levels : 0;          // levels of the last layered costs (0: the general sweeps ran)
+    else if (!strcmp(name, "tamp_streams")) *value = c->opt_tamp_streams;
+    else if (!strcmp(name, "tamp_wave")) *value = c->opt_tamp_wave;
+    else if (!strcmp(name, "tamp_pool")) *value = c->opt_tamp_pool;
+    else if (!strcmp(name, "tamp_search")) *value = c->opt_tamp_search;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4178,6 +4263,10 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "host_ranks")) { c->opt_host_ranks = value != 0; c->eo.tag = ~0ull; }
     else if (!strcmp(name, "early_wave_steps")) c->opt_early_wave = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 64));
     else if (!strcmp(name, "kd_group")) c->opt_kd_group = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 8));
+    else if (!strcmp(name, "tamp_streams")) { if (value != 0 && value != 1) { c->set_err("tamp_streams: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_tamp_streams = (int)value; }
+    else if (!strcmp(name, "tamp_wave")) { if (value < 1 || value > 65536) { c->set_err("tamp_wave: 1 .. 65536"); return PORRT_ERR_INVALID; } c->opt_tamp_wave = (uint32_t)value; }
+    else if (!strcmp(name, "tamp_pool")) { if (value < 1 || value > 4096) { c->set_err("tamp_pool: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_tamp_pool = (uint32_t)value; }
+    else if (!strcmp(name, "tamp_search")) { if (value < 0 || value > 2) { c->set_err("tamp_search: 0 (BranchAndBound), 1 (AStar), 2 (BranchAndBoundMultipleViewPoints)"); return PORRT_ERR_INVALID; } c->opt_tamp_search = (int)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again
     if (strcmp(name, "profile") && c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }

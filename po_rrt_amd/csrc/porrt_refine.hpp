@@ -74,7 +74,11 @@ __device__ __forceinline__ double refine_lerp(double a, double b, uint32_t j, ui
     return a * (1.0 - lambda) + b * lambda;
 }
 
-__global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) {
+// kTamp: MapShelfDomainTampRRT::shortcut (map_shelves_tamp_rrt.rs:565-617) instead -- the same draws (a fresh DiscreteSampler::new()
+// per path, n = 100), one wave per path, but a transition is valid iff its traversed space is Free (RTTFuncs, :43-45: no state
+// check, no belief) and the step from the last candidate into node e is not checked at all.
+template <bool kTamp>
+__device__ __forceinline__ void refine_shortcut_body(const RefineConst &c) {
     __shared__ double lx[kRefineLdsNodes], ly[kRefineLdsNodes];
     const uint32_t lane = threadIdx.x;
     const RefinePiece pc = c.pieces[blockIdx.x];
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) {
     __syncthreads();
     TableGrid grid;
     grid.p = rc.cls; grid.W = rc.W;
-    const unsigned long long compat = as_global(c.compat)[pc.belief];
+    const unsigned long long compat = kTamp ? 0ull : as_global(c.compat)[pc.belief];
     const uint2 *dr = c.draws + pc.draws;
     bool fault = false;
     uint2 ahead = make_uint2(0u, 2u);             // the draws do not depend on the commits: lane l holds the draw of iteration it0 + l
@@ -110,7 +114,13 @@ __global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) {
                     const double cn = refine_lerp(a, b, j + 1, s, e);
                     if (jy) ty = cn; else tx = cn;
                 }
-                st = refine_transition(rc, grid, fx, fy, tx, ty, compat);
+                if (!kTamp) {
+                    st = refine_transition(rc, grid, fx, fy, tx, ty, compat);
+                } else if (j + 1 < e) {           // the TAMP shortcut never looks at the step into node e
+                    uint32_t terr = 0;
+                    const int cls = traversed_class(rc, grid, fx, fy, tx, ty, &terr);
+                    st = terr ? 2u : (cls == CLS_FREE ? 0u : 1u);
+                }
             }
             const unsigned long long bad = __ballot(st != 0u);
             if (bad) {                            // the first transition in path order decides: rejected, or a fault
@@ -128,6 +138,9 @@ __global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) {
         for (uint32_t j = lane; j < pc.len; j += 64) { as_global(c.x)[pc.off + j] = lx[j]; as_global(c.y)[pc.off + j] = ly[j]; }
     if (fault && lane == 0) atomicOr(c.err, ERR_RASTER);
 }
+
+__global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) { refine_shortcut_body<false>(c); }
+__global__ __launch_bounds__(64) void k_tamp_shortcut(RefineConst c) { refine_shortcut_body<true>(c); }
 
 // ------------------------------------------------------------------------------------------------ host side
 

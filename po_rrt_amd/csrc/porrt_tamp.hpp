@@ -1,0 +1,545 @@
+// porrt_tamp.hpp -- MapShelfDomainTampRRT::plan(.., TampSearch::BranchAndBound) (src/map_shelves_tamp_rrt.rs:159-291), the
+// reference's third planner, with its RRT queries grown on the device.
+//
+// The search is the reference's depth-first branch and bound over zone orders: a stack of search nodes; a popped node makes one
+// child per remaining zone (a fresh shuffle of its remaining zones per child, from the planner's discrete sampler), runs two RRT
+// queries per child (to see the zone, then to pick the object up from where it was seen), and pushes the child iff its expected
+// cost is below the best leaf's so far.  A popped node without remaining zones is a leaf; among leaves of the lowest cost the last
+// popped one wins (BTreeMap::insert replaces an equal key).  The policy is the chain root .. best leaf, every path shortcut
+// (:565-617, k_tamp_shortcut) and the expected cost of common.rs:131-154.
+//
+// Two stream modes ("tamp_streams"):
+//   0  the reference's: one context (the lead) grows every query in order, its continuous stream running on across the queries;
+//      the stream is set back to its value at entry when the plan returns (the reference's RRT starts from a clone of the sampler).
+//   1  (default) one stream per search edge: the edge with zone prefix z_1 .. z_d runs its two queries back to back on a context
+//      seeded with h_d, h_0 = the lead's sampler seed, h_k = splitmix64(h_{k-1} ^ (z_k + 1)).  A node's cost is then a function of its
+//      prefix alone and only grows along a branch, so the best leaf does not depend on the order of expansion: up to "tamp_wave"
+//      nodes are popped at once, all their children's observation queries grow in one porrt_grow_batch on worker contexts of a pool
+//      ("tamp_pool" contexts, made on first use, kept across calls, freed with the lead), their best paths are gathered on the
+//      device (k_best_path), the pickup queries grow in a second batch, and the children are pushed in the sequential order.
+// Both modes draw the shuffles from the lead's discrete sampler (porrt_set_discrete_seed; RRT growth never draws from it), which
+// runs on across plans.
+#pragma once
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+namespace {
+
+constexpr uint32_t kTampPathSlot = 1024;      // states of one query's best path (a longer one is PORRT_ERR_CAPACITY, never cut short)
+constexpr uint32_t kTampShortcutIterations = 100;   // map_shelves_tamp_rrt.rs:581
+
+static inline uint64_t tamp_splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct TampNode {
+    int32_t target = -1;
+    int64_t parent = -1;
+    std::vector<uint32_t> remaining;
+    double ox = 0, oy = 0;                     // observation_state
+    double rp = 1.0, ec = 0.0;
+    std::vector<double> belief;
+    uint64_t h = 0;                            // stream seed of the edge into this node (tamp_streams = 1)
+    std::vector<double> path_obs, path_pick;   // root first, x y interleaved
+    double obs_cost = 0, pick_cost = 0;
+};
+
+struct TampState {
+    int device = 0;
+    std::vector<porrt_ctx *> pool;
+    uint64_t pool_raster_gen = 0;
+    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging
+    bool valid = false;
+    uint32_t nw = 0;
+    std::vector<double> xy, beliefs;
+    std::vector<int64_t> parents;
+    std::vector<uint8_t> leaf;
+    porrt_tamp_info info;
+    TampState() { memset(&info, 0, sizeof info); info.fail_node = -1; info.fail_zone = -1; info.fail_query = -1; }
+    ~TampState() {
+        for (porrt_ctx *p : pool) porrt_destroy(p);
+        (void)hipSetDevice(device);
+        scratch.free_all();
+    }
+};
+
+static TampState &tamp_state(porrt_ctx *c) {
+    if (!c->tamp) {
+        TampState *t = new TampState();
+        t->device = c->device;
+        c->tamp = std::shared_ptr<void>(t, [](void *q) { delete (TampState *)q; });
+    }
+    return *(TampState *)c->tamp.get();
+}
+
+// a worker context sees what the lead sees: raster, zones, sampler box
+static void tamp_copy_domain(porrt_ctx *d, const porrt_ctx *s) {
+    d->occ = s->occ; d->zones = s->zones;
+    d->W = s->W; d->H = s->H;
+    d->low[0] = s->low[0]; d->low[1] = s->low[1]; d->ppm = s->ppm;
+    d->domain = s->domain; d->has_grid = s->has_grid;
+    d->visibility = s->visibility;
+    d->n_zones = s->n_zones; d->n_worlds = s->n_worlds; d->n_validities = s->n_validities;
+    memcpy(d->zone_pos, s->zone_pos, sizeof d->zone_pos);
+    memcpy(d->validities, s->validities, sizeof d->validities);
+    d->s_low[0] = s->s_low[0]; d->s_low[1] = s->s_low[1]; d->s_up[0] = s->s_up[0]; d->s_up[1] = s->s_up[1];
+    d->opt_box_table = s->opt_box_table;
+    d->cls_dirty = true;
+    ++d->raster_gen;
+}
+
+static int tamp_ensure_pool(porrt_ctx *c, TampState &T, uint32_t want) {
+    if (T.pool_raster_gen != c->raster_gen) {
+        for (porrt_ctx *p : T.pool) tamp_copy_domain(p, c);
+        T.pool_raster_gen = c->raster_gen;
+    }
+    if (T.pool.size() >= want) return PORRT_OK;
+    const double t0 = now_s();
+    while (T.pool.size() < want) {
+        porrt_ctx *p = porrt_create(c->device);
+        if (!p) { c->set_err("tamp: a worker context could not be created"); return PORRT_ERR_DEVICE; }
+        tamp_copy_domain(p, c);
+        T.pool.push_back(p);
+    }
+    T.pool_raster_gen = c->raster_gen;
+    T.info.pool_s += now_s() - t0;
+    return PORRT_OK;
+}
+
+// The best path of every row ctxs[0 .. n) after its growth (rrt.rs:183-193, 223-227): k_best_cost + k_best_path per batch of the
+// call, one download of the rows' descriptors, one of the paths.  paths[q] root first; ok[q] = 0 for "No solution found".
+static int tamp_gather(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, uint32_t n, std::vector<std::vector<double>> &paths,
+                       std::vector<double> &costs, std::vector<char> &ok) {
+    const double t0 = now_s();
+    HIPCHK_CTX(c, hipSetDevice(c->device));
+    BestPath *d_meta = nullptr;
+    double2 *d_arena = nullptr;
+    uint32_t *d_cur = nullptr;
+    HIPCHK_CTX(c, T.scratch.get(0, d_meta, n));
+    HIPCHK_CTX(c, T.scratch.get(1, d_arena, (size_t)n * kTampPathSlot));
+    HIPCHK_CTX(c, T.scratch.get(2, d_cur, 1));
+    hipStream_t st = c->stream;
+    HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
+    for (uint32_t q0 = 0; q0 < n;) {
+        // runs of the argument that are exactly some leader's last batch (as porrt_best_cost_batch): one launch per run
+        porrt_ctx *L = ctxs[q0]->batch_leader;
+        const uint32_t m = L ? L->batch_size : 0;
+        bool run = L != nullptr && m > 0 && q0 + m <= n;
+        for (uint32_t r = 0; r < m && run; ++r) {
+            const porrt_ctx *x = ctxs[q0 + r];
+            run = x->have_results && x->batch_leader == L && x->batch_slot == r && x->n_steps == L->n_steps && x->batch_gen == L->batch_gen_counter;
+        }
+        const RunConst *rcp;
+        uint32_t rows, steps;
+        if (run) { rcp = L->d_rcarr; rows = m; steps = (uint32_t)L->n_steps; }
+        else {
+            porrt_ctx *x = ctxs[q0];
+            if (!x->have_results) { c->set_err("tamp: a query has no results"); return PORRT_ERR_INVALID; }
+            rcp = x->d_rc.p; rows = 1; steps = (uint32_t)x->n_steps;
+        }
+        hipLaunchKernelGGL(k_best_path_reset, dim3(1, rows), dim3(64), 0, st, rcp);
+        hipLaunchKernelGGL(k_best_cost, dim3(1, rows), dim3(1024), 0, st, rcp, steps);
+        hipLaunchKernelGGL(k_best_path, dim3(1, rows), dim3(64), 0, st, rcp, q0, kTampPathSlot, d_arena, d_cur, d_meta);
+        HIPCHK_CTX(c, hipGetLastError());
+        q0 += rows;
+    }
+    std::vector<BestPath> meta(n);
+    HIPCHK_CTX(c, hipMemcpyAsync(meta.data(), d_meta, n * sizeof(BestPath), hipMemcpyDeviceToHost, st));
+    HIPCHK_CTX(c, hipStreamSynchronize(st));
+    size_t total = 0;
+    for (const BestPath &b : meta) if (b.status == 0) total = std::max<size_t>(total, (size_t)b.off + b.len);
+    std::vector<double2> arena(total);
+    if (total) {
+        HIPCHK_CTX(c, hipMemcpyAsync(arena.data(), d_arena, total * sizeof(double2), hipMemcpyDeviceToHost, st));
+        HIPCHK_CTX(c, hipStreamSynchronize(st));
+    }
+    paths.assign(n, {});
+    costs.assign(n, 0.0);
+    ok.assign(n, 0);
+    for (uint32_t q = 0; q < n; ++q) {
+        const BestPath &b = meta[q];
+        if (b.status == 3) { c->set_err("tamp: a best path longer than its slot of " + std::to_string(kTampPathSlot) + " states"); return PORRT_ERR_CAPACITY; }
+        if (b.status == 1) continue;
+        if (b.status == 2) {                     // k_best_cost's scratch was too small: the host walk
+            double hc = 0;
+            const uint64_t len = porrt_best_solution(ctxs[q], nullptr, 0, &hc);
+            if (!len) continue;
+            paths[q].resize(2 * len);
+            porrt_best_solution(ctxs[q], paths[q].data(), len, &hc);
+            costs[q] = hc; ok[q] = 1;
+            continue;
+        }
+        paths[q].resize(2 * (size_t)b.len);
+        for (uint32_t k = 0; k < b.len; ++k) { paths[q][2 * k] = arena[b.off + k].x; paths[q][2 * k + 1] = arena[b.off + k].y; }
+        costs[q] = b.cost; ok[q] = 1;
+    }
+    T.info.path_s += now_s() - t0;
+    return PORRT_OK;
+}
+
+// shortcut (map_shelves_tamp_rrt.rs:565-617) of every path, in place: one wave per path of >= 3 states, one launch
+static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> &xy, const std::vector<uint64_t> &off, double *dev_s) {
+    const size_t n_paths = off.size() - 1, ns = off.back();
+    std::vector<RefinePiece> longs;
+    std::vector<std::pair<uint32_t, uint32_t>> len_at;
+    std::unordered_map<uint32_t, uint32_t> draws_of;
+    const uint32_t n_iter = kTampShortcutIterations;
+    for (size_t i = 0; i < n_paths; ++i) {
+        const uint64_t len = off[i + 1] - off[i];
+        if (len <= 2) continue;                  // :570-572
+        if (len >= (1ull << 31)) { c->set_err("tamp_shortcut: a path of 2^31 states or more"); return PORRT_ERR_INVALID; }
+        auto found = draws_of.find((uint32_t)len);
+        uint32_t at;
+        if (found == draws_of.end()) { at = (uint32_t)(len_at.size() * n_iter); len_at.push_back({(uint32_t)len, at}); draws_of[(uint32_t)len] = at; }
+        else at = found->second;
+        longs.push_back({(uint32_t)off[i], (uint32_t)len, at, 0u});
+    }
+    if (dev_s) *dev_s = 0.0;
+    if (longs.empty()) return PORRT_OK;
+    if (ns >= (1ull << 31)) { c->set_err("tamp_shortcut: too many states"); return PORRT_ERR_INVALID; }
+    HIPCHK_CTX(c, hipSetDevice(c->device));
+    c->classify_raster();
+    uint8_t *d_raster = nullptr;
+    HIPCHK_CTX(c, c->refine_scratch.get(0, d_raster, c->cls.size()));
+    if (c->refine_raster_gen != c->raster_gen) {
+        HIPCHK_CTX(c, hipMemcpyAsync(d_raster, c->cls.data(), c->cls.size(), hipMemcpyHostToDevice, c->stream));
+        c->refine_raster_gen = c->raster_gen;
+    }
+    RunConst g;
+    memset(&g, 0, sizeof g);
+    g.cls = d_raster; g.clr = d_raster + (size_t)c->W * c->H;
+    g.sat = c->opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(c->W, c->H)) : nullptr;
+    g.W = c->W; g.H = c->H; g.low0 = c->low[0]; g.low1 = c->low[1]; g.ppm = c->ppm; g.domain = c->domain; g.has_grid = c->has_grid;
+    g.n_validities = c->n_validities;
+    for (int i = 0; i < c->n_validities; ++i) g.validities[i] = c->validities[i];
+    // one staging area: RunConst | paths | draws | x | y | error word
+    auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t nd = len_at.size() * n_iter;
+    const size_t o_pc = up8(sizeof(RunConst)), o_dr = o_pc + up8(longs.size() * sizeof(RefinePiece)), o_x = o_dr + up8(nd * sizeof(uint2)),
+                 o_y = o_x + ns * 8, o_err = o_y + ns * 8, bytes = o_err + 16;
+    std::vector<uint8_t> stage(bytes, 0);
+    memcpy(stage.data(), &g, sizeof g);
+    memcpy(stage.data() + o_pc, longs.data(), longs.size() * sizeof(RefinePiece));
+    uint2 *dr = (uint2 *)(stage.data() + o_dr);
+    for (const auto &la : len_at) {              // DiscreteSampler::new() per path (:576-584): partial_shortcut's sequence
+        Pcg64 rng;
+        rng.seed_from_u64(0);
+        const uint64_t L = la.first;
+        for (uint32_t it = 0; it < n_iter; ++it) {
+            const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
+            const uint32_t s = (uint32_t)rng.gen_range_usize(L - 2);
+            const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(L - s - 2);
+            dr[la.second + it] = make_uint2(s | (joint << 31), e);
+        }
+    }
+    double *sx = (double *)(stage.data() + o_x), *sy = (double *)(stage.data() + o_y);
+    for (size_t k = 0; k < ns; ++k) { sx[k] = xy[2 * k]; sy[k] = xy[2 * k + 1]; }
+    uint8_t *d = nullptr;
+    HIPCHK_CTX(c, T.scratch.get(3, d, bytes));
+    for (int k = 0; k < 2; ++k) if (!c->refine_ev[k]) HIPCHK_CTX(c, hipEventCreate(&c->refine_ev[k]));
+    RefineConst rc{};
+    rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = nullptr;
+    rc.draws = (const uint2 *)(d + o_dr); rc.x = (double *)(d + o_x); rc.y = (double *)(d + o_y); rc.err = (uint32_t *)(d + o_err);
+    rc.n_pieces = (uint32_t)longs.size(); rc.n_iter = n_iter;
+    HIPCHK_CTX(c, hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK_CTX(c, hipEventRecord(c->refine_ev[0], c->stream));
+    hipLaunchKernelGGL(k_tamp_shortcut, dim3(rc.n_pieces), dim3(64), 0, c->stream, rc);
+    HIPCHK_CTX(c, hipGetLastError());
+    HIPCHK_CTX(c, hipEventRecord(c->refine_ev[1], c->stream));
+    HIPCHK_CTX(c, hipMemcpyAsync(stage.data() + o_x, d + o_x, bytes - o_x, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK_CTX(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK_CTX(c, hipEventElapsedTime(&ms, c->refine_ev[0], c->refine_ev[1]));
+    if (dev_s) *dev_s = 1e-3 * (double)ms;
+    uint32_t err = 0;
+    memcpy(&err, stage.data() + o_err, 4);
+    if (err) { c->set_err("tamp_shortcut: a segment reads outside the raster (the reference panics)"); return PORRT_ERR_RASTER; }
+    for (size_t k = 0; k < ns; ++k) { xy[2 * k] = sx[k]; xy[2 * k + 1] = sy[k]; }
+    return PORRT_OK;
+}
+
+static std::vector<uint32_t> tamp_shuffled(const std::vector<uint32_t> &v, Pcg64 &rng) {     // :20-32
+    std::vector<uint32_t> to = v, out;
+    out.reserve(v.size());
+    while (!to.empty()) {
+        const size_t i = (size_t)rng.gen_range_usize(to.size());
+        out.push_back(to[i]);
+        to[i] = to.back();                       // swap_remove
+        to.pop_back();
+    }
+    return out;
+}
+
+static void tamp_normalize(std::vector<double> &b) {
+    double s = 0.0;
+    for (double p : b) s = s + p;
+    for (double &p : b) p = p / s;
+}
+
+static double tamp_transition_probability(const double *parent, const double *child, uint32_t nw) {     // common.rs:188-190
+    double s = 0.0;
+    for (uint32_t w = 0; w < nw; ++w) s = s + (child[w] > 0.0 ? parent[w] : 0.0);
+    return s;
+}
+
+// build_policy (:619-663) on the chain root .. leaf
+static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id) {
+    std::vector<int64_t> chain;
+    for (int64_t k = leaf_id; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
+    std::reverse(chain.begin(), chain.end());
+    std::vector<double> xy;
+    std::vector<uint64_t> off{0};
+    for (int64_t k : chain) {
+        const TampNode &sn = nodes[(size_t)k];
+        xy.insert(xy.end(), sn.path_obs.begin(), sn.path_obs.end());
+        off.push_back(xy.size() / 2);
+        xy.insert(xy.end(), sn.path_pick.begin(), sn.path_pick.end());
+        off.push_back(xy.size() / 2);
+    }
+    const double t0 = now_s();
+    double dev_s = 0.0;
+    const int r = tamp_shortcut_device(c, T, xy, off, &dev_s);
+    if (r < 0) return r;
+    T.info.shortcut_s = now_s() - t0;
+    const uint32_t nw = T.nw;
+    T.xy.clear(); T.parents.clear(); T.leaf.clear(); T.beliefs.clear();
+    auto add = [&](double x, double y, const std::vector<double> &b, bool is_leaf) {
+        T.xy.push_back(x); T.xy.push_back(y);
+        T.parents.push_back(-1);
+        T.leaf.push_back(is_leaf ? 1 : 0);
+        T.beliefs.insert(T.beliefs.end(), b.begin(), b.end());
+        return (int64_t)T.parents.size() - 1;
+    };
+    int64_t last_obs = 0;
+    for (size_t i = 0; i < chain.size(); ++i) {
+        const TampNode &sn = nodes[(size_t)chain[i]];
+        int64_t prev = last_obs;
+        for (uint64_t k = off[2 * i]; k < off[2 * i + 1]; ++k) {
+            const int64_t id = add(xy[2 * k], xy[2 * k + 1], sn.belief, false);
+            if (id != prev) T.parents[(size_t)id] = prev;
+            prev = id;
+        }
+        last_obs = prev;
+        const uint64_t p0 = off[2 * i + 1], p1 = off[2 * i + 2];
+        std::vector<double> b(sn.belief);
+        if (p1 > p0) {
+            for (uint32_t w = 0; w < nw; ++w) if ((int32_t)w != sn.target) b[w] = 0.0;
+            tamp_normalize(b);
+        }
+        for (uint64_t k = p0; k < p1; ++k) {
+            const int64_t id = add(xy[2 * k], xy[2 * k + 1], b, k + 1 == p1);
+            if (id != prev) T.parents[(size_t)id] = prev;
+            prev = id;
+        }
+    }
+    T.info.expected_cost = refine_expected_cost(T.parents, T.xy, [&](uint32_t a, uint32_t b2) {
+        return tamp_transition_probability(T.beliefs.data() + (size_t)a * nw, T.beliefs.data() + (size_t)b2 * nw, nw);
+    });
+    return PORRT_OK;
+}
+
+static int tamp_fail(porrt_ctx *c, TampState &T, int64_t node, int32_t zone, int32_t query) {
+    T.info.fail_node = node; T.info.fail_zone = zone; T.info.fail_query = query;
+    c->set_err(std::string(query == 0 ? "no observation path found!" : "no pickup path found!") + " (search node " + std::to_string(node) +
+               ", zone " + std::to_string(zone) + ")");
+    return PORRT_ERR_NO_PATH;
+}
+
+static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
+                         uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
+    const double t_start = now_s();
+    if (c->opt_tamp_search != 0) {
+        c->set_err(c->opt_tamp_search == 1 ? "tamp: TampSearch::AStar is not supported (its expansion order cannot be pinned)"
+                                           : "tamp: TampSearch::BranchAndBoundMultipleViewPoints is not supported (it walks a HashSet)");
+        return PORRT_ERR_INVALID;
+    }
+    if (!c->has_grid || c->zones.empty() || c->domain != PORRT_DOMAIN_SHELF) { c->set_err("tamp: needs a shelf map with zones (porrt_set_grid, porrt_set_zones)"); return PORRT_ERR_INVALID; }
+    if (!start || !belief || nw != (uint32_t)c->n_zones) { c->set_err("tamp: n_worlds must equal the number of zones"); return PORRT_ERR_INVALID; }
+    double sum = 0.0;
+    for (uint32_t w = 0; w < nw; ++w) sum = sum + belief[w];
+    if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp: the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
+    if (K == 0 || K > 4096) { c->set_err("batch_K must be in 1..4096"); return PORRT_ERR_INVALID; }
+    if (!(goal_radius >= 0.0)) { c->set_err("tamp: goal_radius"); return PORRT_ERR_INVALID; }
+    TampState &T = tamp_state(c);
+    T.valid = false;
+    memset(&T.info, 0, sizeof T.info);
+    T.info.fail_node = -1; T.info.fail_zone = -1; T.info.fail_query = -1;
+    T.nw = nw;
+    const uint32_t streams = c->opt_tamp_streams ? 1u : 0u;
+    const uint32_t wave = streams ? std::max<uint32_t>(1u, c->opt_tamp_wave) : 1u;
+    const uint32_t pool_cap = std::max<uint32_t>(1u, c->opt_tamp_pool);
+    T.info.streams = streams; T.info.wave = wave;
+    const uint32_t nz = (uint32_t)c->n_zones;
+    std::vector<TampNode> nodes(1);
+    {
+        TampNode &root = nodes[0];
+        std::vector<uint32_t> all(nz);
+        for (uint32_t z = 0; z < nz; ++z) all[z] = z;
+        root.remaining = tamp_shuffled(all, c->drng);
+        root.ox = start[0]; root.oy = start[1];
+        root.belief.assign(belief, belief + nw);
+        root.h = c->s_seed;
+    }
+    std::vector<int64_t> stack{0};
+    double best = std::numeric_limits<double>::infinity();
+    int64_t best_leaf = -1;
+    const Pcg64 crng0 = c->crng;
+    struct Restore { porrt_ctx *c; Pcg64 s; bool on; ~Restore() { if (on) c->crng = s; } } restore{c, crng0, streams == 0};
+    std::vector<std::vector<double>> paths;
+    std::vector<double> costs;
+    std::vector<char> ok;
+    while (!stack.empty()) {
+        std::vector<int64_t> popped;
+        while (!stack.empty() && popped.size() < wave) { popped.push_back(stack.back()); stack.pop_back(); }
+        ++T.info.waves;
+        // children in the sequential order, with their shuffles
+        std::vector<std::pair<int64_t, std::vector<int64_t>>> made;
+        std::vector<int64_t> edges;
+        for (int64_t uid : popped) {
+            std::vector<int64_t> kids;
+            const std::vector<uint32_t> rem_u = nodes[(size_t)uid].remaining;
+            for (uint32_t t : rem_u) {
+                std::vector<uint32_t> sh = tamp_shuffled(rem_u, c->drng);
+                TampNode v;
+                const TampNode &u = nodes[(size_t)uid];
+                for (uint32_t z : sh) if (z != t) v.remaining.push_back(z);
+                v.belief = u.belief;
+                if (u.target >= 0) v.belief[(size_t)u.target] = 0.0;
+                tamp_normalize(v.belief);
+                v.rp = u.rp * tamp_transition_probability(u.belief.data(), v.belief.data(), nw);
+                v.target = (int32_t)t;
+                v.parent = uid;
+                v.h = tamp_splitmix64(u.h ^ ((uint64_t)t + 1));
+                kids.push_back((int64_t)nodes.size());
+                edges.push_back((int64_t)nodes.size());
+                nodes.push_back(std::move(v));
+            }
+            made.push_back({uid, std::move(kids)});
+        }
+        T.info.search_nodes = nodes.size();
+        // the queries
+        if (streams == 0) {
+            for (int64_t vid : edges) {
+                TampNode &v = nodes[(size_t)vid];
+                const TampNode &u = nodes[(size_t)v.parent];
+                for (int which = 0; which < 2; ++which) {
+                    double t0 = now_s();
+                    int r = which == 0 ? porrt_set_observation_goal(c, (uint32_t)v.target) : [&]() {
+                        const uint64_t m1 = 1;
+                        return porrt_set_square_goal(c, c->zone_pos[v.target], &m1, 1, goal_radius);
+                    }();
+                    T.info.goals_s += now_s() - t0;
+                    if (r < 0) return r;
+                    const double st[2] = {which == 0 ? u.ox : v.ox, which == 0 ? u.oy : v.oy};
+                    t0 = now_s();
+                    r = c->grow(st, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
+                    T.info.grow_s += now_s() - t0;
+                    ++T.info.queries;
+                    if (r < 0) return r;
+                    porrt_ctx *one = c;
+                    r = tamp_gather(c, T, &one, 1, paths, costs, ok);
+                    if (r < 0) return r;
+                    if (!ok[0]) return tamp_fail(c, T, vid, v.target, which);
+                    if (which == 0) {
+                        v.path_obs = std::move(paths[0]); v.obs_cost = costs[0];
+                        v.ox = v.path_obs[v.path_obs.size() - 2]; v.oy = v.path_obs.back();
+                    } else {
+                        v.path_pick = std::move(paths[0]); v.pick_cost = costs[0];
+                    }
+                }
+            }
+        } else {
+            for (size_t e0 = 0; e0 < edges.size(); e0 += pool_cap) {
+                const uint32_t m = (uint32_t)std::min<size_t>(pool_cap, edges.size() - e0);
+                int r = tamp_ensure_pool(c, T, m);
+                if (r < 0) return r;
+                std::vector<double> starts(2 * (size_t)m);
+                double t0 = now_s();
+                for (uint32_t i = 0; i < m; ++i) {
+                    const TampNode &v = nodes[(size_t)edges[e0 + i]];
+                    const TampNode &u = nodes[(size_t)v.parent];
+                    if ((r = porrt_set_sampler(T.pool[i], c->s_low, c->s_up, v.h)) < 0) return r;
+                    if ((r = porrt_set_observation_goal(T.pool[i], (uint32_t)v.target)) < 0) return r;
+                    starts[2 * i] = u.ox; starts[2 * i + 1] = u.oy;
+                }
+                T.info.goals_s += now_s() - t0;
+                t0 = now_s();
+                r = porrt_grow_batch(T.pool.data(), m, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
+                T.info.grow_s += now_s() - t0;
+                T.info.queries += m;
+                if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                if ((r = tamp_gather(c, T, T.pool.data(), m, paths, costs, ok)) < 0) return r;
+                uint32_t first_bad = m;
+                for (uint32_t i = 0; i < m && first_bad == m; ++i) if (!ok[i]) first_bad = i;
+                for (uint32_t i = 0; i < first_bad; ++i) {
+                    TampNode &v = nodes[(size_t)edges[e0 + i]];
+                    v.path_obs = std::move(paths[i]); v.obs_cost = costs[i];
+                    v.ox = v.path_obs[v.path_obs.size() - 2]; v.oy = v.path_obs.back();
+                    starts[2 * i] = v.ox; starts[2 * i + 1] = v.oy;
+                }
+                // the pickup queries of the rows before the first failure, on the same contexts: their streams run on
+                const uint32_t mp = first_bad;
+                if (mp) {
+                    t0 = now_s();
+                    for (uint32_t i = 0; i < mp; ++i) {
+                        const TampNode &v = nodes[(size_t)edges[e0 + i]];
+                        const uint64_t m1 = 1;
+                        if ((r = porrt_set_square_goal(T.pool[i], c->zone_pos[v.target], &m1, 1, goal_radius)) < 0) return r;
+                    }
+                    T.info.goals_s += now_s() - t0;
+                    t0 = now_s();
+                    r = porrt_grow_batch(T.pool.data(), mp, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
+                    T.info.grow_s += now_s() - t0;
+                    T.info.queries += mp;
+                    if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                    if ((r = tamp_gather(c, T, T.pool.data(), mp, paths, costs, ok)) < 0) return r;
+                    for (uint32_t i = 0; i < mp; ++i) {
+                        TampNode &v = nodes[(size_t)edges[e0 + i]];
+                        if (!ok[i]) return tamp_fail(c, T, edges[e0 + i], v.target, 1);
+                        v.path_pick = std::move(paths[i]); v.pick_cost = costs[i];
+                    }
+                }
+                if (first_bad < m) return tamp_fail(c, T, edges[e0 + first_bad], nodes[(size_t)edges[e0 + first_bad]].target, 0);
+            }
+        }
+        // push the children, record the leaves: the sequential order
+        for (const auto &mk : made) {
+            const TampNode &u = nodes[(size_t)mk.first];
+            for (int64_t vid : mk.second) {
+                TampNode &v = nodes[(size_t)vid];
+                v.ec = u.ec + v.rp * (v.obs_cost + v.belief[(size_t)v.target] * v.pick_cost);
+                if (v.ec < best) stack.push_back(vid);
+                else ++T.info.pruned;
+            }
+            if (u.remaining.empty()) {
+                if (u.ec < best) best = u.ec;
+                if (best_leaf < 0 || u.ec <= nodes[(size_t)best_leaf].ec) best_leaf = mk.first;
+            }
+        }
+    }
+    T.info.search_nodes = nodes.size();
+    T.info.search_cost = nodes[(size_t)best_leaf].ec;
+    T.info.n_order = 0;
+    {
+        std::vector<uint32_t> order;
+        for (int64_t k = best_leaf; k > 0; k = nodes[(size_t)k].parent) order.push_back((uint32_t)nodes[(size_t)k].target);
+        std::reverse(order.begin(), order.end());
+        for (uint32_t z : order) T.info.zone_order[T.info.n_order++] = z;
+    }
+    restore.on = false;
+    if (streams == 0) c->crng = crng0;
+    const int r = tamp_build_policy(c, T, nodes, best_leaf);
+    if (r < 0) return r;
+    T.valid = true;
+    T.info.pool = (uint32_t)T.pool.size();
+    T.info.total_s = now_s() - t_start;
+    T.info.search_s = T.info.total_s - T.info.grow_s - T.info.path_s - T.info.shortcut_s - T.info.pool_s - T.info.goals_s;
+    return (int64_t)T.parents.size();
+}
+
+} // namespace

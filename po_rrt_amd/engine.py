@@ -44,6 +44,7 @@ SYMBOLS = [
     "porrt_read_pgm", "porrt_read_pgm_mem", "porrt_graph_write_json", "porrt_graph_save_json", "porrt_graph_load_json", "porrt_graph_file_free",
     "porrt_graph_file_num_nodes", "porrt_graph_file_num_children", "porrt_graph_file_num_parents", "porrt_graph_file_num_validities",
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
+    "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
 ]
 
 
@@ -52,6 +53,16 @@ class Metrics(C.Structure):
                 ("n_tie_fallbacks", C.c_uint64), ("total_s", C.c_double), ("setup_s", C.c_double),
                 ("device_s", C.c_double), ("scan_s", C.c_double), ("scan_launches", C.c_uint64),
                 ("scan_pairs", C.c_double), ("scan_bytes", C.c_double), ("connect_s", C.c_double)]
+
+
+class TampInfo(C.Structure):
+    """porrt_tamp_info"""
+    _fields_ = [("search_cost", C.c_double), ("expected_cost", C.c_double), ("search_nodes", C.c_uint64), ("queries", C.c_uint64),
+                ("waves", C.c_uint64), ("pruned", C.c_uint64), ("n_order", C.c_uint32), ("zone_order", C.c_uint32 * 64),
+                ("fail_node", C.c_int64), ("fail_zone", C.c_int32), ("fail_query", C.c_int32),
+                ("total_s", C.c_double), ("grow_s", C.c_double), ("path_s", C.c_double), ("shortcut_s", C.c_double),
+                ("search_s", C.c_double), ("pool_s", C.c_double), ("goals_s", C.c_double),
+                ("streams", C.c_uint32), ("wave", C.c_uint32), ("pool", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class TreeDeviceView(C.Structure):
@@ -194,6 +205,11 @@ def load_library():
     for nm in ("nodes", "children", "parents", "validities", "worlds"):
         sig("porrt_graph_file_num_" + nm, C.c_uint64, vp)
     sig("porrt_graph_file_get", C.c_int, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+    sig("porrt_tamp_rrt_plan", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_double, C.c_uint32)
+    sig("porrt_tamp_rrt_policy", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_tamp_rrt_get_info", C.c_int, vp, C.POINTER(TampInfo))
+    sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
+    sig("porrt_tamp_shortcut_paths", C.c_int, vp, C.c_void_p, _u64p, C.c_uint64, C.c_void_p)
     _LIB = L
     return L
 
@@ -303,6 +319,64 @@ class Engine:
 
     def num_final(self):
         return self._l.porrt_num_final(self._c)
+
+    TAMP_SEARCH = {"branch_and_bound": 0, "astar": 1, "branch_and_bound_multiple_viewpoints": 2}
+
+    def plan_tamp_rrt(self, start, belief, max_step=0.1, search_radius=2.0, n_iter_min=2500, n_iter_max=10000, goal_radius=0.05,
+                      batch_K=128, search="branch_and_bound"):
+        """MapShelfDomainTampRRT::plan(.., TampSearch) (porrt_tamp_rrt_plan): dict of the policy (xy, parents, is_leaf, beliefs,
+        expected_cost) and the search's info.  Stream mode, wave width and pool size are the options tamp_streams / tamp_wave /
+        tamp_pool.  Only branch_and_bound is supported; the other two search kinds raise PorrtError (PORRT_ERR_INVALID)."""
+        if search not in self.TAMP_SEARCH:
+            raise ValueError("search: one of %s" % sorted(self.TAMP_SEARCH))
+        keep = self.get_option("tamp_search")
+        self.set_option("tamp_search", self.TAMP_SEARCH[search])
+        try:
+            b = _f64(belief)
+            n = self._chk(self._l.porrt_tamp_rrt_plan(self._c, _f64(start), b, b.size, max_step, search_radius, n_iter_min, n_iter_max,
+                                                       goal_radius, batch_K))
+        finally:
+            self.set_option("tamp_search", keep)
+        xy, par = np.zeros((n, 2)), np.zeros(n, dtype=np.int64)
+        leaf, bel = np.zeros(n, dtype=np.uint8), np.zeros((n, b.size))
+        cost = C.c_double(0.0)
+        self._chk(self._l.porrt_tamp_rrt_policy(self._c, xy.ctypes.data, par.ctypes.data, leaf.ctypes.data, bel.ctypes.data, n,
+                                                C.byref(cost)))
+        out = dict(xy=xy, parents=par, is_leaf=leaf, beliefs=bel, expected_cost=cost.value)
+        out.update(self.tamp_info())
+        return out
+
+    def tamp_info(self):
+        i = TampInfo()
+        self._chk(self._l.porrt_tamp_rrt_get_info(self._c, C.byref(i)))
+        d = {k: getattr(i, k) for k, _ in TampInfo._fields_ if k not in ("zone_order", "n_order", "pad")}
+        d["zone_order"] = [int(i.zone_order[k]) for k in range(i.n_order)]
+        return d
+
+    @staticmethod
+    def best_paths(engines):
+        """porrt_best_paths: [(path n x 2, cost) or None] per engine of the last grow_batch, gathered on the device"""
+        L = engines[0]._l
+        arr = (C.c_void_p * len(engines))(*[e._c for e in engines])
+        lens, costs = np.zeros(len(engines), dtype=np.uint64), np.zeros(len(engines))
+        engines[0]._chk(L.porrt_best_paths(arr, len(engines), None, 0, lens, costs))
+        xy = np.zeros((max(int(lens.sum()), 1), 2))
+        engines[0]._chk(L.porrt_best_paths(arr, len(engines), xy.ctypes.data, int(lens.sum()), lens, costs))
+        out, at = [], 0
+        for n, c in zip(lens.tolist(), costs.tolist()):
+            out.append((xy[at:at + n].copy(), c) if n else None)
+            at += n
+        return out
+
+    def tamp_shortcut(self, paths):
+        """the planner's shortcut (map_shelves_tamp_rrt.rs:565-617) of each path (a list of n x 2 arrays), on the device"""
+        arrs = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 2)) for p in paths]
+        off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(a) for a in arrs]) if arrs else []
+        xy = np.concatenate(arrs) if arrs and off[-1] else np.zeros((0, 2))
+        out = np.zeros_like(xy)
+        self._chk(self._l.porrt_tamp_shortcut_paths(self._c, xy.ctypes.data, off, len(arrs), out.ctypes.data))
+        return [out[int(off[k]):int(off[k + 1])].copy() for k in range(len(arrs))]
 
     def get_option(self, name):
         v = C.c_int64(0)
