@@ -493,6 +493,27 @@ public:
         for (size_t k = 0; k < (size_t)n; ++k) path[k] = {xy[2 * k], xy[2 * k + 1]};
         return path;
     }
+    // plan_path for every (start, goal) pair in one call (porrt_prm_plan_paths): paths[i] == plan_path(queries[i].first, queries[i].second)
+    std::vector<std::vector<State>> plan_paths(const std::vector<std::pair<State, State>> &queries) {
+        const size_t n = queries.size();
+        std::vector<double> s(2 * n), g(2 * n);
+        for (size_t i = 0; i < n; ++i) {
+            s[2 * i] = queries[i].first[0]; s[2 * i + 1] = queries[i].first[1];
+            g[2 * i] = queries[i].second[0]; g[2 * i + 1] = queries[i].second[1];
+        }
+        std::vector<uint64_t> off(n + 1);
+        const int64_t total = porrt_prm_plan_paths(ctx_.get(), s.data(), g.data(), (uint64_t)n, off.data(), nullptr, 0);
+        if (total < 0) ctx_.check((int)total);
+        std::vector<double> xy(2 * (size_t)total);
+        if (total) {
+            const int64_t r = porrt_prm_get_paths(ctx_.get(), xy.data(), (uint64_t)total);
+            if (r < 0) ctx_.check((int)r);
+        }
+        std::vector<std::vector<State>> paths(n);
+        for (size_t i = 0; i < n; ++i)
+            for (uint64_t k = off[i]; k < off[i + 1]; ++k) paths[i].push_back({xy[2 * k], xy[2 * k + 1]});
+        return paths;
+    }
 private:
     Context ctx_;
     State start_{0.0, 0.0};

@@ -186,6 +186,26 @@ int      porrt_grow_prm(porrt_ctx *ctx, const double start[2], double max_step, 
  * fixpoint), extract_path (pto_graph.rs:305-326).  Returns the number of states of the path (0 = start and goal are not
  * connected: the reference returns an empty Vec); path_xy receives min(cap, that number) states. */
 int64_t  porrt_prm_plan_path(porrt_ctx *ctx, const double start[2], const double goal[2], double *path_xy, uint64_t cap);
+/* PRM::plan_path (src/prm.rs:111-123) for n start/goal pairs on the roadmap of the last porrt_grow_prm, in one call.
+ * Query i is answered exactly as porrt_prm_plan_path(ctx, starts + 2i, goals + 2i, ..) would answer it: the same nearest nodes
+ * (nearest_neighbor.rs:48-91, on the host), dijkstra from the goal (pto_graph.rs:275-303) as device sweeps of one row of costs per
+ * distinct goal node -- queries that share a goal node share a row; rows run in passes of at most option "prm_rows" (default 256)
+ * rows, fewer when a pass's costs would not fit the device memory budget -- and extract_path (pto_graph.rs:305-326) on the device,
+ * one wave per query.  path_off (n + 1 entries) is always written: the states of query i are rows path_off[i] .. path_off[i+1] of
+ * path_xy.  An empty range means that start and goal are not connected.  The states are written only if the total fits in cap
+ * (counted in states).  The return value is the total, or a negative error: no roadmap on the context, a walk that meets a
+ * zero-length cycle (PORRT_ERR_INVALID; porrt_last_error names the query), PORRT_ERR_CAPACITY when the device buffers of a pass
+ * cannot be allocated (never a truncated answer).  n = 0 returns 0 and writes path_off[0] = 0. */
+int64_t  porrt_prm_plan_paths(porrt_ctx *ctx, const double *starts, const double *goals, uint64_t n,
+                              uint64_t *path_off, double *path_xy, uint64_t cap);
+/* The states of the last porrt_prm_plan_paths, without recomputing them (same total and same cap rule).  It is an error once the
+ * roadmap has changed (a new growth on the context) or before the first call. */
+int64_t  porrt_prm_get_paths(const porrt_ctx *ctx, double *path_xy, uint64_t cap);
+/* Counts and times of the last porrt_prm_plan_paths: queries, rows (distinct goal nodes), sweeps (summed over the passes), passes;
+ * milliseconds on the device (HIP events over the passes), wall (the whole call) and of the nearest-node searches.  The struct
+ * shares its name with the function, as struct stat does with stat(): C++ callers write `struct porrt_prm_paths_info`. */
+struct porrt_prm_paths_info { uint64_t queries, rows, sweeps, passes; double ms_device, ms_wall, ms_nearest; };
+int      porrt_prm_paths_info(const porrt_ctx *ctx, struct porrt_prm_paths_info *out);
 
 /* ---- belief-space expansion: PTO::build_belief_graph (src/pto.rs:185-259) on the graph of the last
  * porrt_grow(mode PORRT_MODE_PTO) of this context, with PTOFuncs::reachable_belief_states (map_io.rs:515-546,
@@ -310,7 +330,9 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * porrt_grow_batch whose members end at different steps launches its later steps on the members that still have work), "gtrack_side" (1 = a single query's goal-path workgroup as a kernel
  * of its own on the side stream; measured slower, 0 is the default: a workgroup of the step kernel), "box_table"
  * (1, default: the group and roadmap kernels answer "is this segment free" from a summed-area table of the raster when the bounding
- * box of its end pixels holds free pixels only, and walk it otherwise; 0 = always walk).  None of them changes a result. */
+ * box of its end pixels holds free pixels only, and walk it otherwise; 0 = always walk), "prm_rows" (porrt_prm_plan_paths: rows of
+ * costs swept together in one pass, 1 .. 4096, default 256), "prm_xcd_rows" (1, default: a row's sweep workgroups are placed together
+ * on one XCD; 0 = the plain grid order).  None of them changes a result. */
 int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
 /* what was in force: "launch_mode" (the last porrt_grow_batch led by this context: 0 = one launch sequence, G = G sequences side by
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a

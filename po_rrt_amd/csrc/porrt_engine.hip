@@ -375,6 +375,12 @@ struct porrt_ctx {
                    const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
                    RefineOut &out);
     PrmState prm;                          // porrt_grow_prm: grid scratch
+    PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
+    GrowScratch prm_paths_scratch;         //   its device buffers (rows of costs, dirty flags, queries), kept across calls
+    uint32_t opt_prm_rows = 256;           // "prm_rows": rows (distinct goal nodes) swept together in one pass
+    uint32_t opt_prm_xcd_rows = 1;         // "prm_xcd_rows": a row's sweep workgroups on one XCD (k_prm_rows_sweep)
+    int ensure_prm_weights();
+    int64_t prm_plan_paths(const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap);
     EdgeOrderState eo;                     // adjacency order of the last PTO graph / roadmap (device)
     std::shared_ptr<void> host_kd;         // the kd-tree of the node coordinates on the host (pre-order ranks, nearest nodes)
     uint64_t host_kd_tag = ~0ull;
@@ -2558,16 +2564,10 @@ int64_t porrt_ctx::prm_plan_path(const double start[2], const double goal[2], do
     int r = download(DL_TREE);
     if (r) return r;
     if ((r = ensure_edge_order())) return r;                        // PTOGraph::parents in push order, on the device
-    const size_t N = n_nodes, E2 = 2 * (size_t)counters.n_edges;
+    const size_t N = n_nodes;
     const HostKd *kd = host_kd_of(this);
     const size_t kd_start = kd->nearest(start[0], start[1]), kd_goal = kd->nearest(goal[0], goal[1]);
-    if (prm.w_cap < E2 + 1) {
-        if (prm.d_w) (void)hipFree(prm.d_w);
-        prm.d_w = nullptr; prm.w_cap = 0;
-        HIPCHK(hipMalloc((void **)&prm.d_w, (E2 + E2 / 8 + 1) * sizeof(double)));
-        prm.w_cap = E2 + E2 / 8 + 1;
-        prm.w_tag = ~0ull;
-    }
+    if ((r = ensure_prm_weights())) return r;
     if (prm.dist_cap < N) {
         void *drop[] = {prm.d_dist, prm.d_dirty[0], prm.d_dirty[1]};
         for (void *q : drop) if (q) (void)hipFree(q);
@@ -2579,11 +2579,6 @@ int64_t porrt_ctx::prm_plan_path(const double start[2], const double goal[2], do
     }
     if (!prm.d_flags) HIPCHK(hipMalloc((void **)&prm.d_flags, 8 * sizeof(uint32_t)));
     const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    if (prm.w_tag != results_tag) {
-        hipLaunchKernelGGL(k_prm_weights, grid, block, 0, stream, (uint32_t)N, (const unsigned long long *)eo.d_adj_off, (const uint32_t *)eo.d_adj_id,
-                           (const double *)d_nx.p, (const double *)d_ny.p, prm.d_w);
-        prm.w_tag = results_tag;
-    }
     // dijkstra from the goal's node (pto_graph.rs:275-303): sweeps until nothing changes, eight between two looks
     HIPCHK(hipMemsetAsync(prm.d_dirty[0], 0, N, stream));
     HIPCHK(hipMemsetAsync(prm.d_dirty[1], 0, N, stream));
@@ -2629,6 +2624,191 @@ int64_t porrt_ctx::prm_plan_path(const double start[2], const double goal[2], do
         node = best;
     }
     return (int64_t)n_path;
+}
+
+// The roadmap's edge weights in adjacency order (k_prm_weights), made once per roadmap; the single and the batched plan_path share them.
+int porrt_ctx::ensure_prm_weights() {
+    const size_t N = n_nodes, E2 = 2 * (size_t)counters.n_edges;
+    if (prm.w_cap < E2 + 1) {
+        if (prm.d_w) (void)hipFree(prm.d_w);
+        prm.d_w = nullptr; prm.w_cap = 0;
+        HIPCHK(hipMalloc((void **)&prm.d_w, (E2 + E2 / 8 + 1) * sizeof(double)));
+        prm.w_cap = E2 + E2 / 8 + 1;
+        prm.w_tag = ~0ull;
+    }
+    if (prm.w_tag != results_tag) {
+        hipLaunchKernelGGL(k_prm_weights, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (uint32_t)N, (const unsigned long long *)eo.d_adj_off,
+                           (const uint32_t *)eo.d_adj_id, (const double *)d_nx.p, (const double *)d_ny.p, prm.d_w);
+        prm.w_tag = results_tag;
+    }
+    return PORRT_OK;
+}
+
+// PRM::plan_path for n start/goal pairs (porrt_prm_plan_paths): the nearest nodes on the host (the literal kd traversal, as plan_path),
+// one row of costs per distinct goal node, the rows swept together in passes (k_prm_rows_init / k_prm_rows_sweep, porrt_prm.hpp), the
+// paths walked on the device (k_prm_walk: a count pass, the offsets, a write pass).  Only the lengths and the states are downloaded.
+int64_t porrt_ctx::prm_plan_paths(const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap) {
+    PrmPathsResult &res = prm_paths;
+    res.valid = false;
+    if (!have_results || mode != PORRT_MODE_PRM) { set_err("plan_paths: grow a roadmap first (porrt_grow_prm)"); return PORRT_ERR_INVALID; }
+    if (!path_off || (n && (!starts || !goals))) { set_err("plan_paths: starts, goals and path_off"); return PORRT_ERR_INVALID; }
+    if (n >= (1ull << 31)) { set_err("plan_paths: fewer than 2^31 queries"); return PORRT_ERR_INVALID; }
+    const double t0 = now_s();
+    res.info = {};
+    res.info.queries = n;
+    res.off.assign(n + 1, 0);
+    res.xy.clear();
+    int r;
+    if (n) {
+        HIPCHK(hipSetDevice(device));
+        if ((r = download(DL_TREE))) return r;
+        if ((r = ensure_edge_order())) return r;                    // PTOGraph::parents in push order, on the device
+        if ((r = ensure_prm_weights())) return r;
+        const size_t N = n_nodes;
+        // the nearest nodes of starts and goals; a row per distinct goal node, in the order of first use
+        const double tn = now_s();
+        const HostKd *kd = host_kd_of(this);
+        std::vector<uint32_t> q_start(n), q_row(n), row_goal;
+        std::unordered_map<uint32_t, uint32_t> row_of_goal;
+        for (uint64_t q = 0; q < n; ++q) {
+            q_start[q] = (uint32_t)kd->nearest(starts[2 * q], starts[2 * q + 1]);
+            const auto it = row_of_goal.emplace((uint32_t)kd->nearest(goals[2 * q], goals[2 * q + 1]), (uint32_t)row_goal.size());
+            if (it.second) row_goal.push_back(it.first->first);
+            q_row[q] = it.first->second;
+        }
+        res.info.ms_nearest = 1e3 * (now_s() - tn);
+        const size_t R = row_goal.size();
+        res.info.rows = R;
+        // queries grouped by row (a pass walks the queries of its rows)
+        std::vector<uint64_t> row_first(R + 1, 0);
+        for (uint64_t q = 0; q < n; ++q) ++row_first[q_row[q] + 1];
+        for (size_t k = 0; k < R; ++k) row_first[k + 1] += row_first[k];
+        std::vector<uint32_t> order(n);
+        {
+            std::vector<uint64_t> at(row_first.begin(), row_first.end() - 1);
+            for (uint64_t q = 0; q < n; ++q) order[at[q_row[q]]++] = (uint32_t)q;
+        }
+        // rows per pass: the option, and the costs + dirty bytes of a pass within the budget and half the free device memory
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = kPrmPathsBudget; }
+        const size_t per_row = 10 * N + 64;
+        const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)opt_prm_rows, R, std::min(kPrmPathsBudget, free_b / 2) / per_row}));
+        auto no_room = [&](const char *what) {
+            (void)hipGetLastError();
+            set_err(std::string("plan_paths: cannot allocate ") + what);
+            return (int64_t)PORRT_ERR_CAPACITY;
+        };
+        GrowScratch &sc = prm_paths_scratch;
+        double *d_dist = nullptr, *d_out = nullptr;
+        uint8_t *d_dirty = nullptr;
+        uint32_t *d_flags = nullptr, *d_act = nullptr, *d_goal = nullptr, *d_qs = nullptr, *d_qr = nullptr, *d_len = nullptr;
+        unsigned long long *d_off = nullptr;
+        if (sc.get(0, d_dist, P * N) != hipSuccess) return no_room("the rows' costs");
+        if (sc.get(1, d_dirty, 2 * P * N) != hipSuccess) return no_room("the rows' dirty flags");
+        if (sc.get(2, d_flags, 8 * P) != hipSuccess || sc.get(3, d_act, P) != hipSuccess || sc.get(4, d_goal, P) != hipSuccess ||
+            sc.get(5, d_qs, n) != hipSuccess || sc.get(6, d_qr, n) != hipSuccess || sc.get(7, d_len, n) != hipSuccess || sc.get(8, d_off, n) != hipSuccess)
+            return no_room("the query arrays");
+        uint8_t *d_dirty_ab[2] = {d_dirty, d_dirty + P * N};
+        const unsigned long long *adj_off = eo.d_adj_off;
+        const uint32_t *adj_id = eo.d_adj_id;
+        const uint32_t nbx = (uint32_t)((N + 255) / 256);
+        std::vector<uint32_t> h_flags(8 * P), act, next, h_qs, h_qr, h_len;
+        std::vector<unsigned long long> h_off;
+        std::vector<uint32_t> lens(n, 0);
+        std::vector<uint64_t> src(n, 0);                            // where query q's states start in `staged`
+        std::vector<double> staged;
+        ScopedEvents<2> evs;
+        HIPCHK(evs.create());
+        double dev_ms = 0;
+        for (size_t r0 = 0; r0 < R; r0 += P) {
+            const size_t pr = std::min(P, R - r0);
+            ++res.info.passes;
+            HIPCHK(hipEventRecord(evs.e[0], stream));
+            HIPCHK(hipMemcpyAsync(d_goal, row_goal.data() + r0, pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemsetAsync(d_dirty_ab[0], 0, pr * N, stream));
+            HIPCHK(hipMemsetAsync(d_dirty_ab[1], 0, pr * N, stream));
+            hipLaunchKernelGGL(k_prm_rows_init, dim3(nbx, (unsigned)pr), dim3(256), 0, stream, (uint32_t)N, (const uint32_t *)d_goal, adj_off, adj_id,
+                               d_dist, d_dirty_ab[1]);
+            act.resize(pr);
+            for (size_t k = 0; k < pr; ++k) act[k] = (uint32_t)k;
+            HIPCHK(hipMemcpyAsync(d_act, act.data(), pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            // dijkstra from every row's goal (pto_graph.rs:275-303): sweeps, eight between two looks at all rows' flags; a row whose
+            // eighth sweep changed nothing has reached its fixpoint (no dirty node is left) and drops out of the later launches
+            int cur = 1;                                            // the init marked the goals' neighbours in buffer 1
+            for (uint64_t sweeps = 0;; sweeps += 8) {
+                const uint32_t nact = (uint32_t)act.size();
+                HIPCHK(hipMemsetAsync(d_flags, 0, 8 * pr * sizeof(uint32_t), stream));
+                for (uint32_t k = 0; k < 8; ++k, cur ^= 1)
+                    hipLaunchKernelGGL(k_prm_rows_sweep, dim3(nbx * nact), dim3(256), 0, stream, (uint32_t)N, nbx, nact, opt_prm_xcd_rows,
+                                       (const uint32_t *)d_act, adj_off, adj_id, (const double *)prm.d_w, d_dist, d_dirty_ab[cur], d_dirty_ab[cur ^ 1],
+                                       d_flags, k);
+                HIPCHK(hipMemcpyAsync(h_flags.data(), d_flags, 8 * pr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                res.info.sweeps += 8;
+                next.clear();
+                for (uint32_t a : act) if (h_flags[8 * a + 7]) next.push_back(a);
+                if (next.empty()) break;
+                if (sweeps > 16u * 1000u * 1000u) { set_err("plan_paths: no fixpoint"); return PORRT_ERR_DEVICE; }
+                if (next.size() != act.size()) HIPCHK(hipMemcpyAsync(d_act, next.data(), next.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+                act.swap(next);                                     // (the copy reads this buffer; it is written again only after the next sync)
+            }
+            // extract_path (pto_graph.rs:305-326) for the queries of these rows: count, offsets, write
+            const uint64_t q0 = row_first[r0], q1 = row_first[r0 + pr];
+            const uint32_t nq = (uint32_t)(q1 - q0);
+            h_qs.resize(nq); h_qr.resize(nq); h_len.resize(nq); h_off.resize(nq);
+            for (uint32_t k = 0; k < nq; ++k) { const uint32_t q = order[q0 + k]; h_qs[k] = q_start[q]; h_qr[k] = q_row[q] - (uint32_t)r0; }
+            HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_qr, h_qr.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            const dim3 wgrid((nq + 3) / 4);
+            hipLaunchKernelGGL(k_prm_walk<false>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
+                               (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)nullptr, (double *)nullptr);
+            HIPCHK(hipMemcpyAsync(h_len.data(), d_len, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            unsigned long long tot = 0;
+            for (uint32_t k = 0; k < nq; ++k) {
+                const uint32_t q = order[q0 + k];
+                if (h_len[k] == kPrmWalkCycle) {
+                    set_err("plan_paths: query " + std::to_string(q) + ": zero-length cycle (the reference would not terminate)");
+                    return PORRT_ERR_INVALID;
+                }
+                if (h_len[k] == kPrmWalkOrphan) { set_err("plan_paths: query " + std::to_string(q) + ": node without parents"); return PORRT_ERR_INVALID; }
+                h_off[k] = tot;
+                lens[q] = h_len[k];
+                src[q] = staged.size() / 2 + tot;
+                tot += h_len[k];
+            }
+            if (tot) {
+                if (sc.get(9, d_out, 2 * tot) != hipSuccess) return no_room("the paths");
+                HIPCHK(hipMemcpyAsync(d_off, h_off.data(), nq * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(k_prm_walk<true>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
+                                   (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)d_off, d_out);
+                const size_t s0 = staged.size();
+                staged.resize(s0 + 2 * tot);
+                HIPCHK(hipMemcpyAsync(staged.data() + s0, d_out, 2 * tot * sizeof(double), hipMemcpyDeviceToHost, stream));
+            }
+            HIPCHK(hipEventRecord(evs.e[1], stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            HIPCHK(hipGetLastError());
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+            dev_ms += ms;
+        }
+        res.info.ms_device = dev_ms;
+        // the answers in query order
+        uint64_t total = 0;
+        for (uint64_t q = 0; q < n; ++q) { res.off[q] = total; total += lens[q]; }
+        res.off[n] = total;
+        res.xy.resize(2 * total);
+        for (uint64_t q = 0; q < n; ++q)
+            if (lens[q]) memcpy(res.xy.data() + 2 * res.off[q], staged.data() + 2 * src[q], 2 * (size_t)lens[q] * sizeof(double));
+    }
+    const uint64_t total = res.off[n];
+    memcpy(path_off, res.off.data(), (n + 1) * sizeof(uint64_t));
+    if (path_xy && total && total <= cap) memcpy(path_xy, res.xy.data(), 2 * total * sizeof(double));
+    res.tag = results_tag;
+    res.valid = true;
+    res.info.ms_wall = 1e3 * (now_s() - t0);
+    return (int64_t)total;
 }
 
 // Best path cost without downloading the tree (k_best_cost).  1 = found, 0 = no final node, -1 = scratch too small
@@ -3166,6 +3346,7 @@ void porrt_destroy(porrt_ctx *c) {
     c->mm_scratch.free_all();
     c->mmp_scratch.free_all();
     c->refine_scratch.free_all();
+    c->prm_paths_scratch.free_all();
     for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
@@ -3757,6 +3938,28 @@ int porrt_mm_get_seconds(const porrt_ctx *c, double *host_s, double *roadmap_s, 
 int64_t porrt_prm_plan_path(porrt_ctx *c, const double start[2], const double goal[2], double *path_xy, uint64_t cap) {
     return c ? c->prm_plan_path(start, goal, path_xy, cap) : PORRT_ERR_INVALID;
 }
+int64_t porrt_prm_plan_paths(porrt_ctx *c, const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try { return c->prm_plan_paths(starts, goals, n, path_off, path_xy, cap); } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int64_t porrt_prm_get_paths(const porrt_ctx *c, double *path_xy, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);                      // (for the error text only)
+    const PrmPathsResult &res = c->prm_paths;
+    if (!res.valid) { m->set_err("prm_get_paths: no answers: call porrt_prm_plan_paths first"); return PORRT_ERR_INVALID; }
+    if (res.tag != c->results_tag || !c->have_results || c->mode != PORRT_MODE_PRM) {
+        m->set_err("prm_get_paths: the roadmap changed since porrt_prm_plan_paths");
+        return PORRT_ERR_INVALID;
+    }
+    const uint64_t total = res.off.back();
+    if (path_xy && total && total <= cap) memcpy(path_xy, res.xy.data(), 2 * total * sizeof(double));
+    return (int64_t)total;
+}
+int porrt_prm_paths_info(const porrt_ctx *c, struct porrt_prm_paths_info *out) {
+    if (!c || !out || !c->prm_paths.valid) return PORRT_ERR_INVALID;
+    *out = c->prm_paths.info;
+    return PORRT_OK;
+}
 
 // ---- belief-space expansion (pto.rs:185-259)
 int porrt_build_belief_graph(porrt_ctx *c, const double *start_belief, uint32_t n_worlds) {
@@ -4226,6 +4429,8 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "tamp_wave")) *value = c->opt_tamp_wave;
     else if (!strcmp(name, "tamp_pool")) *value = c->opt_tamp_pool;
     else if (!strcmp(name, "tamp_search")) *value = c->opt_tamp_search;
+    else if (!strcmp(name, "prm_rows")) *value = c->opt_prm_rows;
+    else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4267,6 +4472,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "tamp_wave")) { if (value < 1 || value > 65536) { c->set_err("tamp_wave: 1 .. 65536"); return PORRT_ERR_INVALID; } c->opt_tamp_wave = (uint32_t)value; }
     else if (!strcmp(name, "tamp_pool")) { if (value < 1 || value > 4096) { c->set_err("tamp_pool: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_tamp_pool = (uint32_t)value; }
     else if (!strcmp(name, "tamp_search")) { if (value < 0 || value > 2) { c->set_err("tamp_search: 0 (BranchAndBound), 1 (AStar), 2 (BranchAndBoundMultipleViewPoints)"); return PORRT_ERR_INVALID; } c->opt_tamp_search = (int)value; }
+    else if (!strcmp(name, "prm_rows")) { if (value < 1 || value > 4096) { c->set_err("prm_rows: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_prm_rows = (uint32_t)value; }
+    else if (!strcmp(name, "prm_xcd_rows")) c->opt_prm_xcd_rows = value != 0;
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again
     if (strcmp(name, "profile") && c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }

@@ -12,6 +12,7 @@
 // reference orders the arguments); a count pass, a scan and a fill pass produce the edge list without a shared cursor.  The order inside a neighbour list (kd pre-order,
 // nearest_neighbor.rs:101-117) is restored on the host when the edges are asked for, as for the belief-space graphs.
 #pragma once
+#include "../../include/porrt_hip.h"
 #include "porrt_belief.hpp"
 
 namespace porrt {
@@ -266,6 +267,119 @@ __global__ __launch_bounds__(256) void k_prm_sssp_sweep(uint32_t N, const unsign
     }
 }
 
+// ---- PRM::plan_path for many start/goal pairs on one roadmap (porrt_prm_plan_paths).  One ROW per distinct goal node: row r holds
+// the costs to its goal, dist[r * N + n], and its own two dirty-byte arrays (same layout, r * N + n).  A sweep launch relaxes every
+// active row at once (act[] lists them; rows that have converged are left out of later launches by the host).  Each row runs
+// exactly the relaxation of k_prm_sssp_sweep on its own arrays -- min over the parents of dist[p] + w, the weights of k_prm_weights --
+// and that relaxation is monotone: a node's value only ever falls, each value is dist[p] + w of some parent, and a node stays dirty
+// until it has been evaluated against its parents' current values.  So every order of evaluation, whichever rows share a launch and
+// however their workgroups interleave, ends in the same fixpoint -- the least solution of dist[n] = min_p dist[p] + w(p, n),
+// dist[goal] = 0 -- and each row is bit-identical to the single query's costs (porrt_dp.hpp gives the same argument for the expected
+// costs).  Any workgroup schedule is correct; the placement below is for speed only.
+//
+// Placement (option "prm_xcd_rows"): the workgroups of a launch are dealt to the eight XCDs in turn, so a plain grid spreads every
+// row over all eight L2s.  With the remap, the workgroups that share an XCD label (blockIdx % 8) take consecutive (row, block)
+// numbers, so a row's blocks run on about one XCD and its costs (8 N bytes: 1.6 MB at N = 200 000) stay in that XCD's 4 MiB L2
+// while the neighbour gathers (random 8-byte reads) hit it.  The remap is bijective for any grid size.
+constexpr size_t kPrmPathsBudget = size_t(2) << 30;     // bytes of costs + dirty flags of one pass (also at most half the free memory)
+__device__ __forceinline__ uint32_t prm_rows_wg(uint32_t orig, uint32_t nwg, uint32_t swz) {
+    if (!swz || nwg <= 8u) return orig;
+    const uint32_t xcd = orig % 8u, q = nwg / 8u, r = nwg % 8u;
+    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + orig / 8u;
+}
+
+// dist of every row of a pass: 0 at the row's goal node, +inf elsewhere; the goal's neighbours marked in dirty_b (the first sweep
+// reads b).  blockIdx.y = row; the dirty arrays were zeroed by the host.
+__global__ __launch_bounds__(256) void k_prm_rows_init(uint32_t N, const uint32_t *__restrict__ goal, const unsigned long long *__restrict__ adj_off,
+                                                       const uint32_t *__restrict__ adj_id, double *__restrict__ dist, uint8_t *__restrict__ dirty_b) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (n >= N) return;
+    const size_t base = (size_t)r * N;
+    const uint32_t g = goal[r];
+    dist[base + n] = n == g ? 0.0 : __builtin_huge_val();
+    if (n == g)
+        for (unsigned long long k = adj_off[n]; k < adj_off[n + 1]; ++k) dirty_b[base + adj_id[k]] = 1;
+}
+
+// One sweep of the active rows: nbx blocks of 256 nodes per row, nact rows, one flat grid of nbx * nact workgroups.  Row r writes its
+// own "changed" word flags[r * 8 + slot] (plain stores: every writer writes 1).
+__global__ __launch_bounds__(256) void k_prm_rows_sweep(uint32_t N, uint32_t nbx, uint32_t nact, uint32_t swz, const uint32_t *__restrict__ act,
+                                                        const unsigned long long *__restrict__ adj_off, const uint32_t *__restrict__ adj_id,
+                                                        const double *__restrict__ w, double *__restrict__ dist, uint8_t *__restrict__ dirty_in,
+                                                        uint8_t *__restrict__ dirty_out, uint32_t *__restrict__ flags, uint32_t slot) {
+    const uint32_t wg = prm_rows_wg(blockIdx.x, nbx * nact, swz);
+    const uint32_t n = (wg % nbx) * 256u + threadIdx.x, r = as_global(act)[wg / nbx];
+    if (n >= N) return;
+    const size_t base = (size_t)r * N;
+    if (!as_global(dirty_in)[base + n]) return;
+    as_global(dirty_in)[base + n] = 0;
+    const double old = as_global(dist)[base + n];
+    if (old == 0.0) return;
+    const unsigned long long a0 = as_global(adj_off)[n], a1 = as_global(adj_off)[n + 1];
+    const double *row = dist + base;
+    double best = old;
+#pragma unroll 4
+    for (unsigned long long k = a0; k < a1; ++k) {
+        const double a = as_global(row)[as_global(adj_id)[k]] + as_global(w)[k];      // dist[v] + cost(u, v)
+        best = a < best ? a : best;
+    }
+    if (best < old) {
+        as_global(dist)[base + n] = best;
+        for (unsigned long long k = a0; k < a1; ++k) as_global(dirty_out)[base + as_global(adj_id)[k]] = 1;
+        as_global(flags)[(size_t)r * 8u + slot] = 1;
+    }
+}
+
+// extract_path (pto_graph.rs:305-326) on the device, one wave per query j of a pass: from its start node to a node of cost 0 of its
+// row, always to the first parent of least dist[p] + norm2(p, node) over the parents list in push order (the min_by of :316-319).
+// Lanes stride the list, each keeping its first strict minimum; the butterfly then keeps the least (cost, list position) -- the first
+// minimum of the whole list (costs are never NaN: finite or +inf).  norm2 is HostKd::norm2's arithmetic: the same rounding.
+// WRITE = false: len[j] = number of states, 0 when the start's cost is +inf (prm.rs:117-119), kPrmWalkCycle after N + 1 steps (a
+// zero-length cycle: the reference would not terminate), kPrmWalkOrphan at a node without parents.  WRITE = true: the states at
+// out + 2 * off[j], never more than the count pass found.
+constexpr uint32_t kPrmWalkCycle = 0xFFFFFFFFu, kPrmWalkOrphan = 0xFFFFFFFEu;
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_prm_walk(uint32_t N, uint32_t nq, const uint32_t *__restrict__ start, const uint32_t *__restrict__ row_of,
+                                                  const unsigned long long *__restrict__ adj_off, const uint32_t *__restrict__ adj_id,
+                                                  const double *__restrict__ nx, const double *__restrict__ ny, const double *__restrict__ dist,
+                                                  uint32_t *__restrict__ len, const unsigned long long *__restrict__ off, double *__restrict__ out) {
+    const uint32_t j = (blockIdx.x * blockDim.x + threadIdx.x) / 64u, lane = threadIdx.x & 63u;
+    if (j >= nq) return;
+    const double *D = dist + (size_t)as_global(row_of)[j] * N;
+    uint32_t node = as_global(start)[j];
+    if (__builtin_isinf(as_global(D)[node])) {
+        if (!WRITE && lane == 0) len[j] = 0;
+        return;
+    }
+    const uint32_t cap = WRITE ? as_global(len)[j] : 0u;
+    double *o = WRITE ? out + 2 * as_global(off)[j] : nullptr;
+    uint32_t cnt = 0, code = 0;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    for (uint32_t guard = 0;; ++guard) {
+        const double xn = as_global(nx)[node], yn = as_global(ny)[node];
+        if (WRITE && lane == 0 && cnt < cap) { o[2 * cnt] = xn; o[2 * cnt + 1] = yn; }
+        ++cnt;
+        if (as_global(D)[node] == 0.0) break;
+        if (guard > N) { code = kPrmWalkCycle; break; }
+        const unsigned long long a0 = as_global(adj_off)[node], a1 = as_global(adj_off)[node + 1];
+        double bc = 0.0;
+        uint32_t bp = kNone;
+        for (unsigned long long k = a0 + lane; k < a1; k += 64u) {
+            const uint32_t p = as_global(adj_id)[k];
+            const double c = as_global(D)[p] + sqrt(dist2(as_global(nx)[p], as_global(ny)[p], xn, yn));
+            if (bp == kNone || c < bc) { bc = c; bp = (uint32_t)(k - a0); }
+        }
+        for (uint32_t s = 32; s >= 1; s >>= 1) {
+            const double oc = __shfl_xor(bc, (int)s);
+            const uint32_t op = (uint32_t)__shfl_xor((int)bp, (int)s);
+            if (op != kNone && (bp == kNone || oc < bc || (oc == bc && op < bp))) { bc = oc; bp = op; }
+        }
+        if (bp == kNone) { code = kPrmWalkOrphan; break; }
+        node = as_global(adj_id)[a0 + bp];
+    }
+    if (!WRITE && lane == 0) len[j] = code ? code : cnt;
+}
+
 struct PrmState {
     uint32_t *d_cell_cnt = nullptr;
     unsigned long long *d_cell_off = nullptr, *d_tot = nullptr, *d_edge_off = nullptr;
@@ -286,6 +400,16 @@ struct PrmState {
         cells_cap = ids_cap = 0;
     }
     ~PrmState() { free_device(); }
+};
+
+// porrt_prm_plan_paths: the last call's answers in query order (porrt_prm_get_paths hands them out again) and its counts.  They
+// belong to the roadmap of results_tag `tag`: a new growth on the context makes them stale.
+struct PrmPathsResult {
+    bool valid = false;
+    uint64_t tag = ~0ull;
+    std::vector<uint64_t> off;        // [queries + 1]: the states of query i are rows off[i] .. off[i + 1] of xy
+    std::vector<double> xy;
+    struct porrt_prm_paths_info info = {};
 };
 
 } // namespace porrt

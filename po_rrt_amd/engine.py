@@ -25,7 +25,7 @@ _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 SYMBOLS = [
     "porrt_create", "porrt_destroy", "porrt_last_error", "porrt_set_grid", "porrt_set_zones", "porrt_set_sampler",
     "porrt_set_discrete_seed", "porrt_set_samples", "porrt_set_worlds", "porrt_set_square_goal",
-    "porrt_set_observation_goal", "porrt_grow", "porrt_grow_batch", "porrt_grow_batch_each", "porrt_grow_prm", "porrt_prm_plan_path", "porrt_num_nodes", "porrt_num_iterations", "porrt_get_tree", "porrt_get_trees",
+    "porrt_set_observation_goal", "porrt_grow", "porrt_grow_batch", "porrt_grow_batch_each", "porrt_grow_prm", "porrt_prm_plan_path", "porrt_prm_plan_paths", "porrt_prm_get_paths", "porrt_prm_paths_info", "porrt_num_nodes", "porrt_num_iterations", "porrt_get_tree", "porrt_get_trees",
     "porrt_num_final", "porrt_get_final_ids", "porrt_get_final_masks", "porrt_get_reach", "porrt_get_node_validity",
     "porrt_num_edges", "porrt_get_edges", "porrt_is_final_set_complete", "porrt_n_worlds", "porrt_get_validities",
     "porrt_get_zone_positions", "porrt_best_solution", "porrt_best_cost", "porrt_best_cost_batch", "porrt_get_metrics", "porrt_set_option", "porrt_get_option", "porrt_selftest",
@@ -63,6 +63,12 @@ class TampInfo(C.Structure):
                 ("total_s", C.c_double), ("grow_s", C.c_double), ("path_s", C.c_double), ("shortcut_s", C.c_double),
                 ("search_s", C.c_double), ("pool_s", C.c_double), ("goals_s", C.c_double),
                 ("streams", C.c_uint32), ("wave", C.c_uint32), ("pool", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class PrmPathsInfo(C.Structure):
+    """struct porrt_prm_paths_info"""
+    _fields_ = [("queries", C.c_uint64), ("rows", C.c_uint64), ("sweeps", C.c_uint64), ("passes", C.c_uint64),
+                ("ms_device", C.c_double), ("ms_wall", C.c_double), ("ms_nearest", C.c_double)]
 
 
 class TreeDeviceView(C.Structure):
@@ -131,6 +137,9 @@ def load_library():
     sig("porrt_best_cost", C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64))
     sig("porrt_grow_prm", C.c_int, vp, _f64p, C.c_double, C.c_double, C.c_uint64)
     sig("porrt_prm_plan_path", C.c_int64, vp, _f64p, _f64p, C.c_void_p, C.c_uint64)
+    sig("porrt_prm_plan_paths", C.c_int64, vp, _f64p, _f64p, C.c_uint64, _u64p, C.c_void_p, C.c_uint64)
+    sig("porrt_prm_get_paths", C.c_int64, vp, C.c_void_p, C.c_uint64)
+    sig("porrt_prm_paths_info", C.c_int, vp, C.POINTER(PrmPathsInfo))
     sig("porrt_build_belief_graph", C.c_int, vp, _f64p, C.c_uint32)
     sig("porrt_bg_num_beliefs", C.c_uint64, vp)
     sig("porrt_bg_num_nodes", C.c_uint64, vp)
@@ -506,6 +515,26 @@ class Engine:
         if n:
             self._l.porrt_prm_plan_path(self._c, a, b, out.ctypes.data_as(C.c_void_p), n)
         return out
+
+    def prm_plan_paths(self, starts, goals):
+        """porrt_prm_plan_paths: PRM::plan_path for every pair (starts[i], goals[i]) in one call -- a list of (k, 2) arrays, each
+        equal to prm_plan_path(starts[i], goals[i]) (empty when start and goal are not connected)"""
+        s, g = _f64(starts).reshape(-1, 2), _f64(goals).reshape(-1, 2)
+        if len(s) != len(g):
+            raise ValueError("prm_plan_paths: one goal per start")
+        n = len(s)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        total = self._chk(int(self._l.porrt_prm_plan_paths(self._c, s.reshape(-1), g.reshape(-1), n, off, None, 0)))
+        xy = np.zeros((total, 2))
+        if total:
+            self._chk(int(self._l.porrt_prm_get_paths(self._c, xy.ctypes.data_as(C.c_void_p), total)))
+        return [xy[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def prm_paths_info(self):
+        """porrt_prm_paths_info of the last prm_plan_paths: queries, rows, sweeps, passes, ms_device, ms_wall, ms_nearest"""
+        i = PrmPathsInfo()
+        self._chk(self._l.porrt_prm_paths_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in PrmPathsInfo._fields_}
 
     # ---- belief-space expansion (PTO::build_belief_graph, pto.rs:185-259)
     def build_belief_graph(self, start_belief):

@@ -1,0 +1,193 @@
+"""GPU tests of porrt_prm_plan_paths: PRM::plan_path (prm.rs:111-123) for many start/goal pairs on one roadmap in one call.  Every
+answer equals porrt_prm_plan_path and the oracle's literal restatement bit for bit; queries that share a goal node share a row of
+costs; rows run in passes of at most option prm_rows; and the interface's sizing, staleness and error rules hold."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import cases
+from oracle import orc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng_mod():
+    from po_rrt_amd import build
+    build.build()
+    import po_rrt_amd
+    return po_rrt_amd
+
+
+def pair(eng_mod, grid, zones, domain, visibility, seed):
+    objs = []
+    for mk in (eng_mod.Engine, orc.Oracle):
+        x = mk()
+        x.set_grid(cases.load_map(grid), (-1.0, -1.0), (1.0, 1.0), domain)
+        if zones:
+            x.set_zones(cases.load_map(zones), visibility)
+        x.set_sampler((-1.0, -1.0), (1.0, 1.0), seed)
+        objs.append(x)
+    return objs
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+@pytest.fixture(scope="module")
+def bench8000(eng_mod):
+    """the roadmap of test_gpu_prm.py::test_prm_plan_path_equals_oracle"""
+    e, o = pair(eng_mod, "map_benchmark_like", None, cases.SHELF, 0.0, 9)
+    e.grow_prm((0.0, -0.8), 0.1, 2.0, 8000)
+    o.grow_prm((0.0, -0.8), 0.1, 2.0, 8000)
+    return e, o
+
+
+def random_pairs(seed, n):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(-1.0, 1.0, (n, 2)), rng.uniform(-1.0, 1.0, (n, 2))
+
+
+def test_many_queries_equal_oracle(bench8000):
+    e, o = bench8000
+    fixed = [((0.0, -0.8), (0.9, 0.0)), ((-0.7, 0.7), (0.7, -0.7)), ((0.3, 0.3), (0.3, 0.3)), ((0.0, -0.8), (2.0, 2.0))]
+    rs, rg = random_pairs(11, 180)
+    rnd = [(tuple(s), tuple(g)) for s, g in zip(rs, rg)]
+    node = tuple(e.tree()[0][1234])                              # start and goal on the same node: one state
+    queries = fixed + rnd + rnd[:8] + fixed + [(node, node)]
+    S, G = np.array([q[0] for q in queries]), np.array([q[1] for q in queries])
+    paths = e.prm_plan_paths(S, G)
+    assert len(paths) == len(queries)
+    for (s, g), p in zip(queries, paths):
+        assert same(p, o.prm_plan_path(s, g)), (s, g)
+    assert len(paths[-1]) == 1 and len(paths[0]) > 5
+    # path_off through the C ABI: consistent with the answers
+    off = np.zeros(len(queries) + 1, dtype=np.uint64)
+    total = e._l.porrt_prm_plan_paths(e._c, S.reshape(-1), G.reshape(-1), len(queries), off, None, 0)
+    assert off[0] == 0 and total == int(off[-1]) == sum(len(p) for p in paths)
+    assert np.array_equal(np.diff(off.astype(np.int64)), [len(p) for p in paths])
+    info = e.prm_paths_info()
+    assert info["queries"] == len(queries) and 0 < info["rows"] <= len(queries) and info["passes"] == 1 and info["sweeps"] > 0
+    assert info["ms_wall"] >= info["ms_nearest"] >= 0.0 and info["ms_device"] > 0.0
+
+
+def test_connected_and_unconnected_in_one_call(eng_mod):
+    e, o = pair(eng_mod, "door_map_like", "door_map_like_zone_ids", cases.DOOR, 0.3, 3)
+    e.grow_prm((0.5, -0.6), 0.05, 5.0, 3000)                  # the walled-off rooms: 18 of the 60 random pairs are not connected
+    o.grow_prm((0.5, -0.6), 0.05, 5.0, 3000)
+    rs, rg = random_pairs(4, 60)
+    node = tuple(e.tree()[0][100])
+    queries = [((0.5, -0.6), (-0.5, 0.6)), (node, node)] + [(tuple(s), tuple(g)) for s, g in zip(rs, rg)] + [((0.5, -0.6), node)]
+    paths = e.prm_plan_paths([q[0] for q in queries], [q[1] for q in queries])
+    expect = [o.prm_plan_path(s, g) for s, g in queries]
+    assert all(same(p, x) for p, x in zip(paths, expect))
+    assert any(len(x) == 0 for x in expect) and any(len(x) > 1 for x in expect)     # both kinds in the one call
+
+
+def test_bench_roadmap_1024_queries(eng_mod):
+    """the bench's roadmap (map_benchmark_like, 200 000 samples): 1024 queries in one call"""
+    e, o = pair(eng_mod, "map_benchmark_like", None, cases.SHELF, 0.0, 3)
+    e.grow_prm((0.0, -0.8), 0.1, 2.0, 200000)
+    S, G = random_pairs(2024, 1024)
+    paths = e.prm_plan_paths(S, G)
+    info = e.prm_paths_info()
+    assert info["queries"] == 1024 and info["passes"] == -(-info["rows"] // 256)
+    for i in range(0, 1024, 16):                                 # 64 of them against the single call
+        assert same(paths[i], e.prm_plan_path(S[i], G[i])), i
+    o.grow_prm((0.0, -0.8), 0.1, 2.0, 200000)
+    for i in range(3, 1024, 128):                                # 8 against the oracle
+        assert same(paths[i], o.prm_plan_path(S[i], G[i])), i
+    assert any(len(p) > 10 for p in paths)
+
+
+def test_rows_are_shared_and_run_in_passes(bench8000):
+    e, o = bench8000
+    rs, _ = random_pairs(7, 300)
+    goals3 = np.array([(0.9, 0.0), (-0.7, 0.7), (0.1, -0.5)])
+    G = goals3[np.arange(300) % 3]
+    base = e.prm_plan_paths(rs, G)
+    info = e.prm_paths_info()
+    assert info["rows"] == 3 and info["passes"] == 1
+    try:
+        for rows in (1, 2, 7):
+            e.set_option("prm_rows", rows)
+            assert e.get_option("prm_rows") == rows
+            got = e.prm_plan_paths(rs, G)
+            info = e.prm_paths_info()
+            assert info["rows"] == 3 and info["passes"] == -(-3 // rows)
+            assert all(same(a, b) for a, b in zip(got, base))
+        e.set_option("prm_xcd_rows", 0)                          # the plain grid order: the same answers
+        assert all(same(a, b) for a, b in zip(e.prm_plan_paths(rs, G), base))
+    finally:
+        e.set_option("prm_rows", 256)
+        e.set_option("prm_xcd_rows", 1)
+    for i in range(0, 300, 10):
+        assert same(base[i], e.prm_plan_path(rs[i], G[i])), i
+    for i in (0, 1, 2, 150):
+        assert same(base[i], o.prm_plan_path(rs[i], G[i])), i
+    with pytest.raises(RuntimeError):
+        e.set_option("prm_rows", 0)
+
+
+def test_interface(eng_mod, bench8000):
+    e, _ = bench8000
+    L = e._l
+    S = np.array([[0.0, -0.8], [-0.7, 0.7], [0.3, 0.3]])
+    G = np.array([[0.9, 0.0], [0.7, -0.7], [0.3, 0.3]])
+    # cap too small: the total and path_off, no states; porrt_prm_get_paths fetches them
+    off = np.zeros(4, dtype=np.uint64)
+    small = np.full((4, 2), 7.0)
+    total = L.porrt_prm_plan_paths(e._c, S.reshape(-1), G.reshape(-1), 3, off, small.ctypes.data_as(C.c_void_p), 4)
+    assert total > 4 and int(off[-1]) == total and np.all(small == 7.0)
+    full = np.zeros((total, 2))
+    assert L.porrt_prm_get_paths(e._c, full.ctypes.data_as(C.c_void_p), total) == total
+    for i in range(3):
+        assert same(full[int(off[i]):int(off[i + 1])], e.prm_plan_path(S[i], G[i]))
+    # n = 0
+    off0 = np.full(1, 99, dtype=np.uint64)
+    assert L.porrt_prm_plan_paths(e._c, np.zeros(0), np.zeros(0), 0, off0, None, 0) == 0 and off0[0] == 0
+    assert e.prm_plan_paths(np.zeros((0, 2)), np.zeros((0, 2))) == []
+    assert e.prm_paths_info()["queries"] == 0
+    # no roadmap on the context
+    with pytest.raises(RuntimeError):
+        cases.configure(eng_mod.Engine(), cases.cfg2(100)).prm_plan_paths([(0.0, 0.0)], [(0.5, 0.5)])
+    fresh = eng_mod.Engine()
+    assert fresh._l.porrt_prm_get_paths(fresh._c, None, 0) < 0     # nothing asked yet
+    # a regrowth makes the last answers stale
+    e2, _ = pair(eng_mod, "map_benchmark_like", None, cases.SHELF, 0.0, 5)
+    e2.grow_prm((0.0, -0.8), 0.1, 2.0, 1500)
+    total = e2._chk(int(L.porrt_prm_plan_paths(e2._c, S.reshape(-1), G.reshape(-1), 3, off, None, 0)))
+    full2 = np.zeros((max(total, 1), 2))
+    assert L.porrt_prm_get_paths(e2._c, full2.ctypes.data_as(C.c_void_p), total) == total
+    e2.grow_prm((0.0, -0.8), 0.1, 2.0, 1500)
+    assert L.porrt_prm_get_paths(e2._c, full2.ctypes.data_as(C.c_void_p), total) < 0
+    assert "changed" in L.porrt_last_error(e2._c).decode()
+
+
+def test_interleaved_with_single_calls_and_rrt(eng_mod):
+    """single calls, batched calls and an RRT* growth on one context: none changes another's results"""
+    case = cases.cfg2(4000)
+    e = cases.configure(eng_mod.Engine(), case)
+    o = cases.configure(orc.Oracle(), case)
+    e.grow_prm((0.0, -0.8), 0.1, 2.0, 3000)
+    o.grow_prm((0.0, -0.8), 0.1, 2.0, 3000)
+    S, G = random_pairs(21, 20)
+    first = e.prm_plan_paths(S, G)
+    singles = [e.prm_plan_path(S[i], G[i]) for i in range(5)]
+    again = e.prm_plan_paths(S, G)
+    assert all(same(a, b) for a, b in zip(first, again))
+    assert all(same(first[i], singles[i]) for i in range(5))
+    assert all(same(first[i], o.prm_plan_path(S[i], G[i])) for i in range(20))
+    cases.grow(e, case, K=256)
+    cases.grow(o, case, K=256, algo=orc.ALGO_BATCHED_KD)
+    assert np.array_equal(e.tree()[1], o.tree()[1])
+    with pytest.raises(RuntimeError):
+        e.prm_plan_paths(S, G)                                   # the context holds a tree now, not a roadmap
+    e.grow_prm((0.0, -0.8), 0.1, 2.0, 2000)
+    o.grow_prm((0.0, -0.8), 0.1, 2.0, 2000)
+    paths = e.prm_plan_paths(S, G)
+    assert all(same(paths[i], o.prm_plan_path(S[i], G[i])) for i in range(20))
+    assert same(paths[3], e.prm_plan_path(S[3], G[3]))
