@@ -235,6 +235,12 @@ struct porrt_ctx {
     // "early_wave_steps": the group kernels take one wave per sample (64 lanes, 320 hits in LDS) for this many first steps of a run,
     // where the tree is a dense blob and a sample has hundreds of neighbours, and 16 lanes per sample afterwards
     uint32_t opt_early_wave = 0;
+    // "conn_wg_waves": waves per workgroup of the group kernels' connect pass.  1: k_conn2 with one wave per workgroup (a finished wave
+    // frees its slot and its LDS lists at once) + k_conn2_riders (page filing, goal-point copies, goal path) as a kernel of its own;
+    // 4: k_conn2_wg4, everything in one kernel of four-wave workgroups.  "conn_riders_first": k_conn2_riders before (1) or after (0) k_conn2.
+    uint32_t opt_conn_wg_waves = 1;
+    bool opt_conn_riders_first = true;
+    uint32_t opt_nn_wg_waves = 4;          // "nn_wg_waves": the same choice for k_nn2 (4 or 1 waves per workgroup)
     // "batch_streams": porrt_grow_batch advances its contexts as this many sub-batches side by side, each a launch sequence
     // (hipGraph) of its own on its own streams, so that one sub-batch's kernel tails and its kd side chain are filled by the
     // other's kernels.  0 (default): 2 from 32 contexts on, else 1.
@@ -793,11 +799,15 @@ void porrt_ctx::launch_step(uint32_t b, uint32_t i0, uint32_t nb, uint32_t vword
     if (mode == PORRT_MODE_PTO) hipLaunchKernelGGL(k_near<true>, dim3(wave_blocks, Q), dim3(256), 0, stream, rcp, b, i0, nb, vwords, 0xFFFFFFFFu, 0u);
     else if (GLn) {
         // GL lanes per sample; the previous step's rewire phase 2 rides along in extra workgroups
-        const uint32_t spb = 256u / GLn, sblocks = (nb + spb - 1) / spb;
+        const uint32_t spb = opt_nn_wg_waves * 64u / GLn, sblocks = (nb + spb - 1) / spb;
         const uint32_t cblocks = commit_pend_b != 0xFFFFFFFFu ? (commit_pend_nb + spb - 1) / spb : 0;
         const dim3 g(sblocks + cblocks, Q);
         const uint32_t cnb = cblocks ? commit_pend_nb : 0u;
-        if (GLn == 16) hipLaunchKernelGGL(k_nn2<16>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
+        if (opt_nn_wg_waves == 1u) {
+            if (GLn == 16) hipLaunchKernelGGL((k_nn2<16, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
+            else if (GLn == 32) hipLaunchKernelGGL((k_nn2<32, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
+            else hipLaunchKernelGGL((k_nn2<64, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
+        } else if (GLn == 16) hipLaunchKernelGGL(k_nn2<16>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
         else if (GLn == 32) hipLaunchKernelGGL(k_nn2<32>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
         else hipLaunchKernelGGL(k_nn2<64>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
         commit_pend_b = 0xFFFFFFFFu;
@@ -824,13 +834,26 @@ void porrt_ctx::launch_step(uint32_t b, uint32_t i0, uint32_t nb, uint32_t vword
     (void)hipEventRecord(ev_steered, stream);
     ev();
     if (GLn) {
-        const uint32_t spb = 256u / GLc;
         const uint32_t lazy = kd_lazy ? 1u : 0u;
-        const dim3 g2((nb + spb - 1) / spb + 2 + lazy, Q);       // + the clone workgroup + the page-filing workgroup (+ the goal path's)
-        const size_t dyn = conn2_lds_bytes(GLc);
-        if (GLc == 16) hipLaunchKernelGGL(k_conn2<16>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
-        else if (GLc == 32) hipLaunchKernelGGL(k_conn2<32>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
-        else hipLaunchKernelGGL(k_conn2<64>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
+        if (opt_conn_wg_waves == 4u) {
+            const uint32_t spb = 256u / GLc;
+            const dim3 g2((nb + spb - 1) / spb + 2 + lazy, Q);       // + the clone workgroup + the page-filing workgroup (+ the goal path's)
+            const size_t dyn = conn2_wg4_lds_bytes(GLc);
+            if (GLc == 16) hipLaunchKernelGGL(k_conn2_wg4<16>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
+            else if (GLc == 32) hipLaunchKernelGGL(k_conn2_wg4<32>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
+            else hipLaunchKernelGGL(k_conn2_wg4<64>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy);
+        } else {
+            // one-wave workgroups for the samples; the step's single workgroups as a kernel of their own on the same stream (one more
+            // node of the chain under capture), before or after the samples (conn_riders_first)
+            const uint32_t spb = 64u / GLc;
+            const dim3 g2((nb + spb - 1) / spb, Q), gr(2 + lazy, Q);
+            const size_t dyn = conn2_lds_bytes(GLc);
+            if (opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy);
+            if (GLc == 16) hipLaunchKernelGGL(k_conn2<16>, g2, dim3(64), dyn, stream, rcp, b, nb, vwords);
+            else if (GLc == 32) hipLaunchKernelGGL(k_conn2<32>, g2, dim3(64), dyn, stream, rcp, b, nb, vwords);
+            else hipLaunchKernelGGL(k_conn2<64>, g2, dim3(64), dyn, stream, rcp, b, nb, vwords);
+            if (!opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy);
+        }
     } else if (lds_bytes) hipLaunchKernelGGL(k_connect_rrt<true>, cgrid, cblock, lds_bytes, stream, rcp, b, nb, vwords);
     else hipLaunchKernelGGL(k_connect_rrt<false>, cgrid, cblock, 0, stream, rcp, b, nb, vwords);
     ev();
@@ -4423,6 +4446,10 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "kd_lca_steps")) *value = (int64_t)c->counters.lca_next;      // this context's own need: 1 + the last step with a tie that took the structure
     else if (!strcmp(name, "compactions")) *value = c->n_compactions;               // how often the last batch this context led gathered its running rows
     else if (!strcmp(name, "kd_built_after")) *value = c->kd_built_after;           // 1: a tie of the last grow needed the whole kd structure, built after the steps
+    else if (!strcmp(name, "n_heavy")) *value = (int64_t)c->counters.n_heavy;        // samples of this context's last grow with more hits than their LDS list holds (served by a whole wave)
+    else if (!strcmp(name, "conn_wg_waves")) *value = c->opt_conn_wg_waves;
+    else if (!strcmp(name, "conn_riders_first")) *value = c->opt_conn_riders_first ? 1 : 0;
+    else if (!strcmp(name, "nn_wg_waves")) *value = c->opt_nn_wg_waves;
     else if (!strcmp(name, "dp_wide_rows")) *value = (int64_t)c->opt_dp_wide_rows;
     else if (!strcmp(name, "dp_levels")) *value = c->dp.valid ? (int64_t)c->dp.levels : 0;          // levels of the last layered costs (0: the general sweeps ran)
     else if (!strcmp(name, "tamp_streams")) *value = c->opt_tamp_streams;
@@ -4467,6 +4494,9 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "tree_out_blocks")) c->opt_tree_out_blocks = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 1024));
     else if (!strcmp(name, "host_ranks")) { c->opt_host_ranks = value != 0; c->eo.tag = ~0ull; }
     else if (!strcmp(name, "early_wave_steps")) c->opt_early_wave = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 64));
+    else if (!strcmp(name, "conn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("conn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_conn_wg_waves = (uint32_t)value; }
+    else if (!strcmp(name, "conn_riders_first")) c->opt_conn_riders_first = value != 0;
+    else if (!strcmp(name, "nn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("nn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_nn_wg_waves = (uint32_t)value; }
     else if (!strcmp(name, "kd_group")) c->opt_kd_group = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 8));
     else if (!strcmp(name, "tamp_streams")) { if (value != 0 && value != 1) { c->set_err("tamp_streams: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_tamp_streams = (int)value; }
     else if (!strcmp(name, "tamp_wave")) { if (value < 1 || value > 65536) { c->set_err("tamp_wave: 1 .. 65536"); return PORRT_ERR_INVALID; } c->opt_tamp_wave = (uint32_t)value; }

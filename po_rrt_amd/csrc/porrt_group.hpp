@@ -449,11 +449,11 @@ __device__ __forceinline__ void group_nn(const RunConst &rc, uint32_t b, const G
 #ifndef PORRT_NN2_WAVES
 #define PORRT_NN2_WAVES 5
 #endif
-template <int GL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_NN2_WAVES, 8))) void k_nn2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t i0, uint32_t nb, uint32_t vwords, uint32_t cb,
+template <int GL, int WV = 4>
+__global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_NN2_WAVES, 8))) void k_nn2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t i0, uint32_t nb, uint32_t vwords, uint32_t cb,
                                              uint32_t cnb) {
     static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
-    constexpr uint32_t SPB = 256u / GL;
+    constexpr uint32_t SPB = (uint32_t)WV * 64u / GL;      // (WV waves per workgroup; nothing below synchronises beyond the wave)
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     xcd_swizzle(bx, by);
     const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
@@ -558,10 +558,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_NN2_W
     }
 }
 
-// dynamic LDS of k_conn2: per sample the LDS part of its hit list; the page-filing workgroup uses the same bytes as its
-// scratch
+// dynamic LDS of the connect kernels.  A wave's lists hold 4 x kLdsHits hits between them whatever the group size (kHitBytes per
+// 16-lane sample); the riders (page filing, the goal path) use their bytes as scratch.
+//   conn2_lds_bytes       k_conn2: one wave, its lists and nothing else
+//   conn2_riders_lds_bytes  k_conn2_riders: the larger of the riders' scratch areas
+//   conn2_wg4_lds_bytes   k_conn2_wg4 (four waves and the riders in one kernel): the largest of all three
 __host__ __device__ inline size_t conn2_lds_bytes(uint32_t GL) {
-    const size_t a = 4u * (64u / 16u) * kHitBytes;      // per workgroup whatever the group size: a wave's lists hold 4 x kLdsHits hits between them
+    (void)GL;
+    return (64u / 16u) * kHitBytes;
+}
+__host__ __device__ inline size_t conn2_riders_lds_bytes() { return kInsertLds > kGTrackLds ? kInsertLds : kGTrackLds; }
+__host__ __device__ inline size_t conn2_wg4_lds_bytes(uint32_t GL) {
+    const size_t a = 4u * conn2_lds_bytes(GL);
     static_assert(kGTrackLds <= 4u * (64u / 16u) * kHitBytes, "g_track_step uses the same bytes");
     return a > kInsertLds ? a : kInsertLds;
 }
@@ -723,28 +731,12 @@ __device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc, 
 #ifndef PORRT_CONN2_WAVES
 #define PORRT_CONN2_WAVES 4
 #endif
+// One wave's samples of the connect pass (64 / GL of them, GL lanes each): radius search into the sample's LDS list, choice of the
+// parent, rewire candidates; a sample with more hits than its list holds is then served by the whole wave.  `wl`: the wave's lists
+// ((64 / GL) x kLdsHits (GL / 16) hits).  Nothing in here synchronises beyond the wave, so the waves of a workgroup are independent.
 template <int GL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
-    static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
-    constexpr uint32_t SPB = 256u / GL;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
-    uint32_t bx = blockIdx.x, by = blockIdx.y;
-    const uint32_t ns = lazy ? 3u : 2u;         // the rows' special workgroups: page filing, goal-point copies, (lazy) the goal path of the kd order
-    const uint32_t role = xcd_swizzle_roles(bx, by, ns);
-    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
-    nb = row_nb(rc, b, nb);
-    if (nb == 0) return;                        // (a row that has stopped, or does not run this step)
-    if (role == 0) { insert_step_pages(rc, b, nb, vwords, lds_dyn); return; }    // the page-filing workgroup
-    if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
-    const uint32_t lane = threadIdx.x & 63u, si = threadIdx.x / GL;
-    const uint32_t slot = bx * SPB + si;
-    // first round trip: everything that depends on nothing
-    const uint32_t N = as_global(rc.n_at)[b];
-    const double T2 = as_global(rc.t2_at)[b];              // rad_T2[N], rrt.rs:121: the size before insertion
-    uint32_t k = 0xFFFFu;
-    double px = 0.0, py = 0.0;
-    if (role == ns && slot < nb) { k = as_global(rc.bq_k)[slot]; px = as_global(rc.bq_x)[slot]; py = as_global(rc.bq_y)[slot]; }
-    if (role == 1) { clone_workgroup(rc, b, vwords, N, T2); return; }
+__device__ __forceinline__ void conn2_wave(const RunConst &rc, uint32_t b, uint32_t vwords, uint32_t N, double T2, uint32_t k, double px, double py, uint8_t *wl) {
+    const uint32_t lane = threadIdx.x & 63u;
     GTeam<GL> tm;
     tm.gl = threadIdx.x % GL;
     tm.base = lane - tm.gl;
@@ -767,7 +759,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
         }
         // a sample's list: the wave's LDS share split between its 64 / GL samples (80 hits at 16 lanes per sample, 320 at 64)
         constexpr uint32_t kHits = kLdsHits * (uint32_t)(GL / 16);
-        uint8_t *hb = lds_dyn + si * (kHits * 28u);
+        uint8_t *hb = wl + (lane / (uint32_t)GL) * (kHits * 28u);
         LdsHits L;
         L.hx = reinterpret_cast<double *>(hb);
         L.hy = L.hx + kHits;
@@ -812,18 +804,82 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
         // written by this wave: its own loads see the entries once its stores are counted down
         __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0)
         __builtin_amdgcn_wave_barrier();
-        uint8_t *wb = lds_dyn + (threadIdx.x >> 6) * (64u / (uint32_t)GL) * ((kLdsHits * (uint32_t)(GL / 16)) * 28u);      // the wave's lists as one (their samples are through)
-        while (hv) {
+        while (hv) {                                // the wave's lists as one (their samples are through)
             const int l = (int)__builtin_ctzll(hv);
             hv &= hv - 1;
             const uint32_t kh = uni((uint32_t)__shfl((int)k, l)), idh = uni((uint32_t)__shfl((int)id, l)), toth = uni((uint32_t)__shfl((int)tot, l));
             const int clrh = (int)uni((uint32_t)__shfl(clr_b, l));
             const double pxh = uni_d(__shfl(px, l)), pyh = uni_d(__shfl(py, l));
-            heavy_sample_wave<GL>(rc, b, N, kh, idh, toth, clrh, pxh, pyh, wb, err);
+            heavy_sample_wave<GL>(rc, b, N, kh, idh, toth, clrh, pxh, pyh, wl, err);
         }
         PORRT_TACC_B(rc, 3);
     }
     if (err) atomicOr(&rc.cnt->err, err);
+}
+
+// The connect pass of a step, one wave per workgroup (64 / GL samples): a wave that is through gives its slot and its lists back at
+// once, whatever its neighbours still do -- a sample on the heavy path keeps one slot and 9 KB busy, not four and 36 KB.
+// grid.x = ceil(nb / (64 / GL)); the step's single workgroups (page filing, goal-point copies, goal path) are k_conn2_riders.
+template <int GL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords) {
+    static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
+    constexpr uint32_t SPB = 64u / GL;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
+    uint32_t bx = blockIdx.x, by = blockIdx.y;
+    xcd_swizzle(bx, by);
+    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
+    nb = row_nb(rc, b, nb);
+    const uint32_t slot = bx * SPB + threadIdx.x / GL;
+    if (bx * SPB >= nb) return;                 // (a row that has stopped, does not run this step, or runs a shorter one)
+    // first round trip: everything that depends on nothing
+    const uint32_t N = as_global(rc.n_at)[b];
+    const double T2 = as_global(rc.t2_at)[b];              // rad_T2[N], rrt.rs:121: the size before insertion
+    uint32_t k = 0xFFFFu;
+    double px = 0.0, py = 0.0;
+    if (slot < nb) { k = as_global(rc.bq_k)[slot]; px = as_global(rc.bq_x)[slot]; py = as_global(rc.bq_y)[slot]; }
+    conn2_wave<GL>(rc, b, vwords, N, T2, k, px, py, lds_dyn);
+}
+
+// The step's single workgroups beside (before or after) k_conn2, 256 threads each: grid = (2 + lazy, Q), blockIdx.x the role --
+// 0 files the new nodes into the region pages, 1 serves the step's copies of the goal point, 2 (lazy) tracks the goal path of the
+// kd order.  They read the snapshot of step b as the samples do and write only what step b + 1 reads, so their place relative
+// to k_conn2 of the same step is free.  Launch index = row * roles + role: the dealing to XCDs of xcd_swizzle_roles.
+// (The register request of k_conn2_wg4: clone_workgroup is a function of both kernels and is compiled to the larger of their budgets.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_riders(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
+    const RunConst &rc = rcp[blockIdx.y];
+    const uint32_t role = blockIdx.x;
+    nb = row_nb(rc, b, nb);
+    if (nb == 0) return;
+    if (role == 0) { insert_step_pages(rc, b, nb, vwords, lds_dyn); return; }
+    if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
+    clone_workgroup(rc, b, vwords, as_global(rc.n_at)[b], as_global(rc.t2_at)[b]);
+}
+
+// The same step as ONE kernel of four-wave workgroups (option conn_wg_waves = 4): the riders are its first 2 + lazy workgroups per
+// row, and a workgroup's lists stay allocated until its slowest wave is through.
+template <int GL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_wg4(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
+    static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
+    constexpr uint32_t SPB = 256u / GL;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
+    uint32_t bx = blockIdx.x, by = blockIdx.y;
+    const uint32_t ns = lazy ? 3u : 2u;         // the rows' special workgroups: page filing, goal-point copies, (lazy) the goal path of the kd order
+    const uint32_t role = xcd_swizzle_roles(bx, by, ns);
+    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
+    nb = row_nb(rc, b, nb);
+    if (nb == 0) return;                        // (a row that has stopped, or does not run this step)
+    if (role == 0) { insert_step_pages(rc, b, nb, vwords, lds_dyn); return; }    // the page-filing workgroup
+    if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
+    const uint32_t slot = bx * SPB + threadIdx.x / GL;
+    // first round trip: everything that depends on nothing
+    const uint32_t N = as_global(rc.n_at)[b];
+    const double T2 = as_global(rc.t2_at)[b];              // rad_T2[N], rrt.rs:121: the size before insertion
+    uint32_t k = 0xFFFFu;
+    double px = 0.0, py = 0.0;
+    if (role == ns && slot < nb) { k = as_global(rc.bq_k)[slot]; px = as_global(rc.bq_x)[slot]; py = as_global(rc.bq_y)[slot]; }
+    if (role == 1) { clone_workgroup(rc, b, vwords, N, T2); return; }
+    conn2_wave<GL>(rc, b, vwords, N, T2, k, px, py, lds_dyn + (threadIdx.x >> 6) * conn2_lds_bytes(GL));
 }
 
 // stand-alone rewire phase 2 for the last step of a launch sequence, GL lanes per sample
