@@ -441,6 +441,47 @@ public:
         compute_expected_costs_to_goals(false);
         return extract_policy();
     }
+    // ---- QMdpPolicyExtractor (qmdp_policy_extractor.rs) on this graph
+    // plan_qmdp :23-35; the costs stay on the device
+    void plan_qmdp() { ctx_.check(porrt_qmdp_plan(ctx_.get())); }
+    // cost_to_goals[world][node]
+    std::vector<std::vector<double>> qmdp_cost_to_goals() const {
+        const size_t n = (size_t)porrt_num_nodes(ctx_.get()), nw = (size_t)n_worlds();
+        std::vector<double> flat(n * nw);
+        ctx_.check(porrt_qmdp_get_costs(ctx_.get(), flat.data()));
+        std::vector<std::vector<double>> out(nw);
+        for (size_t w = 0; w < nw; ++w) out[w].assign(flat.begin() + w * n, flat.begin() + (w + 1) * n);
+        return out;
+    }
+    // react_qmdp :38-49 for every query (start, belief, common horizon) in one call: result[q][world] is paths[world] of query q
+    struct QmdpQuery { State start; BeliefState belief_state; double common_horizon; };
+    std::vector<std::vector<std::vector<State>>> react_qmdp(const std::vector<QmdpQuery> &queries) {
+        const size_t n = queries.size(), nw = (size_t)n_worlds();
+        std::vector<double> s(2 * n), b(n * nw), h(n);
+        for (size_t q = 0; q < n; ++q) {
+            if (queries[q].belief_state.size() != nw) throw std::runtime_error("belief state size should match the number of worlds");
+            s[2 * q] = queries[q].start[0]; s[2 * q + 1] = queries[q].start[1]; h[q] = queries[q].common_horizon;
+            std::copy(queries[q].belief_state.begin(), queries[q].belief_state.end(), b.begin() + q * nw);
+        }
+        std::vector<uint64_t> off(n * nw + 1), common(n + 1);
+        const int64_t total = porrt_qmdp_react(ctx_.get(), s.data(), b.data(), (uint32_t)nw, h.data(), (uint64_t)n, off.data(), common.data(), nullptr, 0);
+        if (total < 0) ctx_.check((int)total);
+        std::vector<double> xy(2 * (size_t)total + 2);
+        if (total) {
+            const int64_t r = porrt_qmdp_react(ctx_.get(), s.data(), b.data(), (uint32_t)nw, h.data(), (uint64_t)n, off.data(), common.data(), xy.data(), (uint64_t)total);
+            if (r < 0) ctx_.check((int)r);
+        }
+        std::vector<std::vector<std::vector<State>>> paths(n, std::vector<std::vector<State>>(nw));
+        for (size_t q = 0; q < n; ++q)
+            for (size_t w = 0; w < nw; ++w)
+                for (uint64_t k = off[q * nw + w]; k < off[q * nw + w + 1]; ++k) paths[q][w].push_back({xy[2 * k], xy[2 * k + 1]});
+        return paths;
+    }
+    struct porrt_qmdp_info qmdp_info() const {
+        struct porrt_qmdp_info i;
+        ctx_.check(porrt_qmdp_info(ctx_.get(), &i));
+        return i;
+    }
     // the expansion without copying the lists to the host (plan_belief_space only needs the policy)
     void build_belief_graph_on_device(const BeliefState &start_belief_state) {
         ctx_.check(porrt_build_belief_graph(ctx_.get(), start_belief_state.data(), (uint32_t)start_belief_state.size()));
@@ -449,6 +490,31 @@ private:
     Context ctx_;
     std::vector<uint64_t> reach_, final_ids_, final_masks_;
 };
+
+// dijkstra over PTOGraphWorldView (pto_graph.rs:245-303) of an explicit graph for every world at once (porrt_qmdp_costs):
+// validities[node_validity[i]] is node i's word of world bits, children[i] its children in push order, finals[w] the final nodes
+// of world w (none: that world's costs are all +inf).  Returns costs[world][node].
+inline std::vector<std::vector<double>> qmdp_costs(const std::vector<State> &states, const std::vector<uint32_t> &node_validity,
+                                                   const std::vector<uint64_t> &validities, const std::vector<std::vector<uint32_t>> &children,
+                                                   const std::vector<std::vector<uint64_t>> &finals, int device = 0) {
+    const size_t n = states.size(), nw = finals.size();
+    std::vector<double> xy(2 * n), flat(n * nw);
+    std::vector<uint64_t> coff(n + 1, 0), foff(nw + 1, 0), fid;
+    std::vector<uint32_t> cid;
+    for (size_t i = 0; i < n; ++i) {
+        xy[2 * i] = states[i][0]; xy[2 * i + 1] = states[i][1];
+        cid.insert(cid.end(), children[i].begin(), children[i].end());
+        coff[i + 1] = cid.size();
+    }
+    for (size_t w = 0; w < nw; ++w) { fid.insert(fid.end(), finals[w].begin(), finals[w].end()); foff[w + 1] = fid.size(); }
+    cid.push_back(0); fid.push_back(0);                      // (never read: keeps data() non-null for empty lists)
+    const int r = porrt_qmdp_costs(device, (uint64_t)n, xy.data(), node_validity.data(), validities.data(), (uint32_t)validities.size(), (uint32_t)nw,
+                                   coff.data(), cid.data(), foff.data(), fid.data(), flat.data());
+    if (r != PORRT_OK) throw std::runtime_error("porrt_qmdp_costs failed (" + std::to_string(r) + ")");
+    std::vector<std::vector<double>> out(nw);
+    for (size_t w = 0; w < nw; ++w) out[w].assign(flat.begin() + w * n, flat.begin() + (w + 1) * n);
+    return out;
+}
 
 // prm.rs:13-109.  init(start) + grow_graph(...) build one roadmap per call pair (porrt_grow_prm evaluates all samples at
 // once; growing an existing roadmap further is a new call with the full iteration count on a sampler reset to its seed).

@@ -293,6 +293,47 @@ int64_t  porrt_refine_policy(porrt_ctx *ctx, uint64_t n, const double *xy, const
  * has 3 nodes or n_iterations is 0) */
 int      porrt_bg_get_refine_info(const porrt_ctx *ctx, double *total_s, double *device_s);
 
+/* ---- the QMDP policy extractor: QMdpPolicyExtractor (src/qmdp_policy_extractor.rs) on the graph of the last
+ * porrt_grow(mode PORRT_MODE_PTO) of this context -- no belief graph: one cost-to-goal field per world and a greedy walk.
+ *
+ * porrt_qmdp_plan is plan_qmdp (qmdp_policy_extractor.rs:23-35): for every world w, cost_to_goals[w] = dijkstra
+ * (pto_graph.rs:275-303) over PTOGraphWorldView{world: w} (pto_graph.rs:245-271: a node is relaxed only where its own validity
+ * has the world) from Reachability::get_final_nodes_for_world(w) (pto_reachability.rs:58-63).  All worlds are solved in one set
+ * of device sweeps over cost planes interleaved per node; any evaluation order ends in the reference's fixpoint, bit for bit.
+ * The costs stay on the device.  PORRT_ERR_INVALID with "We should have final node ids for each world" when a world has no final
+ * node (:28-30), or when the context holds no PTO graph.  get_policy_graph (pto_graph.rs:363-419, an LP) is not offered. */
+int      porrt_qmdp_plan(porrt_ctx *ctx);
+/* out[w * N + id] = cost_to_goals[w][id], n_worlds * N doubles, N = porrt_num_nodes(ctx); +inf where no final node of w is reached */
+int      porrt_qmdp_get_costs(const porrt_ctx *ctx, double *out);
+/* Counts and times of the last porrt_qmdp_plan and the last porrt_qmdp_react after it: nodes, edges (adjacency entries: every
+ * PTO edge counts both ways), worlds, sweeps, queries; milliseconds on the device (HIP events) and wall for each, and of the
+ * nearest-node searches of the react call.  C++ callers write `struct porrt_qmdp_info` (the name is the function's too). */
+struct porrt_qmdp_info { uint64_t nodes, edges, worlds, sweeps, queries; double ms_plan_device, ms_plan_wall, ms_react_device, ms_react_wall, ms_nearest; };
+int      porrt_qmdp_info(const porrt_ctx *ctx, struct porrt_qmdp_info *out);
+/* react_qmdp (qmdp_policy_extractor.rs:38-49) for n queries in one call.  Query q: kd_start = the nearest graph node of
+ * starts[2q..] (nearest_neighbor.rs:48-91, all nodes, on the host); get_common_path (:65-87) follows get_best_expected_child
+ * (:90-108: the first child of strictly least sum over the worlds of cost[w][child] * belief[w], summed in world order; a NaN
+ * -- inf * 0.0 -- or +inf never wins, and without a winner the walk goes to node 0 with cost +inf) while the accumulated norm2 is
+ * below common_horizons[q] and the last expected cost is above 0; then for every world get_path (:51-62) follows get_best_child
+ * (:110-123: the first child of strictly least cost[w][child]) from the node the common path ended on while its cost is above 0.
+ * The node a walk ends on is not part of it.  paths[w] of query q = common path ++ get_path: rows path_off[q * n_worlds + w] ..
+ * path_off[q * n_worlds + w + 1] of path_xy, the first common_len[q] of them the common path.  path_off (n * n_worlds + 1) and
+ * common_len (n) are always written; the states only if the total fits cap (counted in states); the return value is the total.
+ * n = 0 returns 0 and writes path_off[0] = 0.
+ * Errors (PORRT_ERR_INVALID): n_worlds != porrt_n_worlds(ctx) ("belief state size should match the number of worlds", :66-68);
+ * no porrt_qmdp_plan since the last growth on the context; a walk that would emit more than option "qmdp_max_states" states
+ * (default 1 << 16) -- the reference does not terminate on such input (a walk parked on node 0 with nothing finite below it, a
+ * zero-length hop between duplicates); porrt_last_error names the query and the world. */
+int64_t  porrt_qmdp_react(porrt_ctx *ctx, const double *starts, const double *beliefs, uint32_t n_worlds, const double *common_horizons,
+                          uint64_t n, uint64_t *path_off, uint64_t *common_len, double *path_xy, uint64_t cap);
+/* plan_qmdp's costs on an explicit graph given as host arrays (the form of the reference's dijkstra tests, pto_graph.rs:626-678):
+ * node i has state xy[2i..] and validity validities[node_validity[i]] (one word of world bits each, n_worlds <= 64), children as
+ * CSR in push order, and world w has the final nodes final_ids[final_off[w] .. final_off[w + 1]].  out[w * n + id].  A world
+ * without finals is all +inf (pto_graph.rs:658-667).  No context needed. */
+int      porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *node_validity, const uint64_t *validities,
+                          uint32_t n_validities, uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids,
+                          const uint64_t *final_off, const uint64_t *final_ids, double *out);
+
 /* ---- measurement */
 typedef struct {
     uint64_t n_iter;          /* iterations run */
@@ -336,7 +377,8 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * (1, default: the group and roadmap kernels answer "is this segment free" from a summed-area table of the raster when the bounding
  * box of its end pixels holds free pixels only, and walk it otherwise; 0 = always walk), "prm_rows" (porrt_prm_plan_paths: rows of
  * costs swept together in one pass, 1 .. 4096, default 256), "prm_xcd_rows" (1, default: a row's sweep workgroups are placed together
- * on one XCD; 0 = the plain grid order).  None of them changes a result. */
+ * on one XCD; 0 = the plain grid order).  None of them changes a result.  "qmdp_max_states" (porrt_qmdp_react: a walk that would emit
+ * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there. */
 int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
 /* what was in force: "launch_mode" (the last porrt_grow_batch led by this context: 0 = one launch sequence, G = G sequences side by
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a

@@ -17,6 +17,7 @@
 #include "porrt_prm.hpp"
 #include "porrt_edges.hpp"
 #include "porrt_refine.hpp"
+#include "porrt_qmdp.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -387,6 +388,12 @@ struct porrt_ctx {
     uint32_t opt_prm_xcd_rows = 1;         // "prm_xcd_rows": a row's sweep workgroups on one XCD (k_prm_rows_sweep)
     int ensure_prm_weights();
     int64_t prm_plan_paths(const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap);
+    QmdpState qmdp;                        // porrt_qmdp_plan: the per-world costs-to-goal of the last PTO graph (device, porrt_qmdp.hpp)
+    GrowScratch qmdp_scratch;              //   slots 0-4: the plan's buffers, 5-: a react call's
+    uint32_t opt_qmdp_max_states = 1u << 16;       // "qmdp_max_states": a QMDP walk that would emit more states is an error (the reference would not terminate)
+    int qmdp_plan();
+    int64_t qmdp_react(const double *starts, const double *beliefs, uint32_t n_worlds_in, const double *horizons, uint64_t n, uint64_t *path_off,
+                       uint64_t *common_len, double *path_xy, uint64_t cap);
     EdgeOrderState eo;                     // adjacency order of the last PTO graph / roadmap (device)
     std::shared_ptr<void> host_kd;         // the kd-tree of the node coordinates on the host (pre-order ranks, nearest nodes)
     uint64_t host_kd_tag = ~0ull;
@@ -2834,6 +2841,146 @@ int64_t porrt_ctx::prm_plan_paths(const double *starts, const double *goals, uin
     return (int64_t)total;
 }
 
+// plan_qmdp (qmdp_policy_extractor.rs:23-35) on the graph of the last PTO growth: every world needs a final node
+// (Reachability::get_final_nodes_for_world, pto_reachability.rs:58-63), then the cost planes of all worlds in one set of sweeps
+// (porrt_qmdp.hpp).  The planes stay on the device.
+int porrt_ctx::qmdp_plan() {
+    qmdp.valid = false;
+    if (!have_results || mode != PORRT_MODE_PTO) { set_err("qmdp_plan: grow a PTO graph first (porrt_grow, mode PORRT_MODE_PTO)"); return PORRT_ERR_INVALID; }
+    const double t0 = now_s();
+    HIPCHK(hipSetDevice(device));
+    int r = download(DL_TREE | DL_MASKS);
+    if (r) return r;
+    const size_t N = n_nodes;
+    const uint32_t W = (uint32_t)n_worlds, Wp = (W + kQmdpLanes - 1) / kQmdpLanes * kQmdpLanes;
+    if (W < 1 || W > 64 || N >= 0xFFFFFFFFull / Wp) { set_err("qmdp_plan: 1 .. 64 worlds"); return PORRT_ERR_INVALID; }
+    std::vector<unsigned long long> zero(N, 0), valid(N);
+    unsigned long long have = 0;
+    for (uint64_t id : h_final_ids) { zero[id] = h_reach[id] & h_finalmask[id]; have |= zero[id]; }
+    if ((have & ones((int)W)) != ones((int)W)) { set_err("We should have final node ids for each world"); return PORRT_ERR_INVALID; }
+    for (size_t j = 0; j < N; ++j) valid[j] = validities[h_vid[j]];             // validities[nodes[u].validity_id]
+    if ((r = ensure_edge_order())) return r;                        // PTOGraph::children in push order, on the device
+    GrowScratch &sc = qmdp_scratch;
+    double *d_cost = nullptr;
+    unsigned long long *d_zero = nullptr, *d_valid = nullptr;
+    uint8_t *d_dirty = nullptr;
+    uint32_t *d_flags = nullptr;
+    if (sc.get(0, d_cost, N * Wp) != hipSuccess || sc.get(1, d_zero, N) != hipSuccess || sc.get(2, d_valid, N) != hipSuccess ||
+        sc.get(3, d_dirty, 2 * N) != hipSuccess || sc.get(4, d_flags, 8) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err("qmdp_plan: cannot allocate the cost planes");
+        return PORRT_ERR_CAPACITY;
+    }
+    ScopedEvents<2> evs;
+    HIPCHK(evs.create());
+    HIPCHK(hipEventRecord(evs.e[0], stream));
+    HIPCHK(hipMemcpyAsync(d_zero, zero.data(), N * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_valid, valid.data(), N * 8, hipMemcpyHostToDevice, stream));
+    std::string e;
+    uint64_t sweeps = 0;
+    // every PTO edge goes both ways (add_bi_edge, pto.rs:103-120): a node's parents are its children list
+    r = qmdp_solve((uint32_t)N, Wp, eo.d_adj_off, eo.d_adj_id, eo.d_adj_off, eo.d_adj_id, d_nx.p, d_ny.p, d_zero, d_valid, d_cost, d_dirty, d_flags,
+                   stream, sweeps, e);
+    if (r) { set_err(e); return r; }
+    HIPCHK(hipEventRecord(evs.e[1], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    qmdp.info = {};
+    qmdp.info.nodes = N; qmdp.info.edges = 2 * (uint64_t)counters.n_edges; qmdp.info.worlds = W; qmdp.info.sweeps = sweeps;
+    qmdp.info.ms_plan_device = ms;
+    qmdp.info.ms_plan_wall = 1e3 * (now_s() - t0);
+    qmdp.N = (uint32_t)N; qmdp.W = W; qmdp.Wp = Wp; qmdp.d_cost = d_cost; qmdp.tag = results_tag; qmdp.valid = true;
+    return PORRT_OK;
+}
+
+// react_qmdp (qmdp_policy_extractor.rs:38-49) for n queries: the nearest node of every start on the host (the literal kd traversal,
+// as PRM::plan_path's), get_common_path by one wave per query and get_path by one wave per (query, world) on the device, each
+// counted first and written after the offsets are known.  Only lengths and states are downloaded.
+int64_t porrt_ctx::qmdp_react(const double *starts, const double *beliefs, uint32_t n_worlds_in, const double *horizons, uint64_t n, uint64_t *path_off,
+                              uint64_t *common_len, double *path_xy, uint64_t cap) {
+    if (!path_off || (n && (!starts || !beliefs || !horizons || !common_len))) { set_err("qmdp_react: starts, beliefs, horizons, path_off and common_len"); return PORRT_ERR_INVALID; }
+    if ((int)n_worlds_in != n_worlds) { set_err("belief state size should match the number of worlds"); return PORRT_ERR_INVALID; }
+    if (!qmdp.valid || qmdp.tag != results_tag || !have_results) { set_err("qmdp_react: no costs for this graph: call porrt_qmdp_plan after the growth"); return PORRT_ERR_INVALID; }
+    const uint32_t W = qmdp.W;
+    if (n >= (1ull << 31) / W) { set_err("qmdp_react: fewer than 2^31 (query, world) pairs"); return PORRT_ERR_INVALID; }
+    const double t0 = now_s();
+    qmdp.info.queries = n;
+    qmdp.info.ms_react_device = qmdp.info.ms_react_wall = qmdp.info.ms_nearest = 0;
+    path_off[0] = 0;
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(device));
+    int r = download(DL_TREE);
+    if (r) return r;
+    const double tn = now_s();
+    const HostKd *kd = host_kd_of(this);
+    std::vector<uint32_t> q_start(n);
+    for (uint64_t q = 0; q < n; ++q) q_start[q] = (uint32_t)kd->nearest(starts[2 * q], starts[2 * q + 1]);      // kdtree.nearest_neighbor(start): all nodes, unfiltered
+    qmdp.info.ms_nearest = 1e3 * (now_s() - tn);
+    GrowScratch &sc = qmdp_scratch;
+    const size_t nw = (size_t)n * W;
+    QmdpWalk p{};
+    uint32_t *d_start = nullptr;
+    double *d_belief = nullptr, *d_hor = nullptr;
+    unsigned long long *d_off = nullptr;
+    if (sc.get(5, d_start, n) != hipSuccess || sc.get(6, d_belief, nw) != hipSuccess || sc.get(7, d_hor, n) != hipSuccess ||
+        sc.get(8, p.clen, n) != hipSuccess || sc.get(9, p.end_id, n) != hipSuccess || sc.get(10, p.plen, nw) != hipSuccess ||
+        sc.get(11, d_off, nw) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err("qmdp_react: cannot allocate the query arrays");
+        return PORRT_ERR_CAPACITY;
+    }
+    p.N = qmdp.N; p.W = W; p.Wp = qmdp.Wp; p.nq = (uint32_t)n; p.L = opt_qmdp_max_states;
+    p.child_off = eo.d_adj_off; p.child_id = eo.d_adj_id; p.nx = d_nx.p; p.ny = d_ny.p; p.cost = qmdp.d_cost;
+    p.start = d_start; p.belief = d_belief; p.horizon = d_hor; p.off = d_off; p.out = nullptr;
+    ScopedEvents<2> evs;
+    HIPCHK(evs.create());
+    HIPCHK(hipEventRecord(evs.e[0], stream));
+    HIPCHK(hipMemcpyAsync(d_start, q_start.data(), n * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_belief, beliefs, nw * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_hor, horizons, n * 8, hipMemcpyHostToDevice, stream));
+    const dim3 cgrid((unsigned)((n + 3) / 4)), pgrid((unsigned)((nw + 3) / 4));
+    hipLaunchKernelGGL(k_qmdp_common<false>, cgrid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k_qmdp_path<false>, pgrid, dim3(256), 0, stream, p);
+    std::vector<uint32_t> clen(n), plen(nw);
+    HIPCHK(hipMemcpyAsync(clen.data(), p.clen, n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(plen.data(), p.plen, nw * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    const std::string over = ": more than " + std::to_string(opt_qmdp_max_states) + " states (option qmdp_max_states): the reference would not terminate";
+    for (uint64_t q = 0; q < n; ++q) {
+        if (clen[q] == kQmdpWalkOver) { set_err("qmdp_react: query " + std::to_string(q) + ", common path" + over); return PORRT_ERR_INVALID; }
+        for (uint32_t w = 0; w < W; ++w)
+            if (plen[q * W + w] == kQmdpWalkOver) { set_err("qmdp_react: query " + std::to_string(q) + ", world " + std::to_string(w) + over); return PORRT_ERR_INVALID; }
+    }
+    std::vector<unsigned long long> off(nw);
+    uint64_t total = 0;
+    for (uint64_t q = 0; q < n; ++q) {
+        common_len[q] = clen[q];
+        for (uint32_t w = 0; w < W; ++w) {
+            off[q * W + w] = total;
+            path_off[q * W + w] = total;
+            total += (uint64_t)clen[q] + plen[q * W + w];
+        }
+    }
+    path_off[nw] = total;
+    if (path_xy && total && total <= cap) {
+        if (sc.get(12, p.out, 2 * total) != hipSuccess) { (void)hipGetLastError(); set_err("qmdp_react: cannot allocate the paths"); return PORRT_ERR_CAPACITY; }
+        HIPCHK(hipMemcpyAsync(d_off, off.data(), nw * 8, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_qmdp_common<true>, cgrid, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(k_qmdp_path<true>, pgrid, dim3(256), 0, stream, p);
+        HIPCHK(hipMemcpyAsync(path_xy, p.out, 2 * total * 8, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipEventRecord(evs.e[1], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    qmdp.info.ms_react_device = ms;
+    qmdp.info.ms_react_wall = 1e3 * (now_s() - t0);
+    return (int64_t)total;
+}
+
 // Best path cost without downloading the tree (k_best_cost).  1 = found, 0 = no final node, -1 = scratch too small
 // (the caller then walks on the host), other negatives = errors.
 int porrt_ctx::read_best_cost(double *cost, uint64_t *final_id) {
@@ -3370,6 +3517,7 @@ void porrt_destroy(porrt_ctx *c) {
     c->mmp_scratch.free_all();
     c->refine_scratch.free_all();
     c->prm_paths_scratch.free_all();
+    c->qmdp_scratch.free_all();
     for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
@@ -4309,6 +4457,108 @@ int porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const u
     return r;
 }
 
+// ---- QmdpPolicyExtractor (qmdp_policy_extractor.rs; porrt_qmdp.hpp)
+int porrt_qmdp_plan(porrt_ctx *c) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int { return c->qmdp_plan(); });
+}
+
+static bool qmdp_ok(const porrt_ctx *c) { return c && c->have_results && c->qmdp.valid && c->qmdp.tag == c->results_tag; }
+
+int porrt_qmdp_get_costs(const porrt_ctx *cc, double *out) {
+    porrt_ctx *c = const_cast<porrt_ctx *>(cc);
+    if (!c || !out) return PORRT_ERR_INVALID;
+    if (!qmdp_ok(c)) { c->set_err("qmdp_get_costs: no costs for this graph: call porrt_qmdp_plan after the growth"); return PORRT_ERR_INVALID; }
+    return abi_guard([&]() -> int {
+        HIPCHK_CTX(c, hipSetDevice(c->device));
+        const size_t cells = (size_t)c->qmdp.N * c->qmdp.W;
+        double *d_rows = nullptr;
+        if (c->qmdp_scratch.get(13, d_rows, cells) != hipSuccess) { (void)hipGetLastError(); c->set_err("qmdp_get_costs: cannot allocate"); return (int)PORRT_ERR_CAPACITY; }
+        hipLaunchKernelGGL(k_qmdp_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, c->qmdp.N, c->qmdp.W, c->qmdp.Wp,
+                           (const double *)c->qmdp.d_cost, d_rows);
+        HIPCHK_CTX(c, hipMemcpyAsync(out, d_rows, cells * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK_CTX(c, hipStreamSynchronize(c->stream));
+        return (int)PORRT_OK;
+    });
+}
+
+int porrt_qmdp_info(const porrt_ctx *c, struct porrt_qmdp_info *out) {
+    if (!c || !out) return PORRT_ERR_INVALID;
+    if (!qmdp_ok(c)) { const_cast<porrt_ctx *>(c)->set_err("qmdp_info: no costs for this graph: call porrt_qmdp_plan after the growth"); return PORRT_ERR_INVALID; }
+    *out = c->qmdp.info;
+    return PORRT_OK;
+}
+
+int64_t porrt_qmdp_react(porrt_ctx *c, const double *starts, const double *beliefs, uint32_t n_worlds, const double *common_horizons, uint64_t n,
+                         uint64_t *path_off, uint64_t *common_len, double *path_xy, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() -> int { out = c->qmdp_react(starts, beliefs, n_worlds, common_horizons, n, path_off, common_len, path_xy, cap); return out < 0 ? (int)out : (int)PORRT_OK; });
+    return r < 0 ? r : out;
+}
+
+// plan_qmdp's costs on an explicit graph (host arrays in, costs out): the form the reference's own dijkstra tests are in
+// (pto_graph.rs:626-678).  A world without finals is all +inf here.
+int porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *node_validity, const uint64_t *validities, uint32_t n_validities,
+                     uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids, const uint64_t *final_off, const uint64_t *final_ids,
+                     double *out) {
+    if (!n || !xy || !node_validity || !validities || !child_off || !final_off || !out || n_worlds < 1 || n_worlds > 64 || !n_validities) return PORRT_ERR_INVALID;
+    const uint32_t W = n_worlds, Wp = (W + kQmdpLanes - 1) / kQmdpLanes * kQmdpLanes;
+    if (n >= 0xFFFFFFFFull / Wp || child_off[0] != 0 || final_off[0] != 0) return PORRT_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) if (node_validity[i] >= n_validities || child_off[i + 1] < child_off[i]) return PORRT_ERR_INVALID;
+    for (uint32_t w = 0; w < W; ++w) if (final_off[w + 1] < final_off[w]) return PORRT_ERR_INVALID;
+    const uint64_t nc = child_off[n], nf = final_off[W];
+    if ((nc && !child_ids) || (nf && !final_ids)) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < nf; ++k) if (final_ids[k] >= n) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int {
+        if (hipSetDevice(device) != hipSuccess) return (int)PORRT_ERR_DEVICE;
+        std::vector<double> hx(n), hy(n);
+        std::vector<unsigned long long> zero(n, 0), valid(n), par_off(n + 1, 0);
+        std::vector<uint32_t> par_id(nc);
+        for (uint64_t i = 0; i < n; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; valid[i] = validities[node_validity[i]]; }
+        for (uint32_t w = 0; w < W; ++w)
+            for (uint64_t k = final_off[w]; k < final_off[w + 1]; ++k) zero[final_ids[k]] |= 1ull << w;
+        // parents: the transposed children lists (who to evaluate again when a node improves)
+        for (uint64_t k = 0; k < nc; ++k) ++par_off[child_ids[k] + 1];
+        for (uint64_t i = 0; i < n; ++i) par_off[i + 1] += par_off[i];
+        {
+            std::vector<unsigned long long> at(par_off.begin(), par_off.end() - 1);
+            for (uint64_t u = 0; u < n; ++u)
+                for (uint64_t k = child_off[u]; k < child_off[u + 1]; ++k) par_id[at[child_ids[k]]++] = (uint32_t)u;
+        }
+        std::vector<void *> owned;
+        auto up = [&](const void *src, size_t bytes) -> void * {
+            void *d = nullptr;
+            if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+            owned.push_back(d);
+            if (bytes && src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return d;
+        };
+        const double *d_x = (const double *)up(hx.data(), n * 8), *d_y = (const double *)up(hy.data(), n * 8);
+        const unsigned long long *d_coff = (const unsigned long long *)up(child_off, (n + 1) * 8), *d_poff = (const unsigned long long *)up(par_off.data(), (n + 1) * 8);
+        const uint32_t *d_cid = (const uint32_t *)up(child_ids, nc * 4), *d_pid = (const uint32_t *)up(par_id.data(), nc * 4);
+        const unsigned long long *d_zero = (const unsigned long long *)up(zero.data(), n * 8), *d_valid = (const unsigned long long *)up(valid.data(), n * 8);
+        double *d_cost = (double *)up(nullptr, (size_t)n * Wp * 8), *d_rows = (double *)up(nullptr, (size_t)n * W * 8);
+        uint8_t *d_dirty = (uint8_t *)up(nullptr, 2 * n);
+        uint32_t *d_flags = (uint32_t *)up(nullptr, 8 * 4);
+        int r = PORRT_ERR_DEVICE;
+        if (d_x && d_y && d_coff && d_poff && d_cid && d_pid && d_zero && d_valid && d_cost && d_rows && d_dirty && d_flags) {
+            std::string err;
+            uint64_t sweeps = 0;
+            r = qmdp_solve((uint32_t)n, Wp, d_coff, d_cid, d_poff, d_pid, d_x, d_y, d_zero, d_valid, d_cost, d_dirty, d_flags, nullptr, sweeps, err);
+            if (r == PORRT_OK) {
+                const size_t cells = (size_t)n * W;
+                hipLaunchKernelGGL(k_qmdp_rows, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, (uint32_t)n, W, Wp, (const double *)d_cost, d_rows);
+                if (hipMemcpy(out, d_rows, cells * 8, hipMemcpyDeviceToHost) != hipSuccess) r = PORRT_ERR_DEVICE;
+            }
+        }
+        (void)hipGetLastError();
+        for (void *d : owned) (void)hipFree(d);
+        return r;
+    });
+}
+
 // ---- MapShelfDomainTampRRT::plan(.., BranchAndBound) (porrt_tamp.hpp)
 int64_t porrt_tamp_rrt_plan(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
                             double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K) {
@@ -4458,6 +4708,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "tamp_search")) *value = c->opt_tamp_search;
     else if (!strcmp(name, "prm_rows")) *value = c->opt_prm_rows;
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
+    else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4504,6 +4755,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "tamp_search")) { if (value < 0 || value > 2) { c->set_err("tamp_search: 0 (BranchAndBound), 1 (AStar), 2 (BranchAndBoundMultipleViewPoints)"); return PORRT_ERR_INVALID; } c->opt_tamp_search = (int)value; }
     else if (!strcmp(name, "prm_rows")) { if (value < 1 || value > 4096) { c->set_err("prm_rows: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_prm_rows = (uint32_t)value; }
     else if (!strcmp(name, "prm_xcd_rows")) c->opt_prm_xcd_rows = value != 0;
+    else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again
     if (strcmp(name, "profile") && c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }

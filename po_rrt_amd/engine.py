@@ -45,6 +45,7 @@ SYMBOLS = [
     "porrt_graph_file_num_nodes", "porrt_graph_file_num_children", "porrt_graph_file_num_parents", "porrt_graph_file_num_validities",
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
     "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
+    "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
 ]
 
 
@@ -69,6 +70,13 @@ class PrmPathsInfo(C.Structure):
     """struct porrt_prm_paths_info"""
     _fields_ = [("queries", C.c_uint64), ("rows", C.c_uint64), ("sweeps", C.c_uint64), ("passes", C.c_uint64),
                 ("ms_device", C.c_double), ("ms_wall", C.c_double), ("ms_nearest", C.c_double)]
+
+
+class QmdpInfo(C.Structure):
+    """struct porrt_qmdp_info"""
+    _fields_ = [("nodes", C.c_uint64), ("edges", C.c_uint64), ("worlds", C.c_uint64), ("sweeps", C.c_uint64), ("queries", C.c_uint64),
+                ("ms_plan_device", C.c_double), ("ms_plan_wall", C.c_double), ("ms_react_device", C.c_double), ("ms_react_wall", C.c_double),
+                ("ms_nearest", C.c_double)]
 
 
 class TreeDeviceView(C.Structure):
@@ -219,6 +227,11 @@ def load_library():
     sig("porrt_tamp_rrt_get_info", C.c_int, vp, C.POINTER(TampInfo))
     sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
     sig("porrt_tamp_shortcut_paths", C.c_int, vp, C.c_void_p, _u64p, C.c_uint64, C.c_void_p)
+    sig("porrt_qmdp_plan", C.c_int, vp)
+    sig("porrt_qmdp_get_costs", C.c_int, vp, _f64p)
+    sig("porrt_qmdp_info", C.c_int, vp, C.POINTER(QmdpInfo))
+    sig("porrt_qmdp_react", C.c_int64, vp, _f64p, _f64p, C.c_uint32, _f64p, C.c_uint64, _u64p, _u64p, C.c_void_p, C.c_uint64)
+    sig("porrt_qmdp_costs", C.c_int, C.c_int, C.c_uint64, _f64p, _u32p, _u64p, C.c_uint32, C.c_uint32, _u64p, _u32p, _u64p, _u64p, _f64p)
     _LIB = L
     return L
 
@@ -536,6 +549,39 @@ class Engine:
         self._chk(self._l.porrt_prm_paths_info(self._c, C.byref(i)))
         return {k: getattr(i, k) for k, _ in PrmPathsInfo._fields_}
 
+    # ---- QMdpPolicyExtractor (qmdp_policy_extractor.rs)
+    def qmdp_plan(self):
+        """plan_qmdp (:23-35) on the graph of the last PTO growth; the costs stay on the device"""
+        self._chk(self._l.porrt_qmdp_plan(self._c))
+
+    def qmdp_costs(self):
+        """cost_to_goals as an (n_worlds, N) array"""
+        out = np.zeros((self.n_worlds(), self.num_nodes()))
+        self._chk(self._l.porrt_qmdp_get_costs(self._c, out.reshape(-1)))
+        return out
+
+    def qmdp_react(self, starts, beliefs, horizons, with_common_len=False):
+        """react_qmdp (:38-49) for every (starts[i], beliefs[i], horizons[i]) in one call: a list with one entry per query, each a list
+        of n_worlds (k, 2) arrays (paths[w]); with_common_len also returns the number of common-path states of every query"""
+        s, b, h = _f64(starts).reshape(-1, 2), np.atleast_2d(_f64(beliefs)), _f64(horizons).reshape(-1)
+        n, nw = len(s), b.shape[1]
+        if len(b) != n or len(h) != n:
+            raise ValueError("qmdp_react: one belief and one horizon per start")
+        off, cl = np.zeros(n * nw + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        args = (self._c, s.reshape(-1), np.ascontiguousarray(b).reshape(-1), nw, h, n, off, cl)
+        total = self._chk(int(self._l.porrt_qmdp_react(*args, None, 0)))
+        xy = np.zeros((total, 2))
+        if total:
+            self._chk(int(self._l.porrt_qmdp_react(*args, xy.ctypes.data_as(C.c_void_p), total)))
+        paths = [[xy[int(off[q * nw + w]):int(off[q * nw + w + 1])] for w in range(nw)] for q in range(n)]
+        return (paths, cl[:n].copy()) if with_common_len else paths
+
+    def qmdp_info(self):
+        """porrt_qmdp_info of the last qmdp_plan / qmdp_react"""
+        i = QmdpInfo()
+        self._chk(self._l.porrt_qmdp_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in QmdpInfo._fields_}
+
     # ---- belief-space expansion (PTO::build_belief_graph, pto.rs:185-259)
     def build_belief_graph(self, start_belief):
         b = np.ascontiguousarray(start_belief, dtype=np.float64)
@@ -757,6 +803,30 @@ def conditional_dijkstra(xy, belief_row, beliefs, types, children, parents, fina
     if rc < 0:
         raise RuntimeError("porrt_conditional_dijkstra failed (%d)" % rc)
     return dist
+
+
+def qmdp_costs_explicit(xy, node_validity, validities, children, finals, device=0):
+    """porrt_qmdp_costs: plan_qmdp's costs (one dijkstra per world over PTOGraphWorldView, pto_graph.rs:245-303) of an explicit graph
+    on the GPU.  validities: one word of world bits per validity id; children: per-node lists in push order; finals: per-world lists
+    of final node ids (an empty list: that world's costs are all +inf).  Returns an (n_worlds, n) array."""
+    L = load_library()
+    n, nw = len(children), len(finals)
+
+    def csr(lists, dt):
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c) for c in lists])
+        ids = np.array([i for c in lists for i in c], dtype=dt)
+        return off, (ids if len(ids) else np.zeros(1, dtype=dt))
+
+    co, ci = csr(children, np.uint32)
+    fo, fi = csr(finals, np.uint64)
+    val = np.ascontiguousarray(validities, dtype=np.uint64)
+    out = np.zeros((nw, n))
+    rc = L.porrt_qmdp_costs(device, n, _f64(xy).reshape(-1), np.ascontiguousarray(node_validity, dtype=np.uint32), val, len(val), nw,
+                            co, ci, fo, fi, out.reshape(-1))
+    if rc != 0:
+        raise RuntimeError("porrt_qmdp_costs failed (%d)" % rc)
+    return out
 
 
 def exchange_decide(entries):
