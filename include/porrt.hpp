@@ -408,6 +408,42 @@ public:
         }
         return policy;
     }
+    // extract_policy (belief_graph.rs:184-267) started at every belief node of starts, walked on the device in one call
+    // (porrt_bg_extract_policies): one Policy per start, nullopt where there is none (statuses, when asked for: 1 no finite cost,
+    // 2 the walk returns onto its own path, 3 an assertion of the reference fails, 4 more than option "policy_max_nodes" nodes)
+    std::vector<std::optional<Policy>> extract_policies(const std::vector<size_t> &starts, std::vector<uint8_t> *statuses = nullptr) {
+        const size_t nq = starts.size();
+        std::vector<uint64_t> st(starts.begin(), starts.end()), off(nq + 1, 0);
+        std::vector<uint8_t> status(nq + 1, 0);
+        std::vector<double> cost(nq + 1, 0.0);
+        const int64_t n = porrt_bg_extract_policies(ctx_.get(), st.data(), nq, off.data(), status.data(), cost.data(), nullptr, nullptr, nullptr, 0);
+        if (n < 0) ctx_.check((int)n);
+        std::vector<uint64_t> oid((size_t)n);
+        std::vector<int64_t> par((size_t)n);
+        std::vector<uint8_t> leaf((size_t)n);
+        if (n > 0 && porrt_bg_get_policies(ctx_.get(), oid.data(), par.data(), leaf.data(), (uint64_t)n) != n) ctx_.check(PORRT_ERR_INVALID);
+        const size_t nb = porrt_bg_num_beliefs(ctx_.get()), nw = (size_t)n_worlds();
+        std::vector<double> flat(nb * nw);
+        ctx_.check(porrt_bg_get_beliefs(ctx_.get(), flat.data()));
+        std::vector<std::optional<Policy>> out(nq);
+        for (size_t q = 0; q < nq; ++q) {
+            if (status[q]) continue;
+            Policy policy;
+            policy.expected_costs = cost[q];
+            for (size_t k = 0, o = (size_t)off[q]; o < (size_t)off[q + 1]; ++k, ++o) {
+                PolicyNode pn;
+                pn.state = graph.nodes[oid[o] / nb].state;
+                pn.belief_state.assign(flat.begin() + (oid[o] % nb) * nw, flat.begin() + (oid[o] % nb + 1) * nw);
+                pn.original_node_id = (size_t)oid[o];
+                if (par[o] >= 0) { pn.parent = (size_t)par[o]; policy.nodes[(size_t)par[o]].children.push_back(k); }
+                policy.nodes.push_back(std::move(pn));
+                if (leaf[o]) policy.leafs.push_back(k);
+            }
+            out[q] = std::move(policy);
+        }
+        if (statuses) statuses->assign(status.begin(), status.begin() + nq);
+        return out;
+    }
     // PTOPolicyRefiner::new(&policy, ..).refine_solution(RefinmentStrategy::PartialShortCut(n_iterations)) (pto_policy_refiner.rs:87-124)
     // of the policy extract_policy() returned last: node states are the refined ones; a piece start the reference's recompose leaves
     // unconnected (after a one-node piece that branches) has no parent

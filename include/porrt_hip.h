@@ -260,6 +260,55 @@ int      porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, co
                                     const uint64_t *child_off, const uint32_t *child_ids, const uint64_t *parent_off, const uint32_t *parent_ids,
                                     const uint64_t *finals, uint64_t n_final, double *dist);
 
+/* ---- policies from many belief nodes in one call: extract_policy / get_best_expected_children (src/belief_graph.rs:184-267)
+ * started at belief node starts[q] instead of node 0, for n starts, walked on the device (one wave per query, porrt_policy.hpp).
+ * The expected costs of the last porrt_bg_compute_expected_costs are costs-to-goal of every belief node, so no new build and no
+ * new sweeps are needed.  Query q's root is policy node 0 with original id starts[q] and is_leaf 0, whatever its cost (:192);
+ * children are clustered by belief id, clusters in ascending id order; within a cluster p = transition_probability(node, the
+ * cluster's first child) (common.rs:187-190) and the winner is the first child in children order of strictly least
+ * p * (norm2(node, child) + dist[child]), a cluster of +inf / NaN costs keeping its first child; winners become policy nodes in
+ * cluster order, is_leaf = (dist[child] == 0.0), and the non-leaf ones are expanded last pushed first.  For starts[q] = 0 the
+ * policy is, node for node, that of porrt_bg_extract_policy.
+ * A start at a final node (dist 0) is walked exactly as the reference would walk it, not special-cased: its root is no leaf and
+ * is expanded; whether that ends in status 0 or 3 follows from the graph (a child of positive cost fails :261).
+ * status[q]: 0 OK; 1 dist[starts[q]] is not finite, no policy from there; 2 the walk returns to a belief node on its own path
+ * (the reference does not terminate); 3 an assertion of the reference fails (p > 0.0, :250, or p * dist[best] <= dist[node],
+ * :261); 4 the policy would exceed option "policy_max_nodes" (1 .. 2^24, default 65536) or a node has more than 65535 children.
+ * A query whose status is not 0 contributes no policy nodes and does not void the others; porrt_last_error names the first one.
+ * pol_off (n + 1 entries), status and expected_costs (dist[starts[q]]) are always written: the nodes of query q are rows
+ * pol_off[q] .. pol_off[q + 1] of original_ids / parents / is_leaf, parents[k] an index into the same policy (-1 for its root).
+ * The node arrays are written only if the total fits in cap.  Returns the total number of policy nodes, or a negative error:
+ * PORRT_ERR_INVALID for a start >= porrt_bg_num_nodes, or when the belief graph or its costs are missing or stale (a regrowth, a
+ * new belief graph without new costs); PORRT_ERR_CAPACITY when the device pool cannot be allocated.  n = 0 returns 0 and writes
+ * pol_off[0] = 0.  The policy porrt_bg_refine_policy refines stays that of the last porrt_bg_extract_policy; a policy from this
+ * call is refined through porrt_refine_policy. */
+int64_t  porrt_bg_extract_policies(porrt_ctx *ctx, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status,
+                                   double *expected_costs, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+/* The nodes of the last porrt_bg_extract_policies, without recomputing them (same total, same cap rule).  An error before the
+ * first call and once the graph, the belief graph or the costs have changed. */
+int64_t  porrt_bg_get_policies(const porrt_ctx *ctx, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+/* The same on the multi-modal belief graph and the costs of the last porrt_mm_compute_expected_costs, clustered by the nodes'
+ * belief ids (porrt_mm_bg_get_graph); xy (2 per node, may be NULL) receives the nodes' states as porrt_mm_extract_policy gives
+ * them.  The policy porrt_mm_refine_policy refines stays that of the last porrt_mm_extract_policy. */
+int64_t  porrt_mm_extract_policies(porrt_ctx *ctx, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status,
+                                   double *expected_costs, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap);
+int64_t  porrt_mm_get_policies(const porrt_ctx *ctx, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap);
+/* The same on an explicit belief graph given as host arrays, as porrt_conditional_dijkstra takes it (the walk reads neither the
+ * node types nor the parents lists): node i has state xy[2i..], belief vector beliefs[belief_row[i]], clustering key
+ * belief_ids[i] and expected cost dist[i] (any doubles: +inf and NaN follow the rules above).  The reference's own policy
+ * assertions on its two known-answer graphs (belief_graph.rs:531-543, 563-566) run on the device through this entry.
+ * policy_max_nodes: 1 .. 2^24, 0 = 65536.  No context needed. */
+int64_t  porrt_extract_policies(int device, uint64_t n_nodes, const double *xy, const uint32_t *belief_row, const double *beliefs,
+                                uint32_t n_belief_rows, uint32_t n_worlds, const uint32_t *belief_ids, const uint64_t *child_off,
+                                const uint32_t *child_ids, const double *dist, const uint64_t *starts, uint64_t n, uint64_t policy_max_nodes,
+                                uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids, int64_t *parents,
+                                uint8_t *is_leaf, uint64_t cap);
+/* Counts and times of the last porrt_bg_extract_policies or porrt_mm_extract_policies of the context, whichever ran last: queries,
+ * those with status 0, policy nodes in all, nodes of the longest policy; milliseconds on the device (HIP events around the
+ * kernels) and wall (the whole call).  C++ callers write `struct porrt_policies_info` (the name is the function's too). */
+struct porrt_policies_info { uint64_t queries, ok, nodes, max_nodes; double ms_device, ms_wall; };
+int      porrt_policies_info(const porrt_ctx *ctx, struct porrt_policies_info *out);
+
 /* ---- policy refinement: PTOPolicyRefiner::refine_solution(RefinmentStrategy::PartialShortCut(n_iterations))
  * (src/pto_policy_refiner.rs:87-124; pto_c.rs:217-218 runs it inside plan()).  The policy is cut into pieces (Policy::decompose,
  * common.rs:85-129: breadth-first from node 0, a piece runs until a node with 0 or >= 2 children); every piece of >= 3 nodes is
@@ -378,7 +427,8 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * box of its end pixels holds free pixels only, and walk it otherwise; 0 = always walk), "prm_rows" (porrt_prm_plan_paths: rows of
  * costs swept together in one pass, 1 .. 4096, default 256), "prm_xcd_rows" (1, default: a row's sweep workgroups are placed together
  * on one XCD; 0 = the plain grid order).  None of them changes a result.  "qmdp_max_states" (porrt_qmdp_react: a walk that would emit
- * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there. */
+ * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there.  "policy_max_nodes" (porrt_bg_extract_policies,
+ * porrt_mm_extract_policies: a policy that would have more nodes is status 4, 1 .. 2^24, default 1 << 16) is one too. */
 int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
 /* what was in force: "launch_mode" (the last porrt_grow_batch led by this context: 0 = one launch sequence, G = G sequences side by
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a

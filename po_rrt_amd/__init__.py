@@ -7,4 +7,4 @@ query-sharded job (RCCL); `sharding` holds the query partition.  The C++ mirror 
 RRT / PTO / PRM interface is include/porrt.hpp.
 """
 from .engine import (DOMAIN_DOOR, DOMAIN_SHELF, INCOMPLETE, MODE_PTO, MODE_RRT, OK, Comm, Engine, PorrtError,  # noqa: F401
-                     conditional_dijkstra, exchange_decide, load_library)
+                     conditional_dijkstra, exchange_decide, extract_policies_explicit, load_library)

@@ -172,6 +172,7 @@ struct GrowScratch {
 };
 
 #include "porrt_mmplan.hpp"
+#include "porrt_policy.hpp"
 
 struct porrt_ctx {
     int device = 0;
@@ -360,6 +361,17 @@ struct porrt_ctx {
     DpState dp;                            // porrt_bg_compute_expected_costs: dist per belief node (device)
     int compute_expected_costs();
     int extract_policy();
+    // ---- policies from many belief nodes in one call (porrt_policy.hpp): the last call's answers, on the context's graph and on the multi-modal one
+    PoliciesResult policies, mm_policies;
+    GrowScratch policies_scratch;
+    uint32_t opt_policy_max_nodes = 1u << 16;       // "policy_max_nodes": a policy that would have more nodes is status 4
+    int policies_last = 0;                 // whose info porrt_policies_info hands out: 1 = policies, 2 = mm_policies
+    uint64_t costs_stamp = ~0ull;          // bg_stamp after the last successful expected-cost run
+    uint64_t mm_costs_runs = 0;            // porrt_mm_compute_expected_costs calls of this context
+    int64_t extract_policies(const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
+                             int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+    int64_t mm_extract_policies(const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
+                                int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap);
     // ---- policy refinement (porrt_refine.hpp): the policy porrt_bg_extract_policy last handed out, and what it was made from
     uint64_t bg_stamp = 0;                 // belief graph builds and expected-cost runs of this context
     bool pol_out = false;
@@ -1803,6 +1815,7 @@ int porrt_ctx::compute_expected_costs() {
     if (bg.support_shrinks && !opt_dp_sweeps) r = dp_run_layered(dp, bg, c, finals, stream, e, opt_dp_wide_rows);
     else r = dp_run(dp, c, true, finals, stream, e);
     if (r) set_err(e);
+    else costs_stamp = bg_stamp;
     return r;
 }
 
@@ -1824,6 +1837,42 @@ int porrt_ctx::extract_policy() {
     if (r) set_err(e);
     else { pol_tag = results_tag; pol_stamp = bg_stamp; }
     return r;
+}
+
+// copies the answers of an extract_policies call into the caller's arrays (the node arrays when cap holds the total)
+static int64_t policies_copy_out(const PoliciesResult &res, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
+                                 int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
+    const uint64_t n = res.status.size(), total = res.off.back();
+    if (pol_off) memcpy(pol_off, res.off.data(), (n + 1) * sizeof(uint64_t));
+    if (n && status) memcpy(status, res.status.data(), n);
+    if (n && expected_costs) memcpy(expected_costs, res.cost.data(), n * sizeof(double));
+    if (total && total <= cap) {
+        if (original_ids) memcpy(original_ids, res.original.data(), total * sizeof(uint64_t));
+        if (parents) memcpy(parents, res.parent.data(), total * sizeof(int64_t));
+        if (is_leaf) memcpy(is_leaf, res.leaf.data(), total);
+        if (xy && res.xy.size() == 2 * total) memcpy(xy, res.xy.data(), 2 * total * sizeof(double));
+    }
+    return (int64_t)total;
+}
+
+// extract_policy (belief_graph.rs:184-267) from n belief nodes of the context's graph, on the device (porrt_policy.hpp)
+int64_t porrt_ctx::extract_policies(const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
+                                    int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    policies.valid = false;
+    if (!pol_off || (n && (!starts || !status || !expected_costs))) { set_err("extract_policies: starts, pol_off, status and expected_costs"); return PORRT_ERR_INVALID; }
+    if (!bg.valid || !dp.valid || bg_graph_tag != results_tag || costs_stamp != bg_stamp) {
+        set_err("extract_policies: compute the expected costs first (porrt_bg_compute_expected_costs)");
+        return PORRT_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(device));
+    std::string e;
+    const int r = pol_extract(policies_scratch, dp.last, true, nullptr, starts, n, opt_policy_max_nodes, stream, policies, e);
+    if (r) { set_err(e); return r; }
+    if (!e.empty()) set_err(e);
+    policies.tag = results_tag; policies.stamp = bg_stamp;
+    policies.valid = true;
+    policies_last = 1;
+    return policies_copy_out(policies, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
 }
 
 // PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of a policy given as host arrays: node k
@@ -2540,6 +2589,7 @@ int porrt_ctx::mm_compute_expected_costs() {
     HIPCHK(hipSetDevice(device));
     s.costs_gen = s.policy_gen = ~0ull;
     s.dp.have_policy = false;
+    ++mm_costs_runs;
     const double t0 = now_s();
     std::string e;
     int r;
@@ -2585,6 +2635,35 @@ int porrt_ctx::mm_extract_policy() {
     s.t_extract = now_s() - t0;
     s.policy_gen = s.gen;
     return PORRT_OK;
+}
+
+// the same from n belief nodes of the multi-modal graph, clustered by belief id, on the device (porrt_policy.hpp)
+int64_t porrt_ctx::mm_extract_policies(const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
+                                       int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
+    MmPlanState &s = mmp;
+    mm_policies.valid = false;
+    if (!pol_off || (n && (!starts || !status || !expected_costs))) { set_err("mm_extract_policies: starts, pol_off, status and expected_costs"); return PORRT_ERR_INVALID; }
+    if (!mm.valid || !s.valid || s.gen != mm.gen || s.costs_gen != s.gen || !s.dp.valid) {
+        set_err("mm_extract_policies: compute the expected costs of the last belief graph first (porrt_mm_compute_expected_costs)");
+        return PORRT_ERR_INVALID;
+    }
+    HIPCHK(hipSetDevice(device));
+    std::string e;
+    const int r = pol_extract(policies_scratch, s.dp.last, false, s.d_bid, starts, n, opt_policy_max_nodes, stream, mm_policies, e);
+    if (r) { set_err(e); return r; }
+    if (!e.empty()) set_err(e);
+    const size_t total = mm_policies.original.size();
+    mm_policies.xy.resize(2 * total);
+    for (size_t k = 0; k < total; ++k) {
+        const uint64_t id = mm_policies.original[k];
+        const uint32_t m = mm_mode_of(s, id);
+        const uint64_t local = id - s.mode_off[m];
+        mm_policies.xy[2 * k] = mm.modes[m].xy[2 * local]; mm_policies.xy[2 * k + 1] = mm.modes[m].xy[2 * local + 1];
+    }
+    mm_policies.tag = s.gen; mm_policies.stamp = mm_costs_runs;
+    mm_policies.valid = true;
+    policies_last = 2;
+    return policies_copy_out(mm_policies, pol_off, status, expected_costs, original_ids, parents, is_leaf, xy, cap);
 }
 
 int64_t porrt_ctx::prm_plan_path(const double start[2], const double goal[2], double *path_xy, uint64_t cap) {
@@ -3518,6 +3597,7 @@ void porrt_destroy(porrt_ctx *c) {
     c->refine_scratch.free_all();
     c->prm_paths_scratch.free_all();
     c->qmdp_scratch.free_all();
+    c->policies_scratch.free_all();
     for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
@@ -4223,6 +4303,100 @@ int64_t porrt_bg_extract_policy(porrt_ctx *c, uint64_t *original_ids, int64_t *p
     return (int64_t)n;
 }
 
+// ---- policies from many belief nodes in one call (porrt_policy.hpp)
+int64_t porrt_bg_extract_policies(porrt_ctx *c, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs,
+                                  uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try { return c->extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, cap); }
+    catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int64_t porrt_bg_get_policies(const porrt_ctx *c, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);                      // (for the error text only)
+    const PoliciesResult &res = c->policies;
+    if (!res.valid) { m->set_err("bg_get_policies: no answers: call porrt_bg_extract_policies first"); return PORRT_ERR_INVALID; }
+    if (!c->bg.valid || !c->dp.valid || c->bg_graph_tag != c->results_tag || res.tag != c->results_tag || res.stamp != c->bg_stamp || c->costs_stamp != c->bg_stamp) {
+        m->set_err("bg_get_policies: the graph, the belief graph or the expected costs changed since porrt_bg_extract_policies");
+        return PORRT_ERR_INVALID;
+    }
+    return policies_copy_out(res, nullptr, nullptr, nullptr, original_ids, parents, is_leaf, nullptr, cap);
+}
+int64_t porrt_mm_extract_policies(porrt_ctx *c, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs,
+                                  uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try { return c->mm_extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, xy, cap); }
+    catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int64_t porrt_mm_get_policies(const porrt_ctx *c, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);
+    const PoliciesResult &res = c->mm_policies;
+    const MmPlanState &s = c->mmp;
+    if (!res.valid) { m->set_err("mm_get_policies: no answers: call porrt_mm_extract_policies first"); return PORRT_ERR_INVALID; }
+    if (!c->mm.valid || !s.valid || s.gen != c->mm.gen || s.costs_gen != s.gen || !s.dp.valid || res.tag != s.gen || res.stamp != c->mm_costs_runs) {
+        m->set_err("mm_get_policies: the modes, the belief graph or the expected costs changed since porrt_mm_extract_policies");
+        return PORRT_ERR_INVALID;
+    }
+    return policies_copy_out(res, nullptr, nullptr, nullptr, original_ids, parents, is_leaf, xy, cap);
+}
+int porrt_policies_info(const porrt_ctx *c, struct porrt_policies_info *out) {
+    if (!c || !out || !c->policies_last) return PORRT_ERR_INVALID;
+    const PoliciesResult &res = c->policies_last == 1 ? c->policies : c->mm_policies;
+    if (!res.valid) return PORRT_ERR_INVALID;
+    *out = res.info;
+    return PORRT_OK;
+}
+// the same on an explicit graph (host arrays in): the form the reference's own policy assertions run in
+int64_t porrt_extract_policies(int device, uint64_t n_nodes, const double *xy, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows,
+                               uint32_t n_worlds, const uint32_t *belief_ids, const uint64_t *child_off, const uint32_t *child_ids, const double *dist,
+                               const uint64_t *starts, uint64_t n, uint64_t policy_max_nodes, uint64_t *pol_off, uint8_t *status, double *expected_costs,
+                               uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!n_nodes || !xy || !belief_row || !beliefs || !belief_ids || !child_off || !dist || !pol_off || n_nodes >= 0xFFFFFFFFull || !n_belief_rows)
+        return PORRT_ERR_INVALID;
+    if (n && (!starts || !status || !expected_costs)) return PORRT_ERR_INVALID;
+    if (policy_max_nodes == 0) policy_max_nodes = 1u << 16;
+    if (policy_max_nodes > kPolMaxNodesLimit) return PORRT_ERR_INVALID;
+    if (child_off[0] != 0) return PORRT_ERR_INVALID;
+    for (uint64_t i = 0; i < n_nodes; ++i) if (belief_row[i] >= n_belief_rows || child_off[i + 1] < child_off[i]) return PORRT_ERR_INVALID;
+    const uint64_t nc = child_off[n_nodes];
+    if (nc && !child_ids) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n_nodes) return PORRT_ERR_INVALID;
+    for (uint64_t q = 0; q < n; ++q) if (starts[q] >= n_nodes) return PORRT_ERR_INVALID;
+    try {
+        if (hipSetDevice(device) != hipSuccess) return PORRT_ERR_DEVICE;
+        std::vector<double> hx(n_nodes), hy(n_nodes);
+        for (uint64_t i = 0; i < n_nodes; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
+        std::vector<void *> owned;
+        auto up = [&](const void *src, size_t bytes) -> void * {
+            void *d = nullptr;
+            if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+            owned.push_back(d);
+            if (bytes && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return d;
+        };
+        DpConst c{};
+        c.n = n_nodes; c.B = 1; c.nw = n_worlds;
+        c.nx = (const double *)up(hx.data(), n_nodes * 8); c.ny = (const double *)up(hy.data(), n_nodes * 8);
+        c.bvec = (const uint32_t *)up(belief_row, n_nodes * 4);
+        c.beliefs = (const double *)up(beliefs, (size_t)n_belief_rows * n_worlds * 8);
+        c.child_off = (const unsigned long long *)up(child_off, (n_nodes + 1) * 8);
+        c.child_id = (const uint32_t *)up(child_ids, nc * 4);
+        c.dist = (double *)up(dist, n_nodes * 8);
+        const uint32_t *d_bid = (const uint32_t *)up(belief_ids, n_nodes * 4);
+        int64_t r = PORRT_ERR_DEVICE;
+        GrowScratch sc;
+        if (c.nx && c.ny && c.bvec && c.beliefs && c.child_off && c.child_id && c.dist && d_bid) {
+            PoliciesResult res;
+            std::string err;
+            r = pol_extract(sc, c, false, d_bid, starts, n, policy_max_nodes, nullptr, res, err);
+            if (r == PORRT_OK) r = policies_copy_out(res, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
+        }
+        sc.free_all();
+        for (void *d : owned) (void)hipFree(d);
+        return r;
+    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+
 // copies a refined policy into the caller's arrays when cap holds it
 static void refine_copy_out(const porrt_ctx::RefineOut &o, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *expected_costs) {
     const size_t m = o.parent.size();
@@ -4709,6 +4883,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "prm_rows")) *value = c->opt_prm_rows;
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
+    else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4755,6 +4930,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "tamp_search")) { if (value < 0 || value > 2) { c->set_err("tamp_search: 0 (BranchAndBound), 1 (AStar), 2 (BranchAndBoundMultipleViewPoints)"); return PORRT_ERR_INVALID; } c->opt_tamp_search = (int)value; }
     else if (!strcmp(name, "prm_rows")) { if (value < 1 || value > 4096) { c->set_err("prm_rows: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_prm_rows = (uint32_t)value; }
     else if (!strcmp(name, "prm_xcd_rows")) c->opt_prm_xcd_rows = value != 0;
+    else if (!strcmp(name, "policy_max_nodes")) { if (value < 1 || value > (int64_t)kPolMaxNodesLimit) { c->set_err("policy_max_nodes: 1 .. 2^24"); return PORRT_ERR_INVALID; } c->opt_policy_max_nodes = (uint32_t)value; }
     else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again

@@ -46,6 +46,8 @@ SYMBOLS = [
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
     "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
+    "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
+    "porrt_policies_info",
 ]
 
 
@@ -77,6 +79,12 @@ class QmdpInfo(C.Structure):
     _fields_ = [("nodes", C.c_uint64), ("edges", C.c_uint64), ("worlds", C.c_uint64), ("sweeps", C.c_uint64), ("queries", C.c_uint64),
                 ("ms_plan_device", C.c_double), ("ms_plan_wall", C.c_double), ("ms_react_device", C.c_double), ("ms_react_wall", C.c_double),
                 ("ms_nearest", C.c_double)]
+
+
+class PoliciesInfo(C.Structure):
+    """struct porrt_policies_info"""
+    _fields_ = [("queries", C.c_uint64), ("ok", C.c_uint64), ("nodes", C.c_uint64), ("max_nodes", C.c_uint64),
+                ("ms_device", C.c_double), ("ms_wall", C.c_double)]
 
 
 class TreeDeviceView(C.Structure):
@@ -232,12 +240,32 @@ def load_library():
     sig("porrt_qmdp_info", C.c_int, vp, C.POINTER(QmdpInfo))
     sig("porrt_qmdp_react", C.c_int64, vp, _f64p, _f64p, C.c_uint32, _f64p, C.c_uint64, _u64p, _u64p, C.c_void_p, C.c_uint64)
     sig("porrt_qmdp_costs", C.c_int, C.c_int, C.c_uint64, _f64p, _u32p, _u64p, C.c_uint32, C.c_uint32, _u64p, _u32p, _u64p, _u64p, _f64p)
+    sig("porrt_bg_extract_policies", C.c_int64, vp, _u64p, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_bg_get_policies", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_mm_extract_policies", C.c_int64, vp, _u64p, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_mm_get_policies", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_extract_policies", C.c_int64, C.c_int, C.c_uint64, _f64p, _u32p, _f64p, C.c_uint32, C.c_uint32, _u32p, _u64p, _u32p, _f64p,
+        _u64p, C.c_uint64, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_policies_info", C.c_int, vp, C.POINTER(PoliciesInfo))
     _LIB = L
     return L
 
 
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def _policy_list(off, status, cost, oid, par, leaf, xy=None):
+    """the answers of an extract_policies call as a list: ((oid, par, leaf[, xy]), cost) per query, None where its status is not 0"""
+    out = []
+    for q in range(len(status)):
+        if status[q]:
+            out.append(None)
+            continue
+        a, b = int(off[q]), int(off[q + 1])
+        arrays = (oid[a:b], par[a:b], leaf[a:b]) + ((xy[a:b],) if xy is not None else ())
+        out.append((arrays, float(cost[q])))
+    return out
 
 
 class Engine:
@@ -638,6 +666,47 @@ class Engine:
         self._l.porrt_bg_extract_policy(self._c, oid.ctypes.data_as(C.c_void_p), par.ctypes.data_as(C.c_void_p), leaf.ctypes.data_as(C.c_void_p), n, C.byref(cost))
         return (oid, par, leaf), cost.value
 
+    def extract_policies_raw(self, starts):
+        """porrt_bg_extract_policies as arrays: pol_off [n + 1], status [n], expected costs [n], original ids, parents, leaf flags"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        n = len(st)
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        stp = st if n else np.zeros(1, dtype=np.uint64)
+        total = self._chk(int(self._l.porrt_bg_extract_policies(self._c, stp, n, off, status, cost, None, None, None, 0)))
+        oid, par, leaf = np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
+        if total:
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            self._chk(int(self._l.porrt_bg_get_policies(self._c, p(oid), p(par), p(leaf), total)))
+        return off, status[:n], cost[:n], oid, par, leaf
+
+    def extract_policies(self, starts):
+        """extract_policy (belief_graph.rs:184-267) from every belief node of starts in one device call: a list with
+        ((original belief node ids, parents (-1 = root), leaf flags), expected cost) per query -- None where the query has no policy --
+        and the status array (0 OK, 1 no finite cost, 2 the walk returns onto its own path, 3 an assertion of the reference fails,
+        4 more than option policy_max_nodes nodes)"""
+        off, status, cost, oid, par, leaf = self.extract_policies_raw(starts)
+        return _policy_list(off, status, cost, oid, par, leaf), status
+
+    def mm_extract_policies(self, starts):
+        """the same on the multi-modal belief graph: ((belief node ids, parents, leaf flags, states [k, 2]), expected cost) or None per
+        query, and the status array"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        n = len(st)
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        stp = st if n else np.zeros(1, dtype=np.uint64)
+        total = self._chk(int(self._l.porrt_mm_extract_policies(self._c, stp, n, off, status, cost, None, None, None, None, 0)))
+        oid, par, leaf, xy = np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8), np.zeros((total, 2))
+        if total:
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            self._chk(int(self._l.porrt_mm_get_policies(self._c, p(oid), p(par), p(leaf), p(xy), total)))
+        return _policy_list(off, status[:n], cost[:n], oid, par, leaf, xy), status[:n]
+
+    def policies_info(self):
+        """porrt_policies_info of the last extract_policies / mm_extract_policies: queries, ok, nodes, max_nodes, ms_device, ms_wall"""
+        i = PoliciesInfo()
+        self._chk(self._l.porrt_policies_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in PoliciesInfo._fields_}
+
     # ---- policy refinement (PTOPolicyRefiner::refine_solution(PartialShortCut(n)), pto_policy_refiner.rs:87-124)
     def _refined(self, call):
         cost = C.c_double(0.0)
@@ -803,6 +872,37 @@ def conditional_dijkstra(xy, belief_row, beliefs, types, children, parents, fina
     if rc < 0:
         raise RuntimeError("porrt_conditional_dijkstra failed (%d)" % rc)
     return dist
+
+
+def extract_policies_explicit(xy, belief_row, beliefs, belief_ids, children, dist, starts, policy_max_nodes=0, device=0):
+    """porrt_extract_policies: extract_policy (belief_graph.rs:184-267) from every node of starts on an explicit graph, on the GPU.
+    children: per-node lists in add_edge order (or a CSR pair (off, ids)); belief_row[i] = row of `beliefs` node i carries, belief_ids[i]
+    its clustering key, dist[i] its expected cost.  Returns (list of ((oid, par, leaf), cost) or None per query, status array)."""
+    L = load_library()
+    n = len(dist)
+    if isinstance(children, tuple):
+        coff, cid = np.ascontiguousarray(children[0], dtype=np.uint64), np.ascontiguousarray(np.append(children[1], 0), dtype=np.uint32)
+    else:
+        coff = np.zeros(n + 1, dtype=np.uint64)
+        coff[1:] = np.cumsum([len(x) for x in children])
+        cid = np.array([v for x in children for v in x] + [0], dtype=np.uint32)
+    beliefs = np.ascontiguousarray(beliefs, dtype=np.float64)
+    st = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+    nq = len(st)
+    off, status, cost = np.zeros(nq + 1, dtype=np.uint64), np.zeros(max(nq, 1), dtype=np.uint8), np.zeros(max(nq, 1))
+    args = (device, n, np.ascontiguousarray(xy, dtype=np.float64).reshape(-1), np.ascontiguousarray(belief_row, dtype=np.uint32), beliefs,
+            beliefs.shape[0], beliefs.shape[1], np.ascontiguousarray(belief_ids, dtype=np.uint32), coff, cid,
+            np.ascontiguousarray(dist, dtype=np.float64), st if nq else np.zeros(1, dtype=np.uint64), nq, int(policy_max_nodes), off, status, cost)
+    total = int(L.porrt_extract_policies(*args, None, None, None, 0))
+    if total < 0:
+        raise RuntimeError("porrt_extract_policies failed (%d)" % total)
+    oid, par, leaf = np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
+    if total:
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = int(L.porrt_extract_policies(*args, p(oid), p(par), p(leaf), total))
+        if rc != total:
+            raise RuntimeError("porrt_extract_policies failed (%d)" % rc)
+    return _policy_list(off, status[:nq], cost[:nq], oid, par, leaf), status[:nq]
 
 
 def qmdp_costs_explicit(xy, node_validity, validities, children, finals, device=0):
