@@ -21,6 +21,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
+#include <vector>
+#include "../../include/porrt_hip.h"
 
 namespace porrt {
 
@@ -37,6 +40,33 @@ struct ScopedEvents {
     ScopedEvents(const ScopedEvents &) = delete;
     ScopedEvents &operator=(const ScopedEvents &) = delete;
 };
+
+// Monotone relaxation sweeps until one changes nothing: the host loop of PRM::plan_path's rows (porrt_prm.hpp) and of the QMDP
+// planes (porrt_qmdp.hpp).  A sweep kernel stores 1 to flags[8 * row + k] when sweep k of a group of eight lowered a cost of that
+// row; eight sweeps run between two looks at the flags, and a row whose eighth sweep changed nothing has no dirty node left.
+// launch(k, cur) enqueues sweep k, which reads dirty buffer cur and marks cur ^ 1 (`cur` comes in as the buffer the first sweep
+// reads).  going_on(rows) is told, in ascending order, the rows whose eighth sweep still changed something, before the next eight.
+// `sweeps` comes back as the number of sweeps launched; errors are texts beginning with `who`.
+template <class Launch, class GoingOn>
+static int sweep_to_fixpoint(hipStream_t stream, uint32_t *flags, size_t rows, int cur, Launch &&launch, GoingOn &&going_on, const char *who,
+                             uint64_t &sweeps, std::string &err) {
+    std::vector<uint32_t> h_flags(8 * rows), changed;
+    hipError_t e;
+    for (sweeps = 0;;) {
+        if ((e = hipMemsetAsync(flags, 0, h_flags.size() * sizeof(uint32_t), stream)) != hipSuccess) break;
+        for (uint32_t k = 0; k < 8; ++k, cur ^= 1) launch(k, cur);
+        if ((e = hipMemcpyAsync(h_flags.data(), flags, h_flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) break;
+        sweeps += 8;
+        changed.clear();
+        for (size_t r = 0; r < rows; ++r) if (h_flags[8 * r + 7]) changed.push_back((uint32_t)r);
+        if (changed.empty()) return PORRT_OK;                        // a sweep that changes nothing marks nothing
+        if (sweeps > 16u * 1000u * 1000u) { err = std::string(who) + ": no fixpoint"; return PORRT_ERR_DEVICE; }
+        if ((e = going_on(changed)) != hipSuccess) break;
+    }
+    err = std::string(who) + ": sweeps: " + hipGetErrorString(e);
+    return PORRT_ERR_DEVICE;
+}
 
 constexpr int kConnectWaves = 4;     // samples per connect workgroup (one wave each)
 constexpr uint32_t kTileRMax = 31;             // LDS tile half-width limit (pixels); above it rays read global
@@ -360,6 +390,17 @@ __device__ __forceinline__ double dist2(double ax, double ay, double bx, double 
     double dx = bx - ax, dy = by - ay;
     double xx = dx * dx, yy = dy * dy;
     return xx + yy;
+}
+
+// The butterfly over a wave's per-lane candidates (value, position in a list the lanes stride): every lane ends with the least
+// value and, among equal values, the lowest position -- the first minimum of the whole list.  pos = 0xFFFFFFFF: no candidate.
+__device__ __forceinline__ void wave_first_min(double &value, uint32_t &pos) {
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    for (uint32_t s = 32; s >= 1; s >>= 1) {
+        const double oc = __shfl_xor(value, (int)s);
+        const uint32_t op = (uint32_t)__shfl_xor((int)pos, (int)s);
+        if (op != kNone && (pos == kNone || oc < value || (oc == value && op < pos))) { value = oc; pos = op; }
+    }
 }
 
 // line_drawing 0.8 octant transforms (Bresenham<i32>, used at map_shelves_io.rs:196 / map_io.rs:225)

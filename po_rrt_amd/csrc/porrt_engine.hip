@@ -169,6 +169,28 @@ struct GrowScratch {
         return hipSuccess;
     }
     void free_all() { for (auto &sl : slots) if (sl.first) (void)hipFree(sl.first); slots.clear(); }
+    GrowScratch() = default;
+    GrowScratch(const GrowScratch &) = delete;
+    GrowScratch &operator=(const GrowScratch &) = delete;
+    ~GrowScratch() { free_all(); }                                   // (a context frees its slots in porrt_destroy, with its device current)
+};
+
+// The device copies of one call's host arrays (the entry points that take an explicit graph): up() allocates n elements (at least
+// 8 bytes), fills them from src when there is one, and returns nullptr on a device error; the destructor frees every buffer,
+// whichever way the call ends.
+struct DeviceUploads {
+    std::vector<void *> owned;
+    template <class T> T *up(const void *src, size_t n) {
+        void *d = nullptr;
+        if (hipMalloc(&d, std::max<size_t>(n * sizeof(T), 8)) != hipSuccess) return nullptr;
+        owned.push_back(d);
+        if (n && src && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return (T *)d;
+    }
+    DeviceUploads() { owned.reserve(16); }                          // (more than any caller uploads: recording a buffer does not allocate)
+    DeviceUploads(const DeviceUploads &) = delete;
+    DeviceUploads &operator=(const DeviceUploads &) = delete;
+    ~DeviceUploads() { for (void *d : owned) (void)hipFree(d); }
 };
 
 #include "porrt_mmplan.hpp"
@@ -395,10 +417,11 @@ struct porrt_ctx {
                    RefineOut &out);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
-    GrowScratch prm_paths_scratch;         //   its device buffers (rows of costs, dirty flags, queries), kept across calls
+    GrowScratch prm_paths_scratch;         // plan_path, one pair or many: device buffers (rows of costs, dirty flags, queries), kept across calls
     uint32_t opt_prm_rows = 256;           // "prm_rows": rows (distinct goal nodes) swept together in one pass
     uint32_t opt_prm_xcd_rows = 1;         // "prm_xcd_rows": a row's sweep workgroups on one XCD (k_prm_rows_sweep)
     int ensure_prm_weights();
+    int prm_answer(const double *starts, const double *goals, uint64_t n, PrmPathsResult &res, const char *who, bool single);
     int64_t prm_plan_paths(const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap);
     QmdpState qmdp;                        // porrt_qmdp_plan: the per-world costs-to-goal of the last PTO graph (device, porrt_qmdp.hpp)
     GrowScratch qmdp_scratch;              //   slots 0-4: the plan's buffers, 5-: a react call's
@@ -2666,72 +2689,16 @@ int64_t porrt_ctx::mm_extract_policies(const uint64_t *starts, uint64_t n, uint6
     return policies_copy_out(mm_policies, pol_off, status, expected_costs, original_ids, parents, is_leaf, xy, cap);
 }
 
+// PRM::plan_path (prm.rs:111-123) for one pair: a batch of one (prm_answer) into a result of its own -- the context's prm_paths, the
+// last BATCHED call's answers, is not touched.  Returns the number of states always and writes at most cap of them.
 int64_t porrt_ctx::prm_plan_path(const double start[2], const double goal[2], double *path_xy, uint64_t cap) {
     if (!have_results || mode != PORRT_MODE_PRM) { set_err("plan_path: grow a roadmap first (porrt_grow_prm)"); return PORRT_ERR_INVALID; }
     if (!start || !goal) { set_err("plan_path: start and goal"); return PORRT_ERR_INVALID; }
-    HIPCHK(hipSetDevice(device));
-    int r = download(DL_TREE);
+    PrmPathsResult res;
+    const int r = prm_answer(start, goal, 1, res, "plan_path", true);
     if (r) return r;
-    if ((r = ensure_edge_order())) return r;                        // PTOGraph::parents in push order, on the device
-    const size_t N = n_nodes;
-    const HostKd *kd = host_kd_of(this);
-    const size_t kd_start = kd->nearest(start[0], start[1]), kd_goal = kd->nearest(goal[0], goal[1]);
-    if ((r = ensure_prm_weights())) return r;
-    if (prm.dist_cap < N) {
-        void *drop[] = {prm.d_dist, prm.d_dirty[0], prm.d_dirty[1]};
-        for (void *q : drop) if (q) (void)hipFree(q);
-        prm.d_dist = nullptr; prm.d_dirty[0] = prm.d_dirty[1] = nullptr; prm.dist_cap = 0;
-        HIPCHK(hipMalloc((void **)&prm.d_dist, (N + N / 8 + 1) * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&prm.d_dirty[0], N + N / 8 + 1));
-        HIPCHK(hipMalloc((void **)&prm.d_dirty[1], N + N / 8 + 1));
-        prm.dist_cap = N + N / 8 + 1;
-    }
-    if (!prm.d_flags) HIPCHK(hipMalloc((void **)&prm.d_flags, 8 * sizeof(uint32_t)));
-    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    // dijkstra from the goal's node (pto_graph.rs:275-303): sweeps until nothing changes, eight between two looks
-    HIPCHK(hipMemsetAsync(prm.d_dirty[0], 0, N, stream));
-    HIPCHK(hipMemsetAsync(prm.d_dirty[1], 0, N, stream));
-    hipLaunchKernelGGL(k_prm_sssp_init, grid, block, 0, stream, (uint32_t)N, (uint32_t)kd_goal, (const unsigned long long *)eo.d_adj_off,
-                       (const uint32_t *)eo.d_adj_id, prm.d_dist, prm.d_dirty[0], prm.d_dirty[1]);
-    int cur = 1;                                                    // the init marked the goal's neighbours in buffer 1
-    uint32_t h_flags[8];
-    for (uint64_t sweeps = 0;; sweeps += 8) {
-        HIPCHK(hipMemsetAsync(prm.d_flags, 0, sizeof h_flags, stream));
-        for (uint32_t k = 0; k < 8; ++k, cur ^= 1)
-            hipLaunchKernelGGL(k_prm_sssp_sweep, grid, block, 0, stream, (uint32_t)N, (const unsigned long long *)eo.d_adj_off, (const uint32_t *)eo.d_adj_id,
-                               (const double *)prm.d_w, prm.d_dist, prm.d_dirty[cur], prm.d_dirty[cur ^ 1], prm.d_flags, k);
-        HIPCHK(hipMemcpyAsync(h_flags, prm.d_flags, sizeof h_flags, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (!h_flags[7]) break;
-        if (sweeps > 16u * 1000u * 1000u) { set_err("plan_path: no fixpoint"); return PORRT_ERR_DEVICE; }
-    }
-    std::vector<double> dist(N);
-    HIPCHK(hipMemcpy(dist.data(), prm.d_dist, N * sizeof(double), hipMemcpyDeviceToHost));
-    if (std::isinf(dist[kd_start])) return 0;                       // prm.rs:117-119: an empty path
-    // extract_path (pto_graph.rs:305-326): from the start always to the first parent of least cost-to-goal + edge; the
-    // parents lists of the few path nodes are read from the device adjacency
-    uint64_t n_path = 0;
-    size_t node = kd_start;
-    std::vector<uint32_t> par;
-    for (size_t guard = 0;; ++guard) {
-        if (n_path < cap && path_xy) { path_xy[2 * n_path] = h_nx[node]; path_xy[2 * n_path + 1] = h_ny[node]; }
-        ++n_path;
-        if (dist[node] == 0.0) break;
-        if (guard > N) { set_err("plan_path: zero-length cycle (the reference would not terminate)"); return PORRT_ERR_INVALID; }
-        unsigned long long off[2];
-        HIPCHK(hipMemcpy(off, eo.d_adj_off + node, sizeof off, hipMemcpyDeviceToHost));
-        par.resize(off[1] - off[0]);
-        if (!par.empty()) HIPCHK(hipMemcpy(par.data(), eo.d_adj_id + off[0], par.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        size_t best = 0;
-        double best_cost = 0.0;
-        bool have = false;
-        for (uint32_t p2 : par) {                                   // min_by: the first minimum over the parents list
-            const double cost = dist[p2] + HostKd::norm2(h_nx[p2], h_ny[p2], h_nx[node], h_ny[node]);
-            if (!have || cost < best_cost) { best = p2; best_cost = cost; have = true; }
-        }
-        if (!have) { set_err("plan_path: node without parents"); return PORRT_ERR_INVALID; }
-        node = best;
-    }
+    const uint64_t n_path = res.off[1];                             // 0: the start's cost is +inf (prm.rs:117-119: an empty path)
+    if (path_xy && n_path && cap) memcpy(path_xy, res.xy.data(), 2 * std::min(n_path, cap) * sizeof(double));
     return (int64_t)n_path;
 }
 
@@ -2753,9 +2720,163 @@ int porrt_ctx::ensure_prm_weights() {
     return PORRT_OK;
 }
 
-// PRM::plan_path for n start/goal pairs (porrt_prm_plan_paths): the nearest nodes on the host (the literal kd traversal, as plan_path),
-// one row of costs per distinct goal node, the rows swept together in passes (k_prm_rows_init / k_prm_rows_sweep, porrt_prm.hpp), the
-// paths walked on the device (k_prm_walk: a count pass, the offsets, a write pass).  Only the lengths and the states are downloaded.
+// PRM::plan_path for n start/goal pairs, n >= 0, on the roadmap of the last growth (the callers have checked that there is one): the
+// nearest nodes on the host (the literal kd traversal), one row of costs per distinct goal node, the rows swept together in passes
+// (k_prm_rows_init / k_prm_rows_sweep, porrt_prm.hpp), the paths walked on the device (k_prm_walk: a count pass, the offsets, a write
+// pass).  Only the lengths and the states are downloaded.  Fills res.off, res.xy and res.info but ms_wall; error texts begin with
+// `who`; `single` (porrt_prm_plan_path's one pair) leaves the query's number out of them and launches the plain grid.
+int porrt_ctx::prm_answer(const double *starts, const double *goals, uint64_t n, PrmPathsResult &res, const char *who, bool single) {
+    res.info = {};
+    res.info.queries = n;
+    res.off.assign(n + 1, 0);
+    res.xy.clear();
+    if (!n) return PORRT_OK;
+    int r;
+    HIPCHK(hipSetDevice(device));
+    if ((r = download(DL_TREE))) return r;
+    if ((r = ensure_edge_order())) return r;                    // PTOGraph::parents in push order, on the device
+    if ((r = ensure_prm_weights())) return r;
+    const size_t N = n_nodes;
+    // the nearest nodes of starts and goals; a row per distinct goal node, in the order of first use
+    const double tn = now_s();
+    const HostKd *kd = host_kd_of(this);
+    std::vector<uint32_t> q_start(n), q_row(n), row_goal;
+    std::unordered_map<uint32_t, uint32_t> row_of_goal;
+    for (uint64_t q = 0; q < n; ++q) {
+        q_start[q] = (uint32_t)kd->nearest(starts[2 * q], starts[2 * q + 1]);
+        const auto it = row_of_goal.emplace((uint32_t)kd->nearest(goals[2 * q], goals[2 * q + 1]), (uint32_t)row_goal.size());
+        if (it.second) row_goal.push_back(it.first->first);
+        q_row[q] = it.first->second;
+    }
+    res.info.ms_nearest = 1e3 * (now_s() - tn);
+    const size_t R = row_goal.size();
+    res.info.rows = R;
+    // queries grouped by row (a pass walks the queries of its rows)
+    std::vector<uint64_t> row_first(R + 1, 0);
+    for (uint64_t q = 0; q < n; ++q) ++row_first[q_row[q] + 1];
+    for (size_t k = 0; k < R; ++k) row_first[k + 1] += row_first[k];
+    std::vector<uint32_t> order(n);
+    {
+        std::vector<uint64_t> at(row_first.begin(), row_first.end() - 1);
+        for (uint64_t q = 0; q < n; ++q) order[at[q_row[q]]++] = (uint32_t)q;
+    }
+    // rows per pass: the option, and the costs + dirty bytes of a pass within the budget and half the free device memory
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = kPrmPathsBudget; }
+    const size_t per_row = 10 * N + 64;
+    const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)opt_prm_rows, R, std::min(kPrmPathsBudget, free_b / 2) / per_row}));
+    auto at_query = [&](uint32_t q) { return std::string(who) + ": " + (single ? std::string() : "query " + std::to_string(q) + ": "); };
+    auto no_room = [&](const char *what) {
+        (void)hipGetLastError();
+        set_err(std::string(who) + ": cannot allocate " + what);
+        return (int)PORRT_ERR_CAPACITY;
+    };
+    GrowScratch &sc = prm_paths_scratch;
+    double *d_dist = nullptr, *d_out = nullptr;
+    uint8_t *d_dirty = nullptr;
+    uint32_t *d_flags = nullptr, *d_act = nullptr, *d_goal = nullptr, *d_qs = nullptr, *d_qr = nullptr, *d_len = nullptr;
+    unsigned long long *d_off = nullptr;
+    if (sc.get(0, d_dist, P * N) != hipSuccess) return no_room("the rows' costs");
+    if (sc.get(1, d_dirty, 2 * P * N) != hipSuccess) return no_room("the rows' dirty flags");
+    if (sc.get(2, d_flags, 8 * P) != hipSuccess || sc.get(3, d_act, P) != hipSuccess || sc.get(4, d_goal, P) != hipSuccess ||
+        sc.get(5, d_qs, n) != hipSuccess || sc.get(6, d_qr, n) != hipSuccess || sc.get(7, d_len, n) != hipSuccess || sc.get(8, d_off, n) != hipSuccess)
+        return no_room("the query arrays");
+    uint8_t *d_dirty_ab[2] = {d_dirty, d_dirty + P * N};
+    const unsigned long long *adj_off = eo.d_adj_off;
+    const uint32_t *adj_id = eo.d_adj_id;
+    const uint32_t nbx = (uint32_t)((N + 255) / 256);
+    std::vector<uint32_t> act, h_qs, h_qr, h_len;
+    std::vector<unsigned long long> h_off;
+    std::vector<uint32_t> lens(n, 0);
+    std::vector<uint64_t> src(n, 0);                            // where query q's states start in `staged`
+    std::vector<double> staged;
+    ScopedEvents<2> evs;
+    HIPCHK(evs.create());
+    double dev_ms = 0;
+    for (size_t r0 = 0; r0 < R; r0 += P) {
+        const size_t pr = std::min(P, R - r0);
+        ++res.info.passes;
+        HIPCHK(hipEventRecord(evs.e[0], stream));
+        HIPCHK(hipMemcpyAsync(d_goal, row_goal.data() + r0, pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_dirty_ab[0], 0, pr * N, stream));
+        HIPCHK(hipMemsetAsync(d_dirty_ab[1], 0, pr * N, stream));
+        hipLaunchKernelGGL(k_prm_rows_init, dim3(nbx, (unsigned)pr), dim3(256), 0, stream, (uint32_t)N, (const uint32_t *)d_goal, adj_off, adj_id,
+                           d_dist, d_dirty_ab[1]);
+        act.resize(pr);
+        for (size_t k = 0; k < pr; ++k) act[k] = (uint32_t)k;
+        HIPCHK(hipMemcpyAsync(d_act, act.data(), pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        // dijkstra from every row's goal (pto_graph.rs:275-303): sweeps, eight between two looks at all rows' flags; a row whose
+        // eighth sweep changed nothing has reached its fixpoint (no dirty node is left) and drops out of the later launches
+        const uint32_t swz = single ? 0u : opt_prm_xcd_rows;        // the single call's one row has nothing to place: the plain grid
+        uint64_t sweeps = 0;
+        std::string e;
+        r = sweep_to_fixpoint(stream, d_flags, pr, 1 /* the init marked the goals' neighbours in buffer 1 */,
+            [&](uint32_t k, int cur) {
+                const uint32_t nact = (uint32_t)act.size();
+                hipLaunchKernelGGL(k_prm_rows_sweep, dim3(nbx * nact), dim3(256), 0, stream, (uint32_t)N, nbx, nact, swz, (const uint32_t *)d_act,
+                                   adj_off, adj_id, (const double *)prm.d_w, d_dist, d_dirty_ab[cur], d_dirty_ab[cur ^ 1], d_flags, k);
+            },
+            [&](const std::vector<uint32_t> &going_on) {        // (the copy reads `act`; it is written again only after the next sync)
+                const bool fewer = going_on.size() != act.size();
+                act = going_on;
+                return fewer ? hipMemcpyAsync(d_act, act.data(), act.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) : hipSuccess;
+            },
+            who, sweeps, e);
+        res.info.sweeps += sweeps;
+        if (r) { set_err(e); return r; }
+        // extract_path (pto_graph.rs:305-326) for the queries of these rows: count, offsets, write
+        const uint64_t q0 = row_first[r0], q1 = row_first[r0 + pr];
+        const uint32_t nq = (uint32_t)(q1 - q0);
+        h_qs.resize(nq); h_qr.resize(nq); h_len.resize(nq); h_off.resize(nq);
+        for (uint32_t k = 0; k < nq; ++k) { const uint32_t q = order[q0 + k]; h_qs[k] = q_start[q]; h_qr[k] = q_row[q] - (uint32_t)r0; }
+        HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_qr, h_qr.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        const dim3 wgrid((nq + 3) / 4);
+        hipLaunchKernelGGL(k_prm_walk<false>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
+                           (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)nullptr, (double *)nullptr);
+        HIPCHK(hipMemcpyAsync(h_len.data(), d_len, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        unsigned long long tot = 0;
+        for (uint32_t k = 0; k < nq; ++k) {
+            const uint32_t q = order[q0 + k];
+            if (h_len[k] == kPrmWalkCycle) {
+                set_err(at_query(q) + "zero-length cycle (the reference would not terminate)");
+                return PORRT_ERR_INVALID;
+            }
+            if (h_len[k] == kPrmWalkOrphan) { set_err(at_query(q) + "node without parents"); return PORRT_ERR_INVALID; }
+            h_off[k] = tot;
+            lens[q] = h_len[k];
+            src[q] = staged.size() / 2 + tot;
+            tot += h_len[k];
+        }
+        if (tot) {
+            if (sc.get(9, d_out, 2 * tot) != hipSuccess) return no_room("the paths");
+            HIPCHK(hipMemcpyAsync(d_off, h_off.data(), nq * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(k_prm_walk<true>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
+                               (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)d_off, d_out);
+            const size_t s0 = staged.size();
+            staged.resize(s0 + 2 * tot);
+            HIPCHK(hipMemcpyAsync(staged.data() + s0, d_out, 2 * tot * sizeof(double), hipMemcpyDeviceToHost, stream));
+        }
+        HIPCHK(hipEventRecord(evs.e[1], stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        dev_ms += ms;
+    }
+    res.info.ms_device = dev_ms;
+    // the answers in query order
+    uint64_t total = 0;
+    for (uint64_t q = 0; q < n; ++q) { res.off[q] = total; total += lens[q]; }
+    res.off[n] = total;
+    res.xy.resize(2 * total);
+    for (uint64_t q = 0; q < n; ++q)
+        if (lens[q]) memcpy(res.xy.data() + 2 * res.off[q], staged.data() + 2 * src[q], 2 * (size_t)lens[q] * sizeof(double));
+    return PORRT_OK;
+}
+
+// porrt_prm_plan_paths: the answers of prm_answer kept on the context (porrt_prm_get_paths, porrt_prm_paths_info) and copied out
 int64_t porrt_ctx::prm_plan_paths(const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap) {
     PrmPathsResult &res = prm_paths;
     res.valid = false;
@@ -2763,154 +2884,8 @@ int64_t porrt_ctx::prm_plan_paths(const double *starts, const double *goals, uin
     if (!path_off || (n && (!starts || !goals))) { set_err("plan_paths: starts, goals and path_off"); return PORRT_ERR_INVALID; }
     if (n >= (1ull << 31)) { set_err("plan_paths: fewer than 2^31 queries"); return PORRT_ERR_INVALID; }
     const double t0 = now_s();
-    res.info = {};
-    res.info.queries = n;
-    res.off.assign(n + 1, 0);
-    res.xy.clear();
-    int r;
-    if (n) {
-        HIPCHK(hipSetDevice(device));
-        if ((r = download(DL_TREE))) return r;
-        if ((r = ensure_edge_order())) return r;                    // PTOGraph::parents in push order, on the device
-        if ((r = ensure_prm_weights())) return r;
-        const size_t N = n_nodes;
-        // the nearest nodes of starts and goals; a row per distinct goal node, in the order of first use
-        const double tn = now_s();
-        const HostKd *kd = host_kd_of(this);
-        std::vector<uint32_t> q_start(n), q_row(n), row_goal;
-        std::unordered_map<uint32_t, uint32_t> row_of_goal;
-        for (uint64_t q = 0; q < n; ++q) {
-            q_start[q] = (uint32_t)kd->nearest(starts[2 * q], starts[2 * q + 1]);
-            const auto it = row_of_goal.emplace((uint32_t)kd->nearest(goals[2 * q], goals[2 * q + 1]), (uint32_t)row_goal.size());
-            if (it.second) row_goal.push_back(it.first->first);
-            q_row[q] = it.first->second;
-        }
-        res.info.ms_nearest = 1e3 * (now_s() - tn);
-        const size_t R = row_goal.size();
-        res.info.rows = R;
-        // queries grouped by row (a pass walks the queries of its rows)
-        std::vector<uint64_t> row_first(R + 1, 0);
-        for (uint64_t q = 0; q < n; ++q) ++row_first[q_row[q] + 1];
-        for (size_t k = 0; k < R; ++k) row_first[k + 1] += row_first[k];
-        std::vector<uint32_t> order(n);
-        {
-            std::vector<uint64_t> at(row_first.begin(), row_first.end() - 1);
-            for (uint64_t q = 0; q < n; ++q) order[at[q_row[q]]++] = (uint32_t)q;
-        }
-        // rows per pass: the option, and the costs + dirty bytes of a pass within the budget and half the free device memory
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = kPrmPathsBudget; }
-        const size_t per_row = 10 * N + 64;
-        const size_t P = std::max<size_t>(1, std::min<size_t>({(size_t)opt_prm_rows, R, std::min(kPrmPathsBudget, free_b / 2) / per_row}));
-        auto no_room = [&](const char *what) {
-            (void)hipGetLastError();
-            set_err(std::string("plan_paths: cannot allocate ") + what);
-            return (int64_t)PORRT_ERR_CAPACITY;
-        };
-        GrowScratch &sc = prm_paths_scratch;
-        double *d_dist = nullptr, *d_out = nullptr;
-        uint8_t *d_dirty = nullptr;
-        uint32_t *d_flags = nullptr, *d_act = nullptr, *d_goal = nullptr, *d_qs = nullptr, *d_qr = nullptr, *d_len = nullptr;
-        unsigned long long *d_off = nullptr;
-        if (sc.get(0, d_dist, P * N) != hipSuccess) return no_room("the rows' costs");
-        if (sc.get(1, d_dirty, 2 * P * N) != hipSuccess) return no_room("the rows' dirty flags");
-        if (sc.get(2, d_flags, 8 * P) != hipSuccess || sc.get(3, d_act, P) != hipSuccess || sc.get(4, d_goal, P) != hipSuccess ||
-            sc.get(5, d_qs, n) != hipSuccess || sc.get(6, d_qr, n) != hipSuccess || sc.get(7, d_len, n) != hipSuccess || sc.get(8, d_off, n) != hipSuccess)
-            return no_room("the query arrays");
-        uint8_t *d_dirty_ab[2] = {d_dirty, d_dirty + P * N};
-        const unsigned long long *adj_off = eo.d_adj_off;
-        const uint32_t *adj_id = eo.d_adj_id;
-        const uint32_t nbx = (uint32_t)((N + 255) / 256);
-        std::vector<uint32_t> h_flags(8 * P), act, next, h_qs, h_qr, h_len;
-        std::vector<unsigned long long> h_off;
-        std::vector<uint32_t> lens(n, 0);
-        std::vector<uint64_t> src(n, 0);                            // where query q's states start in `staged`
-        std::vector<double> staged;
-        ScopedEvents<2> evs;
-        HIPCHK(evs.create());
-        double dev_ms = 0;
-        for (size_t r0 = 0; r0 < R; r0 += P) {
-            const size_t pr = std::min(P, R - r0);
-            ++res.info.passes;
-            HIPCHK(hipEventRecord(evs.e[0], stream));
-            HIPCHK(hipMemcpyAsync(d_goal, row_goal.data() + r0, pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemsetAsync(d_dirty_ab[0], 0, pr * N, stream));
-            HIPCHK(hipMemsetAsync(d_dirty_ab[1], 0, pr * N, stream));
-            hipLaunchKernelGGL(k_prm_rows_init, dim3(nbx, (unsigned)pr), dim3(256), 0, stream, (uint32_t)N, (const uint32_t *)d_goal, adj_off, adj_id,
-                               d_dist, d_dirty_ab[1]);
-            act.resize(pr);
-            for (size_t k = 0; k < pr; ++k) act[k] = (uint32_t)k;
-            HIPCHK(hipMemcpyAsync(d_act, act.data(), pr * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            // dijkstra from every row's goal (pto_graph.rs:275-303): sweeps, eight between two looks at all rows' flags; a row whose
-            // eighth sweep changed nothing has reached its fixpoint (no dirty node is left) and drops out of the later launches
-            int cur = 1;                                            // the init marked the goals' neighbours in buffer 1
-            for (uint64_t sweeps = 0;; sweeps += 8) {
-                const uint32_t nact = (uint32_t)act.size();
-                HIPCHK(hipMemsetAsync(d_flags, 0, 8 * pr * sizeof(uint32_t), stream));
-                for (uint32_t k = 0; k < 8; ++k, cur ^= 1)
-                    hipLaunchKernelGGL(k_prm_rows_sweep, dim3(nbx * nact), dim3(256), 0, stream, (uint32_t)N, nbx, nact, opt_prm_xcd_rows,
-                                       (const uint32_t *)d_act, adj_off, adj_id, (const double *)prm.d_w, d_dist, d_dirty_ab[cur], d_dirty_ab[cur ^ 1],
-                                       d_flags, k);
-                HIPCHK(hipMemcpyAsync(h_flags.data(), d_flags, 8 * pr * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                res.info.sweeps += 8;
-                next.clear();
-                for (uint32_t a : act) if (h_flags[8 * a + 7]) next.push_back(a);
-                if (next.empty()) break;
-                if (sweeps > 16u * 1000u * 1000u) { set_err("plan_paths: no fixpoint"); return PORRT_ERR_DEVICE; }
-                if (next.size() != act.size()) HIPCHK(hipMemcpyAsync(d_act, next.data(), next.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                act.swap(next);                                     // (the copy reads this buffer; it is written again only after the next sync)
-            }
-            // extract_path (pto_graph.rs:305-326) for the queries of these rows: count, offsets, write
-            const uint64_t q0 = row_first[r0], q1 = row_first[r0 + pr];
-            const uint32_t nq = (uint32_t)(q1 - q0);
-            h_qs.resize(nq); h_qr.resize(nq); h_len.resize(nq); h_off.resize(nq);
-            for (uint32_t k = 0; k < nq; ++k) { const uint32_t q = order[q0 + k]; h_qs[k] = q_start[q]; h_qr[k] = q_row[q] - (uint32_t)r0; }
-            HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(d_qr, h_qr.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            const dim3 wgrid((nq + 3) / 4);
-            hipLaunchKernelGGL(k_prm_walk<false>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
-                               (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)nullptr, (double *)nullptr);
-            HIPCHK(hipMemcpyAsync(h_len.data(), d_len, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            unsigned long long tot = 0;
-            for (uint32_t k = 0; k < nq; ++k) {
-                const uint32_t q = order[q0 + k];
-                if (h_len[k] == kPrmWalkCycle) {
-                    set_err("plan_paths: query " + std::to_string(q) + ": zero-length cycle (the reference would not terminate)");
-                    return PORRT_ERR_INVALID;
-                }
-                if (h_len[k] == kPrmWalkOrphan) { set_err("plan_paths: query " + std::to_string(q) + ": node without parents"); return PORRT_ERR_INVALID; }
-                h_off[k] = tot;
-                lens[q] = h_len[k];
-                src[q] = staged.size() / 2 + tot;
-                tot += h_len[k];
-            }
-            if (tot) {
-                if (sc.get(9, d_out, 2 * tot) != hipSuccess) return no_room("the paths");
-                HIPCHK(hipMemcpyAsync(d_off, h_off.data(), nq * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(k_prm_walk<true>, wgrid, dim3(256), 0, stream, (uint32_t)N, nq, (const uint32_t *)d_qs, (const uint32_t *)d_qr, adj_off, adj_id,
-                                   (const double *)d_nx.p, (const double *)d_ny.p, (const double *)d_dist, d_len, (const unsigned long long *)d_off, d_out);
-                const size_t s0 = staged.size();
-                staged.resize(s0 + 2 * tot);
-                HIPCHK(hipMemcpyAsync(staged.data() + s0, d_out, 2 * tot * sizeof(double), hipMemcpyDeviceToHost, stream));
-            }
-            HIPCHK(hipEventRecord(evs.e[1], stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipGetLastError());
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-            dev_ms += ms;
-        }
-        res.info.ms_device = dev_ms;
-        // the answers in query order
-        uint64_t total = 0;
-        for (uint64_t q = 0; q < n; ++q) { res.off[q] = total; total += lens[q]; }
-        res.off[n] = total;
-        res.xy.resize(2 * total);
-        for (uint64_t q = 0; q < n; ++q)
-            if (lens[q]) memcpy(res.xy.data() + 2 * res.off[q], staged.data() + 2 * src[q], 2 * (size_t)lens[q] * sizeof(double));
-    }
+    const int r = prm_answer(starts, goals, n, res, "plan_paths", false);
+    if (r) return r;
     const uint64_t total = res.off[n];
     memcpy(path_off, res.off.data(), (n + 1) * sizeof(uint64_t));
     if (path_xy && total && total <= cap) memcpy(path_xy, res.xy.data(), 2 * total * sizeof(double));
@@ -4187,7 +4162,8 @@ int porrt_mm_get_seconds(const porrt_ctx *c, double *host_s, double *roadmap_s, 
 }
 
 int64_t porrt_prm_plan_path(porrt_ctx *c, const double start[2], const double goal[2], double *path_xy, uint64_t cap) {
-    return c ? c->prm_plan_path(start, goal, path_xy, cap) : PORRT_ERR_INVALID;
+    if (!c) return PORRT_ERR_INVALID;
+    try { return c->prm_plan_path(start, goal, path_xy, cap); } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 int64_t porrt_prm_plan_paths(porrt_ctx *c, const double *starts, const double *goals, uint64_t n, uint64_t *path_off, double *path_xy, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
@@ -4366,33 +4342,22 @@ int64_t porrt_extract_policies(int device, uint64_t n_nodes, const double *xy, c
         if (hipSetDevice(device) != hipSuccess) return PORRT_ERR_DEVICE;
         std::vector<double> hx(n_nodes), hy(n_nodes);
         for (uint64_t i = 0; i < n_nodes; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
-        std::vector<void *> owned;
-        auto up = [&](const void *src, size_t bytes) -> void * {
-            void *d = nullptr;
-            if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-            owned.push_back(d);
-            if (bytes && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-            return d;
-        };
+        DeviceUploads dev;
         DpConst c{};
         c.n = n_nodes; c.B = 1; c.nw = n_worlds;
-        c.nx = (const double *)up(hx.data(), n_nodes * 8); c.ny = (const double *)up(hy.data(), n_nodes * 8);
-        c.bvec = (const uint32_t *)up(belief_row, n_nodes * 4);
-        c.beliefs = (const double *)up(beliefs, (size_t)n_belief_rows * n_worlds * 8);
-        c.child_off = (const unsigned long long *)up(child_off, (n_nodes + 1) * 8);
-        c.child_id = (const uint32_t *)up(child_ids, nc * 4);
-        c.dist = (double *)up(dist, n_nodes * 8);
-        const uint32_t *d_bid = (const uint32_t *)up(belief_ids, n_nodes * 4);
-        int64_t r = PORRT_ERR_DEVICE;
+        c.nx = dev.up<double>(hx.data(), n_nodes); c.ny = dev.up<double>(hy.data(), n_nodes);
+        c.bvec = dev.up<uint32_t>(belief_row, n_nodes);
+        c.beliefs = dev.up<double>(beliefs, (size_t)n_belief_rows * n_worlds);
+        c.child_off = dev.up<unsigned long long>(child_off, n_nodes + 1);
+        c.child_id = dev.up<uint32_t>(child_ids, nc);
+        c.dist = dev.up<double>(dist, n_nodes);
+        const uint32_t *d_bid = dev.up<uint32_t>(belief_ids, n_nodes);
+        if (!(c.nx && c.ny && c.bvec && c.beliefs && c.child_off && c.child_id && c.dist && d_bid)) return PORRT_ERR_DEVICE;
         GrowScratch sc;
-        if (c.nx && c.ny && c.bvec && c.beliefs && c.child_off && c.child_id && c.dist && d_bid) {
-            PoliciesResult res;
-            std::string err;
-            r = pol_extract(sc, c, false, d_bid, starts, n, policy_max_nodes, nullptr, res, err);
-            if (r == PORRT_OK) r = policies_copy_out(res, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
-        }
-        sc.free_all();
-        for (void *d : owned) (void)hipFree(d);
+        PoliciesResult res;
+        std::string err;
+        int64_t r = pol_extract(sc, c, false, d_bid, starts, n, policy_max_nodes, nullptr, res, err);
+        if (r == PORRT_OK) r = policies_copy_out(res, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
         return r;
     } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
@@ -4595,40 +4560,32 @@ int porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const u
                                const uint64_t *parent_off, const uint32_t *parent_ids, const uint64_t *finals, uint64_t n_final, double *dist) {
     if (!n || !xy || !belief_row || !beliefs || !types || !child_off || !parent_off || !dist || (n_final && !finals) || n >= 0xFFFFFFFFull)
         return PORRT_ERR_INVALID;
-    if (hipSetDevice(device) != hipSuccess) return PORRT_ERR_DEVICE;
-    for (uint64_t i = 0; i < n; ++i) if (belief_row[i] >= n_belief_rows) return PORRT_ERR_INVALID;
-    for (uint64_t k = 0; k < n_final; ++k) if (finals[k] >= n) return PORRT_ERR_INVALID;
-    const uint64_t nc = child_off[n], np = parent_off[n];
-    for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return PORRT_ERR_INVALID;
-    for (uint64_t k = 0; k < np; ++k) if (parent_ids[k] >= n) return PORRT_ERR_INVALID;
-    std::vector<double> hx(n), hy(n);
-    for (uint64_t i = 0; i < n; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
-    std::vector<void *> owned;
-    auto up = [&](const void *src, size_t bytes) -> void * {
-        void *d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        owned.push_back(d);
-        if (bytes && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    };
-    DpConst c{};
-    c.n = n; c.B = 1; c.nw = n_worlds;
-    c.nx = (const double *)up(hx.data(), n * 8); c.ny = (const double *)up(hy.data(), n * 8);
-    c.bvec = (const uint32_t *)up(belief_row, n * 4);
-    c.beliefs = (const double *)up(beliefs, (size_t)n_belief_rows * n_worlds * 8);
-    c.types = (const uint8_t *)up(types, n);
-    c.child_off = (const unsigned long long *)up(child_off, (n + 1) * 8); c.par_off = (const unsigned long long *)up(parent_off, (n + 1) * 8);
-    c.child_id = (const uint32_t *)up(child_ids, nc * 4); c.par_id = (const uint32_t *)up(parent_ids, np * 4);
-    int r = PORRT_ERR_DEVICE;
-    if (c.nx && c.ny && c.bvec && c.beliefs && c.types && c.child_off && c.par_off && c.child_id && c.par_id) {
+    return abi_guard([&]() -> int {
+        if (hipSetDevice(device) != hipSuccess) return (int)PORRT_ERR_DEVICE;
+        for (uint64_t i = 0; i < n; ++i) if (belief_row[i] >= n_belief_rows) return (int)PORRT_ERR_INVALID;
+        for (uint64_t k = 0; k < n_final; ++k) if (finals[k] >= n) return (int)PORRT_ERR_INVALID;
+        const uint64_t nc = child_off[n], np = parent_off[n];
+        for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return (int)PORRT_ERR_INVALID;
+        for (uint64_t k = 0; k < np; ++k) if (parent_ids[k] >= n) return (int)PORRT_ERR_INVALID;
+        std::vector<double> hx(n), hy(n);
+        for (uint64_t i = 0; i < n; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
+        DeviceUploads dev;
+        DpConst c{};
+        c.n = n; c.B = 1; c.nw = n_worlds;
+        c.nx = dev.up<double>(hx.data(), n); c.ny = dev.up<double>(hy.data(), n);
+        c.bvec = dev.up<uint32_t>(belief_row, n);
+        c.beliefs = dev.up<double>(beliefs, (size_t)n_belief_rows * n_worlds);
+        c.types = dev.up<uint8_t>(types, n);
+        c.child_off = dev.up<unsigned long long>(child_off, n + 1); c.par_off = dev.up<unsigned long long>(parent_off, n + 1);
+        c.child_id = dev.up<uint32_t>(child_ids, nc); c.par_id = dev.up<uint32_t>(parent_ids, np);
+        if (!(c.nx && c.ny && c.bvec && c.beliefs && c.types && c.child_off && c.par_off && c.child_id && c.par_id)) return (int)PORRT_ERR_DEVICE;
         DpState st;
         std::string err;
         std::vector<unsigned long long> f(finals, finals + n_final);
-        r = dp_run(st, c, false, f, nullptr, err);
+        int r = dp_run(st, c, false, f, nullptr, err);
         if (r == PORRT_OK && hipMemcpy(dist, st.d_dist, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) r = PORRT_ERR_DEVICE;
-    }
-    for (void *d : owned) (void)hipFree(d);
-    return r;
+        return r;
+    });
 }
 
 // ---- QmdpPolicyExtractor (qmdp_policy_extractor.rs; porrt_qmdp.hpp)
@@ -4701,21 +4658,14 @@ int porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *n
             for (uint64_t u = 0; u < n; ++u)
                 for (uint64_t k = child_off[u]; k < child_off[u + 1]; ++k) par_id[at[child_ids[k]]++] = (uint32_t)u;
         }
-        std::vector<void *> owned;
-        auto up = [&](const void *src, size_t bytes) -> void * {
-            void *d = nullptr;
-            if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-            owned.push_back(d);
-            if (bytes && src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-            return d;
-        };
-        const double *d_x = (const double *)up(hx.data(), n * 8), *d_y = (const double *)up(hy.data(), n * 8);
-        const unsigned long long *d_coff = (const unsigned long long *)up(child_off, (n + 1) * 8), *d_poff = (const unsigned long long *)up(par_off.data(), (n + 1) * 8);
-        const uint32_t *d_cid = (const uint32_t *)up(child_ids, nc * 4), *d_pid = (const uint32_t *)up(par_id.data(), nc * 4);
-        const unsigned long long *d_zero = (const unsigned long long *)up(zero.data(), n * 8), *d_valid = (const unsigned long long *)up(valid.data(), n * 8);
-        double *d_cost = (double *)up(nullptr, (size_t)n * Wp * 8), *d_rows = (double *)up(nullptr, (size_t)n * W * 8);
-        uint8_t *d_dirty = (uint8_t *)up(nullptr, 2 * n);
-        uint32_t *d_flags = (uint32_t *)up(nullptr, 8 * 4);
+        DeviceUploads dev;
+        const double *d_x = dev.up<double>(hx.data(), n), *d_y = dev.up<double>(hy.data(), n);
+        const unsigned long long *d_coff = dev.up<unsigned long long>(child_off, n + 1), *d_poff = dev.up<unsigned long long>(par_off.data(), n + 1);
+        const uint32_t *d_cid = dev.up<uint32_t>(child_ids, nc), *d_pid = dev.up<uint32_t>(par_id.data(), nc);
+        const unsigned long long *d_zero = dev.up<unsigned long long>(zero.data(), n), *d_valid = dev.up<unsigned long long>(valid.data(), n);
+        double *d_cost = dev.up<double>(nullptr, (size_t)n * Wp), *d_rows = dev.up<double>(nullptr, (size_t)n * W);
+        uint8_t *d_dirty = dev.up<uint8_t>(nullptr, 2 * n);
+        uint32_t *d_flags = dev.up<uint32_t>(nullptr, 8);
         int r = PORRT_ERR_DEVICE;
         if (d_x && d_y && d_coff && d_poff && d_cid && d_pid && d_zero && d_valid && d_cost && d_rows && d_dirty && d_flags) {
             std::string err;
@@ -4728,7 +4678,6 @@ int porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *n
             }
         }
         (void)hipGetLastError();
-        for (void *d : owned) (void)hipFree(d);
         return r;
     });
 }

@@ -128,11 +128,7 @@ __global__ __launch_bounds__(64) void k_pol_walk(DpConst g, const uint32_t *__re
                 const double c = p * (j < kPolRowCache ? s_term[j] : load(j).term);
                 if (c < bc) { bc = c; bp = j; }                       // strictly less: the lane keeps its earliest minimum
             }
-            for (uint32_t d = 1; d < 64; d <<= 1) {                   // (cost, position): the first minimum of the row wins
-                const double oc = __shfl_xor(bc, d, 64);
-                const uint32_t op = __shfl_xor(bp, d, 64);
-                if (op != kPolNone && (bp == kPolNone || oc < bc || (oc == bc && op < bp))) { bc = oc; bp = op; }
-            }
+            wave_first_min(bc, bp);                                   // (cost, position): the first minimum of the row wins
             const uint32_t win = bp == kPolNone ? first : bp;         // nothing below +inf: best_id stays the first child
             uint32_t win_id;
             double win_dist;

@@ -222,8 +222,20 @@ __global__ __launch_bounds__(256) void k_mm_order(MmConst p) {
     }
 }
 
-// ---- PRM::plan_path: dijkstra from the goal's node (pto_graph.rs:275-303) as sweeps over the roadmap's device adjacency
-// (the same monotone relaxation as the expected costs, porrt_dp.hpp: any order ends in the same fixpoint).
+// ---- PRM::plan_path (prm.rs:111-123) for one start/goal pair or many on one roadmap (porrt_prm_plan_path, porrt_prm_plan_paths):
+// ONE relaxation kernel and ONE walk serve both -- the single query is a batch of one pair.  dijkstra from the goal's node
+// (pto_graph.rs:275-303) runs as sweeps over the roadmap's device adjacency (the same monotone relaxation as the expected costs,
+// porrt_dp.hpp), extract_path (pto_graph.rs:305-326) as k_prm_walk.
+//
+// One ROW per distinct goal node: row r holds the costs to its goal, dist[r * N + n], and its own two dirty-byte arrays (same layout,
+// r * N + n).  A sweep launch relaxes every active row at once (act[] lists them; rows that have converged are left out of later
+// launches by the host).  Each row takes min over the parents of dist[p] + w (the weights of k_prm_weights) on its own arrays, and
+// that relaxation is monotone: a node's value only ever falls, each value is dist[p] + w of some parent, and a node stays dirty
+// until it has been evaluated against its parents' current values.  So every order of evaluation, whichever rows share a launch and
+// however their workgroups interleave, ends in the same fixpoint -- the least solution of dist[n] = min_p dist[p] + w(p, n),
+// dist[goal] = 0 -- and a row's costs do not depend on which other rows were swept beside it: a pair gets the same answer alone
+// or in any batch (porrt_dp.hpp gives the same argument for the expected costs).  Any workgroup schedule is correct; the placement
+// below is for speed only.
 __global__ __launch_bounds__(256) void k_prm_weights(uint32_t N, const unsigned long long *__restrict__ adj_off, const uint32_t *__restrict__ adj_id,
                                                      const double *__restrict__ nx, const double *__restrict__ ny, double *__restrict__ w) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,48 +247,6 @@ __global__ __launch_bounds__(256) void k_prm_weights(uint32_t N, const unsigned 
     }
 }
 
-__global__ __launch_bounds__(256) void k_prm_sssp_init(uint32_t N, uint32_t goal, const unsigned long long *__restrict__ adj_off,
-                                                       const uint32_t *__restrict__ adj_id, double *__restrict__ dist, uint8_t *__restrict__ dirty_a,
-                                                       uint8_t *__restrict__ dirty_b) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    dist[n] = n == goal ? 0.0 : __builtin_huge_val();
-    if (n == goal)                                           // (both flag arrays were zeroed by the host before this launch)
-        for (unsigned long long k = adj_off[n]; k < adj_off[n + 1]; ++k) dirty_b[adj_id[k]] = 1;       // evaluated by the first sweep (which reads b)
-}
-
-__global__ __launch_bounds__(256) void k_prm_sssp_sweep(uint32_t N, const unsigned long long *__restrict__ adj_off, const uint32_t *__restrict__ adj_id,
-                                                        const double *__restrict__ w, double *__restrict__ dist, uint8_t *__restrict__ dirty_in,
-                                                        uint8_t *__restrict__ dirty_out, uint32_t *__restrict__ flags, uint32_t slot) {
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N || !as_global(dirty_in)[n]) return;
-    as_global(dirty_in)[n] = 0;
-    const double old = as_global(dist)[n];
-    if (old == 0.0) return;
-    const unsigned long long a0 = as_global(adj_off)[n], a1 = as_global(adj_off)[n + 1];
-    double best = old;
-#pragma unroll 4
-    for (unsigned long long k = a0; k < a1; ++k) {
-        const double a = as_global(dist)[as_global(adj_id)[k]] + as_global(w)[k];     // dist[v] + cost(u, v)
-        best = a < best ? a : best;
-    }
-    if (best < old) {
-        as_global(dist)[n] = best;
-        for (unsigned long long k = a0; k < a1; ++k) as_global(dirty_out)[as_global(adj_id)[k]] = 1;
-        as_global(flags)[slot] = 1;
-    }
-}
-
-// ---- PRM::plan_path for many start/goal pairs on one roadmap (porrt_prm_plan_paths).  One ROW per distinct goal node: row r holds
-// the costs to its goal, dist[r * N + n], and its own two dirty-byte arrays (same layout, r * N + n).  A sweep launch relaxes every
-// active row at once (act[] lists them; rows that have converged are left out of later launches by the host).  Each row runs
-// exactly the relaxation of k_prm_sssp_sweep on its own arrays -- min over the parents of dist[p] + w, the weights of k_prm_weights --
-// and that relaxation is monotone: a node's value only ever falls, each value is dist[p] + w of some parent, and a node stays dirty
-// until it has been evaluated against its parents' current values.  So every order of evaluation, whichever rows share a launch and
-// however their workgroups interleave, ends in the same fixpoint -- the least solution of dist[n] = min_p dist[p] + w(p, n),
-// dist[goal] = 0 -- and each row is bit-identical to the single query's costs (porrt_dp.hpp gives the same argument for the expected
-// costs).  Any workgroup schedule is correct; the placement below is for speed only.
-//
 // Placement (option "prm_xcd_rows"): the workgroups of a launch are dealt to the eight XCDs in turn, so a plain grid spreads every
 // row over all eight L2s.  With the remap, the workgroups that share an XCD label (blockIdx % 8) take consecutive (row, block)
 // numbers, so a row's blocks run on about one XCD and its costs (8 N bytes: 1.6 MB at N = 200 000) stay in that XCD's 4 MiB L2
@@ -369,11 +339,7 @@ __global__ __launch_bounds__(256) void k_prm_walk(uint32_t N, uint32_t nq, const
             const double c = as_global(D)[p] + sqrt(dist2(as_global(nx)[p], as_global(ny)[p], xn, yn));
             if (bp == kNone || c < bc) { bc = c; bp = (uint32_t)(k - a0); }
         }
-        for (uint32_t s = 32; s >= 1; s >>= 1) {
-            const double oc = __shfl_xor(bc, (int)s);
-            const uint32_t op = (uint32_t)__shfl_xor((int)bp, (int)s);
-            if (op != kNone && (bp == kNone || oc < bc || (oc == bc && op < bp))) { bc = oc; bp = op; }
-        }
+        wave_first_min(bc, bp);
         if (bp == kNone) { code = kPrmWalkOrphan; break; }
         node = as_global(adj_id)[a0 + bp];
     }
@@ -386,24 +352,22 @@ struct PrmState {
     uint32_t *d_cell_ids = nullptr, *d_err = nullptr, *d_deg = nullptr;
     size_t cells_cap = 0, ids_cap = 0;
     double t_device = 0, t_total = 0;
-    // plan_path: edge weights, costs to the goal, sweep flags
-    double *d_w = nullptr, *d_dist = nullptr;
-    uint8_t *d_dirty[2] = {nullptr, nullptr};
-    uint32_t *d_flags = nullptr;
-    size_t w_cap = 0, dist_cap = 0;
+    // plan_path: edge weights (the costs and dirty flags of a call live in the context's prm_paths_scratch)
+    double *d_w = nullptr;
+    size_t w_cap = 0;
     uint64_t w_tag = ~0ull;
     void free_device() {
-        void *all[] = {d_cell_cnt, d_cell_off, d_tot, d_edge_off, d_cell_ids, d_err, d_deg, d_w, d_dist, d_dirty[0], d_dirty[1], d_flags};
+        void *all[] = {d_cell_cnt, d_cell_off, d_tot, d_edge_off, d_cell_ids, d_err, d_deg, d_w};
         for (void *q : all) if (q) (void)hipFree(q);
         d_cell_cnt = nullptr; d_cell_off = d_tot = d_edge_off = nullptr; d_cell_ids = d_err = d_deg = nullptr;
-        d_w = d_dist = nullptr; d_dirty[0] = d_dirty[1] = nullptr; d_flags = nullptr; w_cap = dist_cap = 0; w_tag = ~0ull;
+        d_w = nullptr; w_cap = 0; w_tag = ~0ull;
         cells_cap = ids_cap = 0;
     }
     ~PrmState() { free_device(); }
 };
 
-// porrt_prm_plan_paths: the last call's answers in query order (porrt_prm_get_paths hands them out again) and its counts.  They
-// belong to the roadmap of results_tag `tag`: a new growth on the context makes them stale.
+// The answers of one plan_path call in query order and its counts.  The context keeps the last porrt_prm_plan_paths' (porrt_prm_get_paths
+// hands them out again); they belong to the roadmap of results_tag `tag`: a new growth on the context makes them stale.
 struct PrmPathsResult {
     bool valid = false;
     uint64_t tag = ~0ull;

@@ -116,16 +116,6 @@ struct QmdpWalk {
     double *out;
 };
 
-// the butterfly of a wave's per-lane candidates: the least (value, list position); a lane without a candidate holds kNone
-__device__ __forceinline__ void qmdp_wave_first_min(double &bc, uint32_t &bp) {
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
-    for (uint32_t s = 32; s >= 1; s >>= 1) {
-        const double oc = __shfl_xor(bc, (int)s);
-        const uint32_t op = (uint32_t)__shfl_xor((int)bp, (int)s);
-        if (op != kNone && (bp == kNone || oc < bc || (oc == bc && op < bp))) { bc = oc; bp = op; }
-    }
-}
-
 // get_common_path (:65-87) with get_best_expected_child (:90-108), one wave per query.  Lanes stride the children list; a lane sums
 // its child's expected cost over the worlds in order (E = 0.0; E += cost[w][child] * belief[w]: no contraction) and keeps its
 // first child with E below its best so far, which starts at +inf: a NaN (inf * 0.0) or +inf never qualifies.  The butterfly keeps
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(256) void k_qmdp_common(QmdpWalk p) {
             for (uint32_t w = 0; w < p.W; ++w) E += as_global(C)[w] * as_global(B)[w];
             if (E < bc) { bc = E; bp = (uint32_t)(k - a0); }
         }
-        qmdp_wave_first_min(bc, bp);
+        wave_first_min(bc, bp);
         const uint32_t c = bp == kNone ? 0u : as_global(p.child_id)[a0 + bp];
         acc += sqrt(dist2(xn, yn, as_global(p.nx)[c], as_global(p.ny)[c]));
         id = c;
@@ -194,41 +184,31 @@ __global__ __launch_bounds__(256) void k_qmdp_path(QmdpWalk p) {
             const double c = as_global(D)[(size_t)as_global(p.child_id)[k] * p.Wp];
             if (c < bc) { bc = c; bp = (uint32_t)(k - a0); }
         }
-        qmdp_wave_first_min(bc, bp);
+        wave_first_min(bc, bp);
         id = bp == kNone ? 0u : as_global(p.child_id)[a0 + bp];
     }
     if (!WRITE && lane == 0) p.plen[j] = over ? kQmdpWalkOver : cnt;
 }
 
-// The cost planes of a graph whose arrays are on the device: init, then sweeps until one changes nothing (eight between two looks
-// at the flags, as PRM::plan_path's).  zero / valid: one word per node.  dirty: 2 * N bytes, flags: 8 words.
+// The cost planes of a graph whose arrays are on the device: init, then sweeps until one changes nothing (sweep_to_fixpoint: eight
+// between two looks at the flags, as PRM::plan_path's; the planes are its one row).  zero / valid: one word per node.  dirty: 2 * N
+// bytes, flags: 8 words.
 static int qmdp_solve(uint32_t N, uint32_t Wp, const unsigned long long *child_off, const uint32_t *child_id, const unsigned long long *par_off,
                       const uint32_t *par_id, const double *nx, const double *ny, const unsigned long long *zero, const unsigned long long *valid,
                       double *cost, uint8_t *dirty, uint32_t *flags, hipStream_t stream, uint64_t &sweeps, std::string &err) {
-#define QMDP_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return PORRT_ERR_DEVICE; } } while (0)
     uint8_t *dirty_ab[2] = {dirty, dirty + N};
     const size_t cells = (size_t)N * Wp;
     hipLaunchKernelGGL(k_qmdp_init, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, N, Wp, zero, cost);
-    QMDP_HIP(hipMemsetAsync(dirty_ab[0], 1, N, stream));             // the first sweep evaluates every node
-    QMDP_HIP(hipMemsetAsync(dirty_ab[1], 0, N, stream));
+    hipError_t e = hipMemsetAsync(dirty_ab[0], 1, N, stream);        // the first sweep evaluates every node
+    if (e == hipSuccess) e = hipMemsetAsync(dirty_ab[1], 0, N, stream);
+    if (e != hipSuccess) { err = std::string("qmdp: dirty flags: ") + hipGetErrorString(e); return PORRT_ERR_DEVICE; }
     const dim3 grid((unsigned)(((size_t)N * kQmdpLanes + 255) / 256));
-    int cur = 0;
-    uint32_t h_flags[8];
-    sweeps = 0;
-    for (;;) {
-        QMDP_HIP(hipMemsetAsync(flags, 0, sizeof h_flags, stream));
-        for (uint32_t k = 0; k < 8; ++k, cur ^= 1)
+    return sweep_to_fixpoint(stream, flags, 1, 0,
+        [&](uint32_t k, int cur) {
             hipLaunchKernelGGL(k_qmdp_sweep, grid, dim3(256), 0, stream, N, Wp, child_off, child_id, par_off, par_id, nx, ny, valid, cost,
                                dirty_ab[cur], dirty_ab[cur ^ 1], flags, k);
-        QMDP_HIP(hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, stream));
-        QMDP_HIP(hipStreamSynchronize(stream));
-        QMDP_HIP(hipGetLastError());
-        sweeps += 8;
-        if (!h_flags[7]) break;                                      // a sweep that changes nothing marks nothing: no dirty node is left
-        if (sweeps > 16u * 1000u * 1000u) { err = "qmdp: no fixpoint"; return PORRT_ERR_DEVICE; }
-    }
-#undef QMDP_HIP
-    return PORRT_OK;
+        },
+        [](const std::vector<uint32_t> &) { return hipSuccess; }, "qmdp", sweeps, err);
 }
 
 // porrt_qmdp_plan's result on a context: the planes stay on the device for porrt_qmdp_react; they belong to the graph of

@@ -77,3 +77,25 @@ def test_null_context_is_an_error_not_a_crash(lib):
     assert lib.porrt_conditional_dijkstra(0, 0, one, np.zeros(1, dtype=np.uint32), np.ones((1, 1)), 1, 1, np.ones(1, dtype=np.uint8),
                                           np.zeros(2, dtype=np.uint64), np.zeros(1, dtype=np.uint32), np.zeros(2, dtype=np.uint64),
                                           np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64), 0, np.zeros(1)) < 0      # n = 0
+
+
+def test_conditional_dijkstra_rejects_bad_arguments_before_the_device(lib):
+    """porrt_conditional_dijkstra with n = 0 or a NULL array is PORRT_ERR_INVALID (-1): the answer of the argument check, which comes
+    before any device call (a machine without a GPU would answer PORRT_ERR_DEVICE from there on)"""
+    import ctypes as C
+    import numpy as np
+    raw = C.CDLL(lib._name).porrt_conditional_dijkstra            # the same symbol with plain pointers, so that NULL can be passed
+    vp = C.c_void_p
+    raw.restype = C.c_int
+    raw.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    arrays = [np.zeros(2), np.zeros(1, dtype=np.uint32), np.ones((1, 1)), np.ones(1, dtype=np.uint8), np.zeros(2, dtype=np.uint64),
+              np.zeros(1, dtype=np.uint32), np.zeros(2, dtype=np.uint64), np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64), np.zeros(1)]
+
+    def call(n, null=None, n_final=0):
+        xy, brow, bel, types, coff, cid, poff, pid, fin, dist = [None if k == null else a.ctypes.data for k, a in enumerate(arrays)]
+        return raw(0, n, xy, brow, bel, 1, 1, types, coff, cid, poff, pid, fin, n_final, dist)
+    assert call(0) == -1
+    for null in (0, 1, 2, 3, 4, 6, 9):                             # xy, belief_row, beliefs, types, child_off, parent_off, dist
+        assert call(1, null) == -1, null
+    assert call(1, 8, n_final=1) == -1                               # finals announced but not given
+    assert call(0xFFFFFFFF) == -1                                    # more nodes than a 32-bit id holds: refused before any array is read

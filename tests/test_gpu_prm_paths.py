@@ -1,6 +1,8 @@
 """GPU tests of porrt_prm_plan_paths: PRM::plan_path (prm.rs:111-123) for many start/goal pairs on one roadmap in one call.  Every
 answer equals porrt_prm_plan_path and the oracle's literal restatement bit for bit; queries that share a goal node share a row of
-costs; rows run in passes of at most option prm_rows; and the interface's sizing, staleness and error rules hold."""
+costs; rows run in passes of at most option prm_rows; and the interface's sizing, staleness and error rules hold.  The single call
+is a batch of one pair through the same code, so the independent check of both is the oracle (its literal kd-tree walk and
+dijkstra); the comparisons with porrt_prm_plan_path check the single call's copy-out."""
 import ctypes as C
 
 import numpy as np
@@ -126,6 +128,7 @@ def test_rows_are_shared_and_run_in_passes(bench8000):
         e.set_option("prm_xcd_rows", 1)
     for i in range(0, 300, 10):
         assert same(base[i], e.prm_plan_path(rs[i], G[i])), i
+        assert same(base[i], o.prm_plan_path(rs[i], G[i])), i
     for i in (0, 1, 2, 150):
         assert same(base[i], o.prm_plan_path(rs[i], G[i])), i
     with pytest.raises(RuntimeError):
@@ -133,7 +136,7 @@ def test_rows_are_shared_and_run_in_passes(bench8000):
 
 
 def test_interface(eng_mod, bench8000):
-    e, _ = bench8000
+    e, o = bench8000
     L = e._l
     S = np.array([[0.0, -0.8], [-0.7, 0.7], [0.3, 0.3]])
     G = np.array([[0.9, 0.0], [0.7, -0.7], [0.3, 0.3]])
@@ -146,6 +149,7 @@ def test_interface(eng_mod, bench8000):
     assert L.porrt_prm_get_paths(e._c, full.ctypes.data_as(C.c_void_p), total) == total
     for i in range(3):
         assert same(full[int(off[i]):int(off[i + 1])], e.prm_plan_path(S[i], G[i]))
+        assert same(full[int(off[i]):int(off[i + 1])], o.prm_plan_path(S[i], G[i]))
     # n = 0
     off0 = np.full(1, 99, dtype=np.uint64)
     assert L.porrt_prm_plan_paths(e._c, np.zeros(0), np.zeros(0), 0, off0, None, 0) == 0 and off0[0] == 0
@@ -176,7 +180,16 @@ def test_interleaved_with_single_calls_and_rrt(eng_mod):
     o.grow_prm((0.0, -0.8), 0.1, 2.0, 3000)
     S, G = random_pairs(21, 20)
     first = e.prm_plan_paths(S, G)
+    # the single call leaves the last batched call's answers and counts alone
+    total = sum(len(p) for p in first)
+    before, after = np.full((total, 2), 7.0), np.full((total, 2), 9.0)
+    assert e._l.porrt_prm_get_paths(e._c, before.ctypes.data_as(C.c_void_p), total) == total
+    info = e.prm_paths_info()
     singles = [e.prm_plan_path(S[i], G[i]) for i in range(5)]
+    assert e._l.porrt_prm_get_paths(e._c, after.ctypes.data_as(C.c_void_p), total) == total
+    assert before.tobytes() == after.tobytes() and same(before, np.concatenate(first))
+    assert all(e.prm_paths_info()[k] == info[k] for k in ("queries", "rows", "passes", "sweeps"))
+    assert info["queries"] == 20
     again = e.prm_plan_paths(S, G)
     assert all(same(a, b) for a, b in zip(first, again))
     assert all(same(first[i], singles[i]) for i in range(5))
@@ -191,3 +204,43 @@ def test_interleaved_with_single_calls_and_rrt(eng_mod):
     paths = e.prm_plan_paths(S, G)
     assert all(same(paths[i], o.prm_plan_path(S[i], G[i])) for i in range(20))
     assert same(paths[3], e.prm_plan_path(S[3], G[3]))
+
+
+@pytest.mark.parametrize("samples", [200, 3000])
+def test_single_call_at_the_edges_of_one_row(eng_mod, samples):
+    """porrt_prm_plan_path is a batch of one row: 200 samples are one block of 256 nodes with a partial tail and fewer than 8
+    workgroups, 3000 are twelve blocks, not a multiple of 8"""
+    case = cases.cfg2(4000)
+    e = cases.configure(eng_mod.Engine(), case)
+    o = cases.configure(orc.Oracle(), case)
+    e.grow_prm((0.0, -0.8), 0.1, 2.0, samples)
+    o.grow_prm((0.0, -0.8), 0.1, 2.0, samples)
+    S, G = random_pairs(samples, 6)
+    for s, g in zip(S, G):
+        assert same(e.prm_plan_path(s, g), o.prm_plan_path(s, g)), (s, g)
+    node = tuple(e.tree()[0][samples // 2])                      # start and goal on the same node: one state
+    one = e.prm_plan_path(node, node)
+    assert len(one) == 1 and same(one, o.prm_plan_path(node, node))
+
+
+def test_single_call_unconnected_pair(eng_mod):
+    e, o = pair(eng_mod, "door_map_like", "door_map_like_zone_ids", cases.DOOR, 0.3, 3)
+    e.grow_prm((0.5, -0.6), 0.05, 5.0, 3000)                  # the roadmap of test_connected_and_unconnected_in_one_call
+    o.grow_prm((0.5, -0.6), 0.05, 5.0, 3000)
+    rs, rg = random_pairs(4, 60)
+    s, g = next(((s, g) for s, g in zip(rs, rg) if len(o.prm_plan_path(s, g)) == 0), (None, None))
+    assert s is not None, "none of the 60 random pairs is unconnected in the oracle's roadmap: the case needs another seed"
+    got = e.prm_plan_path(s, g)
+    assert got.shape == (0, 2) and same(got, o.prm_plan_path(s, g))
+    assert e._l.porrt_prm_plan_path(e._c, s, g, None, 0) == 0
+
+
+def test_single_call_cap_smaller_than_the_path(bench8000):
+    """porrt_prm_plan_path returns the number of states always and writes at most cap of them"""
+    e, o = bench8000
+    s, g = np.array([0.0, -0.8]), np.array([0.9, 0.0])
+    full = o.prm_plan_path(s, g)
+    assert len(full) > 2
+    buf = np.full((len(full) + 3, 2), 7.0)
+    assert e._l.porrt_prm_plan_path(e._c, s, g, buf.ctypes.data_as(C.c_void_p), 2) == len(full)
+    assert same(buf[:2], full[:2]) and np.all(buf[2:] == 7.0)
