@@ -420,7 +420,9 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * wave gives back its slot and its LDS lists whatever its neighbours still do, and the step's single workgroups -- page filing, goal-point copies,
  * goal path -- as k_conn2_riders, a kernel of its own on the same stream; 4 = everything in one kernel of four-wave workgroups, k_conn2_wg4),
  * "conn_riders_first" (1, default: k_conn2_riders before k_conn2 of its step; 0 = after it), "nn_wg_waves" (waves per workgroup of k_nn2: 4,
- * default, or 1), "compact_rows" (1, default: a
+ * default, or 1), "commit_flat" (the group kernels' rewire commit: 1, default: a workgroup takes 128 consecutive samples of its row and runs one
+ * lane per candidate record -- k_nn2's commit workgroups and k_commit_flat after the last step; 0 = a group of lanes per sample, k_commit2 after
+ * the last step), "compact_rows" (1, default: a
  * porrt_grow_batch whose members end at different steps launches its later steps on the members that still have work), "gtrack_side" (1 = a single query's goal-path workgroup as a kernel
  * of its own on the side stream; measured slower, 0 is the default: a workgroup of the step kernel), "box_table"
  * (1, default: the group and roadmap kernels answer "is this segment free" from a summed-area table of the raster when the bounding
@@ -436,7 +438,7 @@ int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
  * this context led -- needed the whole kd structure, which was built after its steps), "kd_lca_steps" (this context's own need: 1 + the
  * last step with a tie that took that structure, 0 = none), "compactions" (how often the last batch this context led gathered the
  * members still running), "n_heavy" (samples of this context's last grow with more hits than their LDS list holds: served by a whole wave
- * from the lists in memory), "conn_wg_waves", "conn_riders_first", "nn_wg_waves", "dp_wide_rows", "dp_levels" and "dp_wide_levels" (the levels of the last layered expected costs, 0 when the
+ * from the lists in memory), "conn_wg_waves", "conn_riders_first", "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed), "dp_wide_rows", "dp_levels" and "dp_wide_levels" (the levels of the last layered expected costs, 0 when the
  * general sweeps ran; bit k of the mask: level k -- k-th smallest number of possible worlds -- ran the wide kernel) */
 int porrt_get_option(const porrt_ctx *ctx, const char *name, int64_t *value);
 

@@ -265,6 +265,9 @@ struct porrt_ctx {
     uint32_t opt_conn_wg_waves = 1;
     bool opt_conn_riders_first = true;
     uint32_t opt_nn_wg_waves = 4;          // "nn_wg_waves": the same choice for k_nn2 (4 or 1 waves per workgroup)
+    // "commit_flat": the group kernels' rewire phase 2 with one lane per candidate record, kSpan samples per workgroup (commit_flat_span:
+    // k_nn2's commit workgroups and k_commit_flat), 1, or with a group of lanes per sample (commit_rrt_sample, k_commit2), 0.  The same trees.
+    uint32_t opt_commit_flat = 1;
     // "batch_streams": porrt_grow_batch advances its contexts as this many sub-batches side by side, each a launch sequence
     // (hipGraph) of its own on its own streams, so that one sub-batch's kernel tails and its kd side chain are filled by the
     // other's kernels.  0 (default): 2 from 32 contexts on, else 1.
@@ -842,16 +845,17 @@ void porrt_ctx::launch_step(uint32_t b, uint32_t i0, uint32_t nb, uint32_t vword
     else if (GLn) {
         // GL lanes per sample; the previous step's rewire phase 2 rides along in extra workgroups
         const uint32_t spb = opt_nn_wg_waves * 64u / GLn, sblocks = (nb + spb - 1) / spb;
-        const uint32_t cblocks = commit_pend_b != 0xFFFFFFFFu ? (commit_pend_nb + spb - 1) / spb : 0;
+        const uint32_t cflat = opt_commit_flat, cspb = cflat ? kSpan : spb;
+        const uint32_t cblocks = commit_pend_b != 0xFFFFFFFFu ? (commit_pend_nb + cspb - 1) / cspb : 0;
         const dim3 g(sblocks + cblocks, Q);
         const uint32_t cnb = cblocks ? commit_pend_nb : 0u;
         if (opt_nn_wg_waves == 1u) {
-            if (GLn == 16) hipLaunchKernelGGL((k_nn2<16, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
-            else if (GLn == 32) hipLaunchKernelGGL((k_nn2<32, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
-            else hipLaunchKernelGGL((k_nn2<64, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
-        } else if (GLn == 16) hipLaunchKernelGGL(k_nn2<16>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
-        else if (GLn == 32) hipLaunchKernelGGL(k_nn2<32>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
-        else hipLaunchKernelGGL(k_nn2<64>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb);
+            if (GLn == 16) hipLaunchKernelGGL((k_nn2<16, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
+            else if (GLn == 32) hipLaunchKernelGGL((k_nn2<32, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
+            else hipLaunchKernelGGL((k_nn2<64, 1>), g, dim3(64), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
+        } else if (GLn == 16) hipLaunchKernelGGL(k_nn2<16>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
+        else if (GLn == 32) hipLaunchKernelGGL(k_nn2<32>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
+        else hipLaunchKernelGGL(k_nn2<64>, g, dim3(256), 0, stream, rcp, b, i0, nb, vwords, commit_pend_b, cnb, cflat);
         commit_pend_b = 0xFFFFFFFFu;
     } else {
         // the previous step's rewire phase 2 rides along in extra workgroups
@@ -998,7 +1002,8 @@ static uint32_t kd_group_for(uint32_t K, uint32_t opt, uint32_t Q) {
 void porrt_ctx::flush_commit() {
     if (commit_pend_b == 0xFFFFFFFFu) return;
     const uint32_t vwords = (rc.cand_K + 63) / 64;
-    if (opt_group == 16) hipLaunchKernelGGL(k_commit2<16>, dim3((commit_pend_nb * 16 + 255) / 256, launch_Q), dim3(256), 0, stream, launch_rcp, commit_pend_b, commit_pend_nb, vwords);
+    if (opt_group && opt_commit_flat) hipLaunchKernelGGL(k_commit_flat, dim3((commit_pend_nb + kSpan - 1) / kSpan, launch_Q), dim3(256), 0, stream, launch_rcp, commit_pend_b, commit_pend_nb, vwords);
+    else if (opt_group == 16) hipLaunchKernelGGL(k_commit2<16>, dim3((commit_pend_nb * 16 + 255) / 256, launch_Q), dim3(256), 0, stream, launch_rcp, commit_pend_b, commit_pend_nb, vwords);
     else if (opt_group == 32) hipLaunchKernelGGL(k_commit2<32>, dim3((commit_pend_nb * 32 + 255) / 256, launch_Q), dim3(256), 0, stream, launch_rcp, commit_pend_b, commit_pend_nb, vwords);
     else hipLaunchKernelGGL(k_commit_rrt, dim3((commit_pend_nb * 64 + 255) / 256, launch_Q), dim3(256), 0, stream, launch_rcp, commit_pend_b, commit_pend_nb, vwords, lag_on ? 1u : 0u);
     commit_pend_b = 0xFFFFFFFFu;
@@ -1471,7 +1476,7 @@ int porrt_ctx::grow_once(const double start[2], double max_step, double search_r
     } else if (opt_graph && !prof && n_iter_min > 0) {
         // all steps up to n_iter_min as one hipGraph (two branches: main pipeline + kd insertion); the graph
         // only depends on the launch geometry, so it is instantiated once and replayed by later grows
-        const uint64_t key[6] = {(uint64_t)mode, K, n_iter_min, lds_bytes, (uint64_t)(uintptr_t)launch_rcp, kd_group | ((uint64_t)opt_early_wave << 8) | ((uint64_t)launch_Q << 32) | ((uint64_t)opt_group << 48) | ((uint64_t)pipe_on << 56) | ((uint64_t)lag_on << 57) | ((uint64_t)kd_lazy << 58) | ((uint64_t)(kd_lazy && opt_gtrack_side) << 59)};
+        const uint64_t key[6] = {(uint64_t)mode, K, n_iter_min, lds_bytes, (uint64_t)(uintptr_t)launch_rcp, kd_group | ((uint64_t)opt_early_wave << 8) | ((uint64_t)launch_Q << 32) | ((uint64_t)opt_group << 48) | ((uint64_t)pipe_on << 56) | ((uint64_t)lag_on << 57) | ((uint64_t)kd_lazy << 58) | ((uint64_t)(kd_lazy && opt_gtrack_side) << 59) | ((uint64_t)opt_commit_flat << 60)};
         if (!graph_exec || memcmp(key, graph_key, sizeof key)) {
             double t0 = now_s();
             if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
@@ -3363,7 +3368,7 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
             steps = sched_steps();
             if (sched_rc) { L->set_err("porrt_grow_batch: step schedule (device)"); return sched_rc; }
         } else if (L->opt_graph && !prof && !L->sub_eager) {
-            const uint64_t key[6] = {(uint64_t)mode, K, n_iter, L->run_lds_bytes, (uint64_t)(uintptr_t)L->launch_rcp, L->kd_group | ((uint64_t)L->opt_early_wave << 8) | ((uint64_t)n << 32) | ((uint64_t)L->opt_group << 48) | ((uint64_t)L->pipe_on << 56)};
+            const uint64_t key[6] = {(uint64_t)mode, K, n_iter, L->run_lds_bytes, (uint64_t)(uintptr_t)L->launch_rcp, L->kd_group | ((uint64_t)L->opt_early_wave << 8) | ((uint64_t)n << 32) | ((uint64_t)L->opt_group << 48) | ((uint64_t)L->pipe_on << 56) | ((uint64_t)L->opt_commit_flat << 60)};
             if (!L->graph_exec || memcmp(key, L->graph_key, sizeof key)) {
                 if (L->graph_exec) { (void)hipGraphExecDestroy(L->graph_exec); L->graph_exec = nullptr; }
                 hipGraph_t g = nullptr;
@@ -4823,6 +4828,8 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "conn_wg_waves")) *value = c->opt_conn_wg_waves;
     else if (!strcmp(name, "conn_riders_first")) *value = c->opt_conn_riders_first ? 1 : 0;
     else if (!strcmp(name, "nn_wg_waves")) *value = c->opt_nn_wg_waves;
+    else if (!strcmp(name, "commit_flat")) *value = c->opt_commit_flat;
+    else if (!strcmp(name, "cand_cap")) *value = c->opt_cand_cap;                     // (grown by a call whose lists overflowed: the call was replayed)
     else if (!strcmp(name, "dp_wide_rows")) *value = (int64_t)c->opt_dp_wide_rows;
     else if (!strcmp(name, "dp_levels")) *value = c->dp.valid ? (int64_t)c->dp.levels : 0;          // levels of the last layered costs (0: the general sweeps ran)
     else if (!strcmp(name, "tamp_streams")) *value = c->opt_tamp_streams;
@@ -4872,6 +4879,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "conn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("conn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_conn_wg_waves = (uint32_t)value; }
     else if (!strcmp(name, "conn_riders_first")) c->opt_conn_riders_first = value != 0;
     else if (!strcmp(name, "nn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("nn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_nn_wg_waves = (uint32_t)value; }
+    else if (!strcmp(name, "commit_flat")) { if (value != 0 && value != 1) { c->set_err("commit_flat: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_commit_flat = (uint32_t)value; }
     else if (!strcmp(name, "kd_group")) c->opt_kd_group = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 8));
     else if (!strcmp(name, "tamp_streams")) { if (value != 0 && value != 1) { c->set_err("tamp_streams: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_tamp_streams = (int)value; }
     else if (!strcmp(name, "tamp_wave")) { if (value < 1 || value > 65536) { c->set_err("tamp_wave: 1 .. 65536"); return PORRT_ERR_INVALID; } c->opt_tamp_wave = (uint32_t)value; }

@@ -19,6 +19,7 @@
 // read by the connect pass, 8 B more written and read again by the commit pass); now 12 B per actual rewire go out.
 #pragma once
 #include "porrt_device.hpp"
+#include "porrt_span.hpp"
 
 namespace porrt {
 
@@ -444,16 +445,108 @@ __device__ __forceinline__ void group_nn(const RunConst &rc, uint32_t b, const G
     if (best == 0x7FFFFFFF) { nn = 0; fx = as_global(rc.nx)[0]; fy = as_global(rc.ny)[0]; }   // (cannot happen without a filter: the root exists)
 }
 
-// RRT* step, first kernel: GL lanes per sample.  grid.x = ceil(nb / SPB) search workgroups + ceil(cnb / SPB) workgroups
-// running the rewire phase 2 of step cb (commit_rrt_sample), SPB = 256 / GL samples per workgroup.
+// The rewire phase 2 of step cb from a flat index (option commit_flat): workgroup `sb` of a row takes the kSpan consecutive samples
+// from sb * kSpan on and runs one lane per candidate RECORD of theirs, not a group of lanes per sample -- a step of a grown tree
+// leaves about four records per sample, and a 16-lane group with four of them is twelve idle lanes and, for 1024 samples, 256 waves
+// where eight do.  The first wave builds the exclusive prefix of the samples' counts in LDS (porrt_span.hpp), every lane finds its
+// record's sample by a binary search of fixed length in it and then does what commit_rrt_sample does for a record without `lag`:
+// the same loads, the same test on equal bits, the same three stores with the same values.  Which lane makes them does not matter
+// (the parent is a minimum over the new ids, all winners of a node carry the same bits), so the trees are the same trees.
+// T threads per workgroup, all of which call this or none (the early returns are uniform over the workgroup).
+template <uint32_t T>
+__device__ __forceinline__ void commit_flat_span(const RunConst &rc, uint32_t cb, uint32_t vwords, uint32_t cnb, uint32_t sb) {
+    static_assert(T % 64u == 0u, "whole waves");
+    __shared__ uint32_t s_prefix[kSpan + 1u];
+    const uint32_t tid = threadIdx.x, k0 = sb * kSpan;
+    if (k0 >= cnb) return;
+    const uint32_t rnb = row_nb(rc, cb, cnb), limit = rnb < cnb ? rnb : cnb;
+    if (k0 >= limit) return;                    // (a row that has stopped, does not run this step, or runs a shorter one)
+    const uint32_t cap = rc.cand_cap;
+    const int N = (int)as_global(rc.n_at)[cb];
+    const uint32_t base = (uint32_t)N + rank_before(rc, cb, vwords, k0);                    // id of the span's first valid sample
+    unsigned long long words[kSpanWords];
+#pragma unroll
+    for (uint32_t w = 0; w < kSpanWords; ++w) {
+        const uint32_t wi = (k0 >> 6) + w;
+        words[w] = wi < vwords ? as_global(rc.valid_mask)[(size_t)cb * vwords + wi] : 0ull;
+    }
+    if (tid < 64u) {
+        uint32_t c[kSpanPer], s = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < kSpanPer; ++u) {
+            const uint32_t t = tid * kSpanPer + u, k = k0 + t;
+            const uint32_t stored = k < limit ? as_global(rc.cand_cnt)[cand_cnt_at(rc, cb, k)] : 0u;
+            c[u] = span_count(stored, cap, span_valid(words, t), k, limit);
+            s += c[u];
+        }
+        uint32_t incl = s;
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, off);
+            if (tid >= off) incl += v;
+        }
+        span_prefix_lane(s_prefix, tid, c, incl - s);
+    }
+    auto gdA = as_global(rc.distA);
+    auto gpd = as_global(rc.pg_d);
+    auto gso = as_global(rc.slot_of);
+    // the new nodes' own dist_root goes to their page slots (filed by insert_step_pages beside the connect pass)
+    for (uint32_t t = tid; t < kSpan; t += T)
+        if (k0 + t < limit && span_valid(words, t)) {
+            const uint32_t id = base + span_rank_in(words, t);
+            gpd[gso[id]] = gdA[id];
+        }
+    __syncthreads();
+    const uint32_t total = s_prefix[kSpan];
+    auto gcid = as_global(rc.cand_id);
+    auto gcval = as_global(rc.cand_val);
+    auto gdB = as_global(rc.distB);
+    // four records per lane in flight, each a chain of dependent loads (record -> distB[j] -> parent[j]); the dense first steps of a
+    // run leave tens of thousands of records per row
+    constexpr int U = 4;
+    for (uint32_t r0 = tid; r0 < total; r0 += T * (uint32_t)U) {
+        double via[U], dB[U];
+        int j[U], id[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t r = r0 + (uint32_t)u * T;
+            via[u] = -1.0; j[u] = 0; id[u] = 0;
+            if (r < total) {
+                const uint32_t t = span_find(s_prefix, r), a = r - s_prefix[t];       // a < the sample's clamped count <= cand_cap
+                via[u] = gcval[cand_val_off(rc, cb, k0 + t) + a];
+                j[u] = gcid[cand_off(rc, cb, k0 + t) + a];
+                id[u] = (int)(base + span_rank_in(words, t));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) dB[u] = via[u] >= 0.0 ? gdB[j[u]] : 0.0;            // (the uncompacted list of the goal-point copies' leader holds negative entries)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!(via[u] >= 0.0) || f64_bits(via[u]) != f64_bits(dB[u])) continue;
+            auto gpar = as_global(rc.parent) + j[u];
+            int old = *gpar;
+            while (old < N || id[u] < old) {        // parents from before this step are always < N
+                int expect = old;
+                if (__hip_atomic_compare_exchange_strong(gpar, &expect, id[u], __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                old = expect;
+            }
+            gdA[j[u]] = via[u];
+            gpd[gso[j[u]]] = via[u];
+        }
+    }
+}
+
+// RRT* step, first kernel: GL lanes per sample.  grid.x = ceil(nb / SPB) search workgroups + the workgroups running the rewire
+// phase 2 of step cb: ceil(cnb / SPB) of them, a group of GL lanes per sample (commit_rrt_sample), SPB = 256 / GL samples per
+// workgroup, or (cflat) ceil(cnb / kSpan), a lane per candidate record (commit_flat_span).
 #ifndef PORRT_NN2_WAVES
 #define PORRT_NN2_WAVES 5
 #endif
 template <int GL, int WV = 4>
 __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_NN2_WAVES, 8))) void k_nn2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t i0, uint32_t nb, uint32_t vwords, uint32_t cb,
-                                             uint32_t cnb) {
+                                             uint32_t cnb, uint32_t cflat) {
     static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
-    constexpr uint32_t SPB = (uint32_t)WV * 64u / GL;      // (WV waves per workgroup; nothing below synchronises beyond the wave)
+    constexpr uint32_t SPB = (uint32_t)WV * 64u / GL;      // (WV waves per workgroup; the search synchronises nothing beyond the wave)
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     xcd_swizzle(bx, by);
     const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
@@ -462,6 +555,12 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_N
     tm.base = (threadIdx.x & 63u) - tm.gl;
     const uint32_t near_blocks = (nb + SPB - 1u) / SPB;
     if (bx >= near_blocks) {
+        if (cflat) {
+            PORRT_T0();
+            commit_flat_span<(uint32_t)WV * 64u>(rc, cb, vwords, cnb, bx - near_blocks);
+            PORRT_TACC_A(rc, 4);
+            return;
+        }
         const uint32_t ck = (bx - near_blocks) * SPB + threadIdx.x / GL;
         PORRT_T0();
         if (ck < cnb && ck < row_nb(rc, cb, cnb)) commit_rrt_sample(rc, cb, vwords, ck, tm.gl, GL);
@@ -887,6 +986,10 @@ template <int GL>
 __global__ __launch_bounds__(256) void k_commit2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords) {
     const uint32_t k = (blockIdx.x * 256u + threadIdx.x) / GL;
     if (k < nb && k < row_nb(rcp[blockIdx.y], b, nb)) commit_rrt_sample(rcp[blockIdx.y], b, vwords, k, threadIdx.x % GL, GL);
+}
+// the same from a flat index (commit_flat_span): grid = (ceil(nb / kSpan), Q).  It needs few registers and asks for eight waves per SIMD.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_commit_flat(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords) {
+    commit_flat_span<256u>(rcp[blockIdx.y], b, vwords, nb, blockIdx.x);
 }
 
 } // namespace porrt
