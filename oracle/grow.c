@@ -21,8 +21,16 @@
  *       strict `<` against the current dist_root of the target;
  *     - PTO: reach[new] = OR over edges of reach_snapshot[nbr] & validity, then
  *       reach[nbr] |= reach[new] & validity (pto.rs:111-120 order).
- *     With K = 1 this is the reference loop itself; tests assert
- *     batched(K=1) == seq bit for bit.
+ *     With K = 1 this is the reference loop itself on every stream in which no
+ *     sample has two nodes at DIFFERENT places at exactly the least distance (any
+ *     continuous sampler: tests assert batched(K=1) == seq bit for bit).  Where a
+ *     sample has two such nodes the contract takes the lowest id and the reference
+ *     the first one its near-side-first kd walk visits (nearest_neighbor.rs:59-88),
+ *     and the two steer to different states: tests/test_exact_inputs_cpu.py shows
+ *     both (test_k1_is_the_reference_loop_without_ties,
+ *     test_k1_differs_from_the_reference_loop_on_nearest_ties).  Copies at one place
+ *     do not part them: a copy lies in the right subtree of the earlier one, which
+ *     the walk visits first.
  *   ORC_ALGO_BATCHED_KD (2) computes the same batched result with the kd-tree as
  *   a candidate generator (exact: the radius set is a set, and the NN tie-break is
  *   re-done over all nodes at the minimal distance) so that 100k-node cases
@@ -39,7 +47,22 @@ static void reset_outputs(orc_ctx *c, int mode) {
     c->n_edges = 0;
     c->complete = 0;
     c->oob = 0;
+    c->nn_log_n = 0;
     c->err[0] = 0;
+}
+
+void orc_ctx_log_nearest(orc_ctx *c, uint64_t id) {
+    if (c->nn_log_n == c->nn_log_cap) {
+        uint64_t cap = c->nn_log_cap ? 2 * c->nn_log_cap : 1024;
+        uint64_t *p = (uint64_t *)realloc(c->nn_log, cap * sizeof(uint64_t));
+        if (!p) {                                  /* the probe loses its entries; the growth itself is not touched */
+            snprintf(c->err, sizeof c->err, "out of memory for the nearest-id log");
+            return;
+        }
+        c->nn_log = p;
+        c->nn_log_cap = cap;
+    }
+    c->nn_log[c->nn_log_n++] = id;
 }
 
 static uint64_t add_node(orc_ctx *c, const double s[2], int64_t parent, double dist, uint64_t reach, uint32_t vid) {
@@ -108,6 +131,7 @@ static int rrt_seq(orc_ctx *c, const double start[2], double max_step, double se
         double ns[2];
         if (rrt_sample(c, i, ns)) { rc = -1; break; }            /* rrt.rs:112 */
         uint64_t kd_from = orc_kd_nearest(kd, ns, NULL, 0);      /* rrt.rs:113 */
+        orc_ctx_log_nearest(c, kd_from);
         double from[2];
         node_state(c, kd_from, from);
         orc_steer(from, ns, max_step);                           /* rrt.rs:115 */
@@ -258,6 +282,7 @@ static int rrt_batched(orc_ctx *c, const double start[2], double max_step, doubl
         for (uint64_t k = 0; k < nbatch; ++k) {
             step_item *it = &items[k];
             it->nn = use_kd ? nn_kd(c, kd, it->ns, NULL, 0, &tmp) : nn_brute(c, n_snap, it->ns, NULL, 0);
+            orc_ctx_log_nearest(c, it->nn);
             double from[2];
             node_state(c, it->nn, from);
             orc_steer(from, it->ns, max_step);
@@ -375,6 +400,7 @@ static int pto_seq(orc_ctx *c, const double start[2], double max_step, double se
         double ns[2];
         if (pto_sample(c, i, &world, ns)) { rc = -1; break; }          /* pto.rs:71 */
         uint64_t kd_from = orc_kd_nearest(kd, ns, c->reach, world);    /* pto.rs:74-77 */
+        orc_ctx_log_nearest(c, kd_from);
         double from[2];
         node_state(c, kd_from, from);
         orc_steer(from, ns, max_step);                                 /* pto.rs:79 */
@@ -464,6 +490,7 @@ static int pto_batched(orc_ctx *c, const double start[2], double max_step, doubl
             step_item *it = &items[k];
             it->nn = use_kd ? nn_kd(c, kd, it->ns, reach_snap, it->world, &tmp)
                             : nn_brute(c, n_snap, it->ns, reach_snap, it->world);
+            orc_ctx_log_nearest(c, it->nn);
             double from[2];
             node_state(c, it->nn, from);
             orc_steer(from, it->ns, max_step);
@@ -554,6 +581,10 @@ int orc_grow(orc_ctx *c, const double start[2], double max_step, double search_r
 /* ------------------------------------------------------------------ getters */
 uint64_t orc_num_nodes(const orc_ctx *c) { return c->n_nodes; }
 uint64_t orc_num_iterations(const orc_ctx *c) { return c->n_iter; }
+uint64_t orc_get_nearest_ids(const orc_ctx *c, uint64_t *ids, uint64_t cap) {
+    if (ids) memcpy(ids, c->nn_log, (c->nn_log_n < cap ? c->nn_log_n : cap) * sizeof(uint64_t));
+    return c->nn_log_n;
+}
 
 int orc_get_tree(const orc_ctx *c, double *xy, int64_t *parent, double *dist_root) {
     for (uint64_t j = 0; j < c->n_nodes; ++j) {

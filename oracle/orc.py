@@ -98,6 +98,7 @@ def lib():
     sig("orc_grow", C.c_int, vp, _f64p, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int)
     sig("orc_num_nodes", C.c_uint64, vp)
     sig("orc_num_iterations", C.c_uint64, vp)
+    sig("orc_get_nearest_ids", C.c_uint64, vp, C.c_void_p, C.c_uint64)
     sig("orc_get_tree", C.c_int, vp, _f64p, _i64p, _f64p)
     sig("orc_num_final", C.c_uint64, vp)
     sig("orc_get_final_ids", C.c_int, vp, _u64p)
@@ -300,6 +301,14 @@ class Oracle:
 
     def num_iterations(self):
         return self._l.orc_num_iterations(self._c)
+
+    def nearest_ids(self):
+        """the node every iteration of the last grow steered from (entry i = iteration i + 1, rejected samples included)"""
+        n = self._l.orc_get_nearest_ids(self._c, None, 0)
+        ids = np.zeros(n, dtype=np.uint64)
+        if n:
+            self._l.orc_get_nearest_ids(self._c, ids.ctypes.data_as(C.c_void_p), n)
+        return ids
 
     def tree(self):
         n = self.num_nodes()

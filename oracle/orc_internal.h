@@ -59,6 +59,8 @@ struct orc_ctx {
     uint64_t n_edges, cap_edges;
     int complete;
     int oob; /* a raster access outside W x H happened (reference would panic) */
+    uint64_t *nn_log; /* nearest id chosen by iteration i + 1 of the last orc_grow (read-only probe for the tests) */
+    uint64_t nn_log_n, nn_log_cap;
     struct orc_bg *bg; /* belief.c: result of the last orc_build_belief_graph */
 };
 
@@ -67,6 +69,7 @@ int orc_pixel_class(const orc_ctx *c, uint32_t i, uint32_t j);
 void orc_ctx_reserve_nodes(orc_ctx *c, uint64_t n);
 void orc_ctx_push_final(orc_ctx *c, uint64_t id, uint64_t mask);
 void orc_ctx_push_edge(orc_ctx *c, uint32_t from, uint32_t to, uint32_t v);
+void orc_ctx_log_nearest(orc_ctx *c, uint64_t id);
 /* validity id of a state / transition as PTOFuncs (map_shelves_io.rs:464-488,
  * map_io.rs:487-513); -1 = None */
 int orc_state_validity(orc_ctx *c, const double xy[2]);

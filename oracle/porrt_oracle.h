@@ -116,6 +116,9 @@ int orc_grow(orc_ctx *c, const double start[2], double max_step, double search_r
 
 uint64_t orc_num_nodes(const orc_ctx *c);
 uint64_t orc_num_iterations(const orc_ctx *c);
+/* probe: the nearest node every iteration of the last orc_grow steered from (entry i = iteration i + 1; an iteration whose
+ * sample was then rejected is listed too); returns the number of entries, writes at most cap of them */
+uint64_t orc_get_nearest_ids(const orc_ctx *c, uint64_t *ids, uint64_t cap);
 int      orc_get_tree(const orc_ctx *c, double *xy, int64_t *parent, double *dist_root);
 uint64_t orc_num_final(const orc_ctx *c);
 int      orc_get_final_ids(const orc_ctx *c, uint64_t *ids);
