@@ -418,6 +418,7 @@ public:
         std::vector<double> cost(nq + 1, 0.0);
         const int64_t n = porrt_bg_extract_policies(ctx_.get(), st.data(), nq, off.data(), status.data(), cost.data(), nullptr, nullptr, nullptr, 0);
         if (n < 0) ctx_.check((int)n);
+        n_policies_ = nq;
         std::vector<uint64_t> oid((size_t)n);
         std::vector<int64_t> par((size_t)n);
         std::vector<uint8_t> leaf((size_t)n);
@@ -470,6 +471,43 @@ public:
             if (leaf[k]) policy.leafs.push_back(k);
         }
         return policy;
+    }
+    // the same for every policy extract_policies() returned last, in one device call (porrt_bg_refine_policies): one refined Policy
+    // per start, nullopt where there is none (statuses, when asked for: 1 no policy to refine, 2 a shortcut met a raster fault --
+    // the reference panics --, 3 a piece whose nodes carry different beliefs -- the reference asserts)
+    size_t n_policies_ = 0;                    // starts of the last extract_policies(): what porrt_bg_refine_policies answers for
+    std::vector<std::optional<Policy>> refine_policies(size_t n_iterations, std::vector<uint8_t> *statuses = nullptr) {
+        const int64_t cap = porrt_bg_get_policies(ctx_.get(), nullptr, nullptr, nullptr, 0);       // the nodes going in bound those coming out
+        if (cap < 0) ctx_.check((int)cap);
+        const size_t nq = n_policies_, room = (size_t)cap + 1;
+        std::vector<uint64_t> off(nq + 1, 0), oid(room);
+        std::vector<uint8_t> status(nq + 1, 0), leaf(room);
+        std::vector<double> cost(nq + 1, 0.0), xy(2 * room);
+        std::vector<int64_t> par(room);
+        const int64_t n = porrt_bg_refine_policies(ctx_.get(), n_iterations, off.data(), status.data(), cost.data(), xy.data(), oid.data(), par.data(),
+                                                   leaf.data(), (uint64_t)room);
+        if (n < 0) ctx_.check((int)n);
+        const size_t nb = porrt_bg_num_beliefs(ctx_.get()), nw = (size_t)n_worlds();
+        std::vector<double> flat(nb * nw);
+        ctx_.check(porrt_bg_get_beliefs(ctx_.get(), flat.data()));
+        std::vector<std::optional<Policy>> out(nq);
+        for (size_t q = 0; q < nq; ++q) {
+            if (status[q]) continue;
+            Policy policy;
+            policy.expected_costs = cost[q];
+            for (size_t k = 0, o = (size_t)off[q]; o < (size_t)off[q + 1]; ++k, ++o) {
+                PolicyNode pn;
+                pn.state = {xy[2 * o], xy[2 * o + 1]};
+                pn.belief_state.assign(flat.begin() + (oid[o] % nb) * nw, flat.begin() + (oid[o] % nb + 1) * nw);
+                pn.original_node_id = (size_t)oid[o];
+                if (par[o] >= 0) { pn.parent = (size_t)par[o]; policy.nodes[(size_t)par[o]].children.push_back(k); }
+                policy.nodes.push_back(std::move(pn));
+                if (leaf[o]) policy.leafs.push_back(k);
+            }
+            out[q] = std::move(policy);
+        }
+        if (statuses) statuses->assign(status.begin(), status.begin() + nq);
+        return out;
     }
     // pto.rs:151-183
     Policy plan_belief_space(const BeliefState &start_belief_state) {

@@ -280,8 +280,8 @@ int      porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, co
  * The node arrays are written only if the total fits in cap.  Returns the total number of policy nodes, or a negative error:
  * PORRT_ERR_INVALID for a start >= porrt_bg_num_nodes, or when the belief graph or its costs are missing or stale (a regrowth, a
  * new belief graph without new costs); PORRT_ERR_CAPACITY when the device pool cannot be allocated.  n = 0 returns 0 and writes
- * pol_off[0] = 0.  The policy porrt_bg_refine_policy refines stays that of the last porrt_bg_extract_policy; a policy from this
- * call is refined through porrt_refine_policy. */
+ * pol_off[0] = 0.  The policy porrt_bg_refine_policy refines stays that of the last porrt_bg_extract_policy; the policies of this
+ * call are refined together by porrt_bg_refine_policies (or one at a time through porrt_refine_policy). */
 int64_t  porrt_bg_extract_policies(porrt_ctx *ctx, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status,
                                    double *expected_costs, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
 /* The nodes of the last porrt_bg_extract_policies, without recomputing them (same total, same cap rule).  An error before the
@@ -341,6 +341,47 @@ int64_t  porrt_refine_policy(porrt_ctx *ctx, uint64_t n, const double *xy, const
 /* seconds of the last refinement that filled its arrays: total (host and device) and the kernel alone (HIP events; 0 when no piece
  * has 3 nodes or n_iterations is 0) */
 int      porrt_bg_get_refine_info(const porrt_ctx *ctx, double *total_s, double *device_s);
+
+/* ---- the refinement of many policies in one call: decomposition, shortcuts, recomposition and expected costs on the device.
+ * porrt_bg_refine_policies refines the policies of the context's last porrt_bg_extract_policies, porrt_mm_refine_policies those
+ * of its last porrt_mm_extract_policies (an error when there is none, or once the graph, the belief graph or the expected costs
+ * have changed since: the test of porrt_bg_get_policies / porrt_mm_get_policies).  Neither touches the policy that
+ * porrt_bg_refine_policy / porrt_mm_refine_policy refines nor what porrt_bg_get_refine_info reports.
+ * porrt_refine_policies takes n_policies policies laid end to end: policy q is rows pol_off[q] .. pol_off[q + 1] (pol_off[0] = 0) of
+ * xy / parents / original_ids / belief_row, parents are indices WITHIN the policy (-1 for its row 0, children in ascending id
+ * order), beliefs as in porrt_refine_policy; it is checked on the context's raster with its world validities.
+ * Policy q's output equals, bit for bit, what porrt_refine_policy returns for policy q given alone -- states, original ids,
+ * parents, leaf flags and expected cost, every quirk included (one-node pieces have no end, nodes not reached from row 0 are
+ * dropped, pieces of <= 2 nodes are untouched, a fresh DiscreteSampler::new() per piece).
+ * status[q]: 0 refined; 1 no policy to refine (the extraction's status was not 0, or an empty policy): no nodes, cost +0.0;
+ * 2 a shortcut of this policy reads outside the raster, a door pixel without zone id or two zones on one segment (the single
+ * call's PORRT_ERR_RASTER): no nodes; 3 a piece whose nodes carry different beliefs (the single call's PORRT_ERR_INVALID,
+ * common.rs:102): no nodes.  A policy with nonzero status does not void the others; porrt_last_error names the first one.
+ * ref_off (n + 1 entries), status and expected_costs are always written: refined policy q is rows ref_off[q] .. ref_off[q + 1] of
+ * xy (2 per node) / original_ids / parents / is_leaf, parents[k] an index into the same policy (-1 for the root and for a piece
+ * start left unconnected by the quirk).  The node arrays are written only if the total fits in cap; the total is never more than
+ * the policies' nodes going in.  Returns the total, or a negative error, found on the host before any launch: PORRT_ERR_INVALID for
+ * a parent out of range, a row 0 whose parent is not -1, a belief row out of range, n_iterations >= 2^31 or 2^31 nodes or more in
+ * all; PORRT_ERR_CAPACITY for more than 2^26 draws (n_iterations x distinct piece lengths of the whole batch).
+ * cap = 0 is the sizing call: it launches no shortcut kernel, so ref_off and status 0 / 1 / 3 are final, status 2 cannot show and
+ * expected_costs are those of the policies as they went in.  n = 0 returns 0 and writes ref_off[0] = 0.
+ * One upload, the decomposition (one wave per policy), one small download (the lengths of the pieces of >= 3 nodes: the draws are
+ * made on the host, one table per distinct length of the whole batch), the shortcuts of every piece in one launch (longest first),
+ * recomposition and costs (one wave per policy), one download, on the context's stream. */
+int64_t  porrt_bg_refine_policies(porrt_ctx *ctx, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs,
+                                  double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_mm_refine_policies(porrt_ctx *ctx, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs,
+                                  double *xy, uint64_t *belief_node_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_refine_policies(porrt_ctx *ctx, uint64_t n_policies, const uint64_t *pol_off, const double *xy, const int64_t *parents,
+                               const uint64_t *original_ids, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows,
+                               uint32_t n_worlds, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs,
+                               double *out_xy, uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap);
+/* Counts and times of the context's last batch refinement: policies given, those with status 0, pieces of the policies that were
+ * decomposed (status 0 or 2), the pieces of >= 3 nodes the shortcut launch took (0 when n_iterations or cap was 0), refined nodes
+ * returned, distinct lengths among the pieces of >= 3 nodes; milliseconds of the shortcut launch (HIP events, 0 without one: what
+ * porrt_bg_get_refine_info calls device_s) and of the whole call. */
+struct porrt_refine_policies_info { uint64_t policies, ok, pieces, shortcut_pieces, nodes, distinct_lengths; double ms_device, ms_wall; };
+int      porrt_refine_policies_info(const porrt_ctx *ctx, struct porrt_refine_policies_info *out);
 
 /* ---- the QMDP policy extractor: QMdpPolicyExtractor (src/qmdp_policy_extractor.rs) on the graph of the last
  * porrt_grow(mode PORRT_MODE_PTO) of this context -- no belief graph: one cost-to-goal field per world and a greedy walk.
@@ -430,7 +471,9 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * costs swept together in one pass, 1 .. 4096, default 256), "prm_xcd_rows" (1, default: a row's sweep workgroups are placed together
  * on one XCD; 0 = the plain grid order).  None of them changes a result.  "qmdp_max_states" (porrt_qmdp_react: a walk that would emit
  * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there.  "policy_max_nodes" (porrt_bg_extract_policies,
- * porrt_mm_extract_policies: a policy that would have more nodes is status 4, 1 .. 2^24, default 1 << 16) is one too. */
+ * porrt_mm_extract_policies: a policy that would have more nodes is status 4, 1 .. 2^24, default 1 << 16) is one too.
+ * "refine_short_lds" (the batch refiner, default 1: the pieces of <= 256 nodes run in a launch of their own whose waves take 4 KiB
+ * of LDS instead of 16; 0 = every piece in one launch; the results are the same bits). */
 int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
 /* what was in force: "launch_mode" (the last porrt_grow_batch led by this context: 0 = one launch sequence, G = G sequences side by
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a

@@ -17,9 +17,11 @@
 #include "porrt_prm.hpp"
 #include "porrt_edges.hpp"
 #include "porrt_refine.hpp"
+#include "porrt_refine_batch.hpp"
 #include "porrt_qmdp.hpp"
 
 #include <algorithm>
+#include <functional>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -418,6 +420,16 @@ struct porrt_ctx {
     int64_t refine(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief,
                    const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
                    RefineOut &out);
+    // ---- the same for many policies in one call (porrt_refine_batch.hpp): refine_scratch slots 2-4, state of its own
+    struct porrt_refine_policies_info refp_info = {};
+    bool refp_done = false;
+    bool opt_refine_short_lds = true;      // "refine_short_lds": pieces of <= kRefineShortLdsNodes nodes in a launch of their own with the small LDS array (0: one launch)
+    hipEvent_t refp_ev[2] = {nullptr, nullptr};
+    std::vector<uint8_t> refp_stage;
+    int64_t refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
+                            const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
+                            uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
+                            int64_t *out_parents, uint8_t *out_leaf, uint64_t cap);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
     GrowScratch prm_paths_scratch;         // plan_path, one pair or many: device buffers (rows of costs, dirty flags, queries), kept across calls
@@ -2029,6 +2041,220 @@ int64_t porrt_ctx::refine(uint64_t n, const double *xy, const int64_t *parents, 
     return (int64_t)m;
 }
 
+// refine_solution(PartialShortCut(n_iter)) of n policies laid end to end (policy q = rows pol_off[q] .. pol_off[q + 1], parents within
+// the policy), everything on the device (porrt_refine_batch.hpp): one upload, the decomposition, one small download (per policy its
+// counts, per piece of >= 3 nodes its length), the draws of every distinct length made here as refine() makes them and uploaded with
+// the launch order (longest piece first), the shortcuts of all pieces in one launch, offsets, recomposition with the expected costs,
+// one download.  cap = 0 launches no shortcut kernel.  Returns the refined nodes of the policies with status 0.
+int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
+                                   const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
+                                   uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
+                                   int64_t *out_parents, uint8_t *out_leaf, uint64_t cap) {
+    const double t0 = now_s();
+    const std::string W_ = std::string(who) + ": ";
+    if (!pol_off || !ref_off || (n && (!status || !expected_costs))) { set_err(W_ + "pol_off, ref_off, status and expected_costs"); return PORRT_ERR_INVALID; }
+    if (n >= (1ull << 31) || pol_off[0] != 0) { set_err(W_ + "fewer than 2^31 policies, pol_off[0] = 0"); return PORRT_ERR_INVALID; }
+    for (uint64_t q = 0; q < n; ++q)
+        if (pol_off[q + 1] < pol_off[q]) { set_err(W_ + "pol_off must not decrease"); return PORRT_ERR_INVALID; }
+    const uint64_t T = pol_off[n];
+    if (T >= (1ull << 31)) { set_err(W_ + "fewer than 2^31 nodes in all"); return PORRT_ERR_INVALID; }
+    if (n_iter >= (1ull << 31)) { set_err(W_ + "at most 2^31 - 1 iterations"); return PORRT_ERR_INVALID; }
+    if (T && (!xy || !parents || !original || !belief || !beliefs || !n_rows || !nw)) { set_err(W_ + "the policies' arrays"); return PORRT_ERR_INVALID; }
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    // the upload: RunConst | pol_off | compat | beliefs | xy | original ids | parents (checked, 32 bits) | belief rows
+    const size_t o_off = up16(sizeof(RunConst)), o_cp = o_off + up16((n + 1) * 8), o_bel = o_cp + up16((size_t)n_rows * 8),
+                 o_xy = o_bel + up16((size_t)n_rows * nw * 8), o_or = o_xy + up16(T * 16), o_pa = o_or + up16(T * 8), o_br = o_pa + up16(T * 4),
+                 up_bytes = o_br + up16(T * 4);
+    refp_stage.resize(up_bytes);
+    uint8_t *stage = refp_stage.data();
+    {
+        int32_t *pa = (int32_t *)(stage + o_pa);
+        for (uint64_t q = 0; q < n; ++q) {
+            const uint64_t b = pol_off[q], m = pol_off[q + 1] - b;
+            for (uint64_t k = 0; k < m; ++k) {
+                const int64_t p = parents[b + k];
+                if (belief[b + k] >= n_rows) { set_err(W_ + "a belief row out of range (policy " + std::to_string(q) + ")"); return PORRT_ERR_INVALID; }
+                if (k == 0 ? p != -1 : (p < 0 || (uint64_t)p >= m || (uint64_t)p == k)) {
+                    set_err(W_ + "a parent out of range, or a row 0 that is no root (policy " + std::to_string(q) + ")");
+                    return PORRT_ERR_INVALID;
+                }
+                pa[b + k] = (int32_t)p;
+            }
+        }
+    }
+    refp_done = false;
+    refp_info = {};
+    refp_info.policies = n;
+    ref_off[0] = 0;
+    if (T == 0) {                                                    // nothing but empty policies: no device work
+        for (uint64_t q = 0; q < n; ++q) { ref_off[q + 1] = 0; status[q] = 1; expected_costs[q] = 0.0; }
+        if (n) set_err(W_ + "policy 0: no policy to refine");
+        refp_info.ms_wall = 1e3 * (now_s() - t0);
+        refp_done = true;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(device));
+    const bool shortcuts = cap != 0 && n_iter != 0;
+    RunConst g;
+    memset(&g, 0, sizeof g);
+    if (has_grid) {
+        // the raster (classes and summed-area table) in the refiner's slot 0, uploaded once per raster
+        classify_raster();
+        uint8_t *d_raster = nullptr;
+        HIPCHK(refine_scratch.get(0, d_raster, cls.size()));
+        if (refine_raster_gen != raster_gen) {
+            HIPCHK(hipMemcpyAsync(d_raster, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
+            refine_raster_gen = raster_gen;
+        }
+        g.cls = d_raster; g.clr = d_raster + (size_t)W * H; g.sat = opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(W, H)) : nullptr;
+        g.W = W; g.H = H; g.low0 = low[0]; g.low1 = low[1]; g.ppm = ppm; g.domain = domain; g.has_grid = has_grid;
+        g.n_validities = n_validities;
+        for (int i = 0; i < n_validities; ++i) g.validities[i] = validities[i];
+    }
+    memcpy(stage, &g, sizeof g);
+    memcpy(stage + o_off, pol_off, (n + 1) * 8);
+    memcpy(stage + o_cp, compat, (size_t)n_rows * 8);
+    memcpy(stage + o_bel, beliefs, (size_t)n_rows * nw * 8);
+    memcpy(stage + o_xy, xy, T * 16);
+    memcpy(stage + o_or, original, T * 8);
+    memcpy(stage + o_br, belief, T * 4);
+    // the work arrays behind it; the first download (records | lengths of the long pieces) in one piece at the end
+    const size_t L = T / 3 + 1;
+    size_t at = up_bytes;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up16(bytes); return o; };
+    const size_t w_link = take(T * 8), w_next = take(T * 4), w_src = take(T * 4), w_par = take(T * 4), w_leaf = take(T), w_any = take(T * sizeof(RefinePolAny)),
+                 w_longs = take(L * sizeof(RefinePolPiece)), w_x = take(T * 8), w_y = take(T * 8), w_q = take(T * 8), w_t = take(T * 8), w_p = take(T * 8),
+                 w_v = take(T * 8), w_err = take(n * 4), w_rec = take(n * sizeof(RefinePolRecord)), w_len = take(L * 4), bytes = at;
+    uint8_t *d = nullptr;
+    HIPCHK(refine_scratch.get(2, d, bytes));
+    RefinePolConst pc{};
+    pc.pol_off = (const unsigned long long *)(d + o_off); pc.in_xy = (const double *)(d + o_xy); pc.in_orig = (const unsigned long long *)(d + o_or);
+    pc.in_parent = (const int32_t *)(d + o_pa); pc.in_belief = (const uint32_t *)(d + o_br); pc.beliefs = (const double *)(d + o_bel);
+    pc.nw = nw; pc.n_policies = (uint32_t)n;
+    pc.link = (uint2 *)(d + w_link); pc.next = (uint32_t *)(d + w_next); pc.src = (uint32_t *)(d + w_src); pc.par = (int32_t *)(d + w_par);
+    pc.leaf = d + w_leaf; pc.any = (RefinePolAny *)(d + w_any); pc.longs = (RefinePolPiece *)(d + w_longs); pc.long_len = (uint32_t *)(d + w_len);
+    pc.rec = (RefinePolRecord *)(d + w_rec); pc.x = (double *)(d + w_x); pc.y = (double *)(d + w_y);
+    pc.wq = (double *)(d + w_q); pc.wt = (double *)(d + w_t); pc.wp = (double *)(d + w_p); pc.wv = (double *)(d + w_v);
+    pc.pol_err = (uint32_t *)(d + w_err);
+    HIPCHK(hipMemcpyAsync(d, stage, up_bytes, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_refine_policies_decompose, dim3((uint32_t)n), dim3(64), 0, stream, pc);
+    HIPCHK(hipGetLastError());
+    std::vector<uint8_t> first(bytes - w_rec);
+    HIPCHK(hipMemcpyAsync(first.data(), d + w_rec, bytes - w_rec, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const RefinePolRecord *rec = (const RefinePolRecord *)first.data();
+    const uint32_t *long_len = (const uint32_t *)(first.data() + (w_len - w_rec));
+    // the launch order (longest first) and one table of draws per distinct length
+    uint64_t M = 0;
+    std::vector<uint64_t> keys;                                      // length << 32 | row of longs
+    for (uint64_t q = 0; q < n; ++q) {
+        if (rec[q].status) continue;
+        M += rec[q].rows;
+        refp_info.pieces += rec[q].pieces;
+        for (uint32_t j = 0; j < rec[q].longs; ++j) {
+            const uint64_t row = pol_off[q] / 3 + j;
+            keys.push_back((uint64_t)long_len[row] << 32 | row);
+        }
+    }
+    std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+    std::vector<std::pair<uint32_t, uint32_t>> len_at;               // (length, first draw), longest first
+    for (uint64_t k : keys)
+        if (len_at.empty() || len_at.back().first != (uint32_t)(k >> 32)) {
+            if (shortcuts && (len_at.size() + 1) * n_iter > (1ull << 26)) { set_err(W_ + "more than 2^26 draws (iterations x distinct piece lengths)"); return PORRT_ERR_CAPACITY; }
+            len_at.push_back({(uint32_t)(k >> 32), (uint32_t)(len_at.size() * n_iter)});
+        }
+    refp_info.distinct_lengths = len_at.size();
+    double ms_device = 0.0;
+    if (shortcuts && !keys.empty()) {
+        if (!has_grid) { set_err(W_ + "the refiner checks transitions on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
+        const size_t nd = len_at.size() * n_iter, o_dr = up16(keys.size() * sizeof(uint2)), bytes2 = o_dr + nd * sizeof(uint2);
+        std::vector<uint8_t> second(bytes2);
+        uint2 *order = (uint2 *)second.data(), *dr = (uint2 *)(second.data() + o_dr);
+        size_t li = 0, n_big = 0;
+        for (size_t k = 0; k < keys.size(); ++k) {
+            const uint32_t len = (uint32_t)(keys[k] >> 32);
+            while (len_at[li].first != len) ++li;
+            order[k] = make_uint2((uint32_t)keys[k], len_at[li].second);
+            if (len > kRefineShortLdsNodes) ++n_big;
+        }
+        for (const auto &la : len_at) {                              // DiscreteSampler::new() per piece (pto_policy_refiner.rs:172-175)
+            Pcg64 rng;
+            rng.seed_from_u64(0);
+            const uint64_t Ln = la.first;
+            for (uint64_t it = 0; it < n_iter; ++it) {
+                const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
+                const uint32_t s = (uint32_t)rng.gen_range_usize(Ln - 2);
+                const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(Ln - s - 2);
+                dr[la.second + it] = make_uint2(s | (joint << 31), e);
+            }
+        }
+        uint8_t *d2 = nullptr;
+        HIPCHK(refine_scratch.get(4, d2, bytes2));
+        for (int k = 0; k < 2; ++k) if (!refp_ev[k]) HIPCHK(hipEventCreate(&refp_ev[k]));
+        RefinePolLaunch ln{};
+        ln.rc.rc = (const RunConst *)d; ln.rc.draws = (const uint2 *)(d2 + o_dr); ln.rc.compat = (const unsigned long long *)(d + o_cp);
+        ln.rc.x = pc.x; ln.rc.y = pc.y; ln.rc.n_pieces = (uint32_t)keys.size(); ln.rc.n_iter = (uint32_t)n_iter;
+        ln.longs = pc.longs; ln.order = (const uint2 *)d2; ln.pol_err = pc.pol_err;
+        HIPCHK(hipMemcpyAsync(d2, second.data(), bytes2, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipEventRecord(refp_ev[0], stream));
+        const size_t n_first = opt_refine_short_lds ? n_big : keys.size();
+        if (n_first) {
+            ln.first = 0;
+            hipLaunchKernelGGL(k_refine_policies_shortcut<kRefineLdsNodes>, dim3((uint32_t)n_first), dim3(64), 0, stream, ln);
+            HIPCHK(hipGetLastError());
+        }
+        if (n_first < keys.size()) {                                 // the short pieces: a quarter of the LDS per wave
+            ln.first = (uint32_t)n_first;
+            hipLaunchKernelGGL(k_refine_policies_shortcut<kRefineShortLdsNodes>, dim3((uint32_t)(keys.size() - n_first)), dim3(64), 0, stream, ln);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(refp_ev[1], stream));
+        refp_info.shortcut_pieces = keys.size();
+    }
+    // offsets, recomposition and costs; the answers packed in one block: ref_off | cost | status | xy | original ids | parents | leafs
+    const size_t r_off = 0, r_cost = r_off + up16((n + 1) * 8), r_st = r_cost + up16(n * 8), r_xy = r_st + up16(n), r_or = r_xy + up16(M * 16),
+                 r_pa = r_or + up16(M * 8), r_lf = r_pa + up16(M * 8), bytes3 = r_lf + up16(M);
+    uint8_t *d3 = nullptr;
+    HIPCHK(refine_scratch.get(3, d3, bytes3));
+    pc.ref_off = (unsigned long long *)(d3 + r_off); pc.cost = (double *)(d3 + r_cost); pc.status = d3 + r_st; pc.out_xy = (double *)(d3 + r_xy);
+    pc.out_orig = (unsigned long long *)(d3 + r_or); pc.out_parent = (long long *)(d3 + r_pa); pc.out_leaf = d3 + r_lf;
+    hipLaunchKernelGGL(k_refine_policies_offsets, dim3(1), dim3(256), 0, stream, pc);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_refine_policies_recompose, dim3((uint32_t)n), dim3(64), 0, stream, pc);
+    HIPCHK(hipGetLastError());
+    std::vector<uint8_t> third(bytes3);
+    HIPCHK(hipMemcpyAsync(third.data(), d3, bytes3, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (refp_info.shortcut_pieces) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, refp_ev[0], refp_ev[1]));
+        ms_device = (double)ms;
+    }
+    memcpy(ref_off, third.data() + r_off, (n + 1) * 8);
+    memcpy(expected_costs, third.data() + r_cost, n * 8);
+    memcpy(status, third.data() + r_st, n);
+    const uint64_t total = ref_off[n];
+    if (total && total <= cap) {
+        if (out_xy) memcpy(out_xy, third.data() + r_xy, total * 16);
+        if (out_original) memcpy(out_original, third.data() + r_or, total * 8);
+        if (out_parents) memcpy(out_parents, third.data() + r_pa, total * 8);
+        if (out_leaf) memcpy(out_leaf, third.data() + r_lf, total);
+    }
+    for (uint64_t q = 0; q < n; ++q) refp_info.ok += status[q] == 0;
+    for (uint64_t q = 0; q < n; ++q)
+        if (status[q]) {
+            static const char *const what[4] = {"", "no policy to refine", "a shortcut reads outside the raster, a door pixel without zone id or two zones on one segment (the reference panics)",
+                                                "a piece whose nodes carry different beliefs (the reference asserts, common.rs:102)"};
+            set_err(W_ + "policy " + std::to_string(q) + ": " + what[status[q] & 3]);
+            break;
+        }
+    refp_info.nodes = total;
+    refp_info.ms_device = ms_device;
+    refp_info.ms_wall = 1e3 * (now_s() - t0);
+    refp_done = true;
+    return (int64_t)total;
+}
+
 // PRM::init + PRM::grow_graph (prm.rs:33-109); see porrt_prm.hpp.
 int porrt_ctx::grow_prm(const double start[2], double max_step, double search_radius, uint64_t n_iter_) {
     const uint64_t n_iter = n_iter_;
@@ -3579,6 +3805,7 @@ void porrt_destroy(porrt_ctx *c) {
     c->qmdp_scratch.free_all();
     c->policies_scratch.free_all();
     for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
+    for (int k = 0; k < 2; ++k) if (c->refp_ev[k]) (void)hipEventDestroy(c->refp_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
     if (c->d_active) (void)hipFree(c->d_active);
@@ -4440,6 +4667,84 @@ int porrt_bg_get_refine_info(const porrt_ctx *c, double *total_s, double *device
     return PORRT_OK;
 }
 
+// ---- refinement of many policies in one call (porrt_refine_batch.hpp)
+// compute_compatibility (common.rs:266-276) of every belief row with the context's world validities
+static std::vector<unsigned long long> refine_compat_rows(const porrt_ctx *c, const double *beliefs, uint32_t n_rows, uint32_t nw) {
+    std::vector<unsigned long long> compat(n_rows, 0ull);
+    for (uint32_t b = 0; b < n_rows; ++b)
+        for (int v = 0; v < c->n_validities; ++v) {
+            bool ok = true;
+            for (uint32_t w = 0; w < nw && ok; ++w) ok = !(beliefs[(size_t)b * nw + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
+            if (ok) compat[b] |= 1ull << v;
+        }
+    return compat;
+}
+int64_t porrt_bg_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                 uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try {
+        const PoliciesResult &res = c->policies;
+        if (!res.valid) { c->set_err("bg_refine_policies: no policies to refine: call porrt_bg_extract_policies first"); return PORRT_ERR_INVALID; }
+        if (!c->bg.valid || !c->dp.valid || !c->have_results || c->bg_graph_tag != c->results_tag || res.tag != c->results_tag || res.stamp != c->bg_stamp ||
+            c->costs_stamp != c->bg_stamp) {
+            c->set_err("bg_refine_policies: the graph, the belief graph or the expected costs changed since porrt_bg_extract_policies");
+            return PORRT_ERR_INVALID;
+        }
+        const int r = c->download(porrt_ctx::DL_TREE);
+        if (r) return r;
+        const uint64_t n = res.status.size(), T = res.off.back(), B = c->bg.B;
+        const BeliefSpace &bs = c->bg.cache.space;
+        std::vector<double> pxy(2 * T);
+        std::vector<uint32_t> belief(T);
+        for (uint64_t k = 0; k < T; ++k) {                    // build_path_piece: the belief graph node's state and belief
+            const uint64_t id = res.original[k], node = id / B;
+            pxy[2 * k] = c->h_nx[node]; pxy[2 * k + 1] = c->h_ny[node];
+            belief[k] = (uint32_t)(id % B);
+        }
+        return c->refine_policies("bg_refine_policies", n, res.off.data(), pxy.data(), res.parent.data(), res.original.data(), belief.data(), bs.vec.data(),
+                                  (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents,
+                                  is_leaf, cap);
+    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int64_t porrt_mm_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                 uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try {
+        const PoliciesResult &res = c->mm_policies;
+        const MmPlanState &s = c->mmp;
+        if (!res.valid) { c->set_err("mm_refine_policies: no policies to refine: call porrt_mm_extract_policies first"); return PORRT_ERR_INVALID; }
+        if (!c->mm.valid || !s.valid || s.gen != c->mm.gen || s.costs_gen != s.gen || !s.dp.valid || res.tag != s.gen || res.stamp != c->mm_costs_runs) {
+            c->set_err("mm_refine_policies: the modes, the belief graph or the expected costs changed since porrt_mm_extract_policies");
+            return PORRT_ERR_INVALID;
+        }
+        const uint64_t n = res.status.size(), T = res.off.back();
+        const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
+        std::vector<uint32_t> row(T);
+        for (uint64_t k = 0; k < T; ++k) row[k] = mm_mode_of(s, res.original[k]);
+        const std::vector<unsigned long long> compat = refine_compat_rows(c, s.beliefs.data(), M, nw);
+        return c->refine_policies("mm_refine_policies", n, res.off.data(), res.xy.data(), res.parent.data(), res.original.data(), row.data(), s.beliefs.data(),
+                                  M, nw, compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap);
+    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int64_t porrt_refine_policies(porrt_ctx *c, uint64_t n_policies, const uint64_t *pol_off, const double *xy, const int64_t *parents,
+                              const uint64_t *original_ids, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows, uint32_t n_worlds,
+                              uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy,
+                              uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    try {
+        if (!pol_off || !beliefs || !n_belief_rows) { c->set_err("refine_policies: pol_off and the beliefs"); return PORRT_ERR_INVALID; }
+        if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policies: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
+        const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
+        return c->refine_policies("refine_policies", n_policies, pol_off, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds,
+                                  compat.data(), n_iterations, ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap);
+    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+}
+int porrt_refine_policies_info(const porrt_ctx *c, struct porrt_refine_policies_info *out) {
+    if (!c || !out || !c->refp_done) return PORRT_ERR_INVALID;
+    *out = c->refp_info;
+    return PORRT_OK;
+}
+
 // ---- the rest of MapShelfDomainTampPRM::plan on the modes of the last porrt_grow_mm_prm (porrt_mmplan.hpp)
 int porrt_mm_build_belief_graph(porrt_ctx *c) {
     if (!c) return PORRT_ERR_INVALID;
@@ -4840,6 +5145,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
     else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
+    else if (!strcmp(name, "refine_short_lds")) *value = c->opt_refine_short_lds ? 1 : 0;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4856,6 +5162,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "mm_levels")) c->mmp.use_levels = value != 0;
     else if (!strcmp(name, "mm_lds_nodes")) c->mmp.lds_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, kMmLdsNodes));
     else if (!strcmp(name, "box_table")) { c->opt_box_table = value != 0; c->cls_dirty = true; }
+    else if (!strcmp(name, "refine_short_lds")) c->opt_refine_short_lds = value != 0;
     else if (!strcmp(name, "gtrack_side")) c->opt_gtrack_side = value != 0;
     else if (!strcmp(name, "pipeline")) {
 #ifndef PORRT_DEV_NONCOOP

@@ -77,13 +77,16 @@ __device__ __forceinline__ double refine_lerp(double a, double b, uint32_t j, ui
 // kTamp: MapShelfDomainTampRRT::shortcut (map_shelves_tamp_rrt.rs:565-617) instead -- the same draws (a fresh DiscreteSampler::new()
 // per path, n = 100), one wave per path, but a transition is valid iff its traversed space is Free (RTTFuncs, :43-45: no state
 // check, no belief) and the step from the last candidate into node e is not checked at all.
-template <bool kTamp>
-__device__ __forceinline__ void refine_shortcut_body(const RefineConst &c) {
-    __shared__ double lx[kRefineLdsNodes], ly[kRefineLdsNodes];
+//
+// One piece on one wave.  Piece: RefinePiece, or a descriptor with the same off / len / draws / belief (the batch refiner's carries
+// its policy too, porrt_refine_batch.hpp); kLds: the piece states kept in LDS (a second, smaller array for a launch of short pieces
+// only); err: the word a raster fault is OR-ed into.  c gives the raster, the draws, the compatibilities, the states and n_iter.
+template <bool kTamp, uint32_t kLds, class Piece>
+__device__ __forceinline__ void refine_shortcut_piece(const RefineConst &c, const Piece &pc, uint32_t *err_word) {
+    __shared__ double lx[kLds], ly[kLds];
     const uint32_t lane = threadIdx.x;
-    const RefinePiece pc = c.pieces[blockIdx.x];
     const RunConst &rc = *c.rc;
-    const bool in_lds = pc.len <= kRefineLdsNodes;
+    const bool in_lds = pc.len <= kLds;
     double *X = in_lds ? lx : c.x + pc.off;
     double *Y = in_lds ? ly : c.y + pc.off;
     if (in_lds)
@@ -136,7 +139,12 @@ __device__ __forceinline__ void refine_shortcut_body(const RefineConst &c) {
     }
     if (in_lds)
         for (uint32_t j = lane; j < pc.len; j += 64) { as_global(c.x)[pc.off + j] = lx[j]; as_global(c.y)[pc.off + j] = ly[j]; }
-    if (fault && lane == 0) atomicOr(c.err, ERR_RASTER);
+    if (fault && lane == 0) atomicOr(err_word, ERR_RASTER);
+}
+
+template <bool kTamp>
+__device__ __forceinline__ void refine_shortcut_body(const RefineConst &c) {
+    refine_shortcut_piece<kTamp, kRefineLdsNodes>(c, c.pieces[blockIdx.x], c.err);
 }
 
 __global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) { refine_shortcut_body<false>(c); }

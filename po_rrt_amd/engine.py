@@ -48,6 +48,7 @@ SYMBOLS = [
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
+    "porrt_bg_refine_policies", "porrt_mm_refine_policies", "porrt_refine_policies", "porrt_refine_policies_info",
 ]
 
 
@@ -85,6 +86,12 @@ class PoliciesInfo(C.Structure):
     """struct porrt_policies_info"""
     _fields_ = [("queries", C.c_uint64), ("ok", C.c_uint64), ("nodes", C.c_uint64), ("max_nodes", C.c_uint64),
                 ("ms_device", C.c_double), ("ms_wall", C.c_double)]
+
+
+class RefinePoliciesInfo(C.Structure):
+    """struct porrt_refine_policies_info"""
+    _fields_ = [("policies", C.c_uint64), ("ok", C.c_uint64), ("pieces", C.c_uint64), ("shortcut_pieces", C.c_uint64), ("nodes", C.c_uint64),
+                ("distinct_lengths", C.c_uint64), ("ms_device", C.c_double), ("ms_wall", C.c_double)]
 
 
 class TreeDeviceView(C.Structure):
@@ -247,6 +254,11 @@ def load_library():
     sig("porrt_extract_policies", C.c_int64, C.c_int, C.c_uint64, _f64p, _u32p, _f64p, C.c_uint32, C.c_uint32, _u32p, _u64p, _u32p, _f64p,
         _u64p, C.c_uint64, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_policies_info", C.c_int, vp, C.POINTER(PoliciesInfo))
+    for nm in ("porrt_bg_refine_policies", "porrt_mm_refine_policies"):
+        sig(nm, C.c_int64, vp, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_refine_policies", C.c_int64, vp, C.c_uint64, _u64p, _f64p, _i64p, _u64p, _u32p, _f64p, C.c_uint32, C.c_uint32, C.c_uint64,
+        _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_refine_policies_info", C.c_int, vp, C.POINTER(RefinePoliciesInfo))
     _LIB = L
     return L
 
@@ -673,6 +685,7 @@ class Engine:
         off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
         stp = st if n else np.zeros(1, dtype=np.uint64)
         total = self._chk(int(self._l.porrt_bg_extract_policies(self._c, stp, n, off, status, cost, None, None, None, 0)))
+        self._n_pol = dict(getattr(self, "_n_pol", {}), bg=n)        # what refine_policies sizes its answer by
         oid, par, leaf = np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
         if total:
             p = lambda a: a.ctypes.data_as(C.c_void_p)
@@ -695,6 +708,7 @@ class Engine:
         off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
         stp = st if n else np.zeros(1, dtype=np.uint64)
         total = self._chk(int(self._l.porrt_mm_extract_policies(self._c, stp, n, off, status, cost, None, None, None, None, 0)))
+        self._n_pol = dict(getattr(self, "_n_pol", {}), mm=n)
         oid, par, leaf, xy = np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8), np.zeros((total, 2))
         if total:
             p = lambda a: a.ctypes.data_as(C.c_void_p)
@@ -732,6 +746,78 @@ class Engine:
         bel = _f64(beliefs).reshape(len(beliefs), -1)
         return self._refined(lambda oxy, ooid, opar, oleaf, cap, cost: self._l.porrt_refine_policy(
             self._c, len(par), xy, par, oid, row, bel, bel.shape[0], bel.shape[1], int(n_iterations), oxy, ooid, opar, oleaf, cap, cost))
+
+    def _refined_many_raw(self, n, cap, call):
+        """one batch call with room for cap nodes (never fewer than come back): ref_off [n + 1], status [n], expected costs [n],
+        states [total, 2], original ids, parents, leaf flags"""
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        cap = max(int(cap), 1)
+        xy, oid, par, leaf = np.zeros((cap, 2)), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        total = self._chk(int(call(off, status, cost, p(xy), p(oid), p(par), p(leaf), cap)))
+        assert total <= cap
+        return off, status[:n], cost[:n], xy[:total], oid[:total], par[:total], leaf[:total]
+
+    def _refined_many(self, n, cap, call):
+        """the same as a list: ((states, original ids, parents, leaf flags), cost) per policy -- None where its status is not 0 --
+        and the status array"""
+        off, status, cost, xy, oid, par, leaf = self._refined_many_raw(n, cap, call)
+        out = []
+        for q in range(n):
+            a, b = int(off[q]), int(off[q + 1])
+            out.append(None if status[q] else ((xy[a:b], oid[a:b], par[a:b], leaf[a:b]), float(cost[q])))
+        return out, status
+
+    def refine_policies_raw(self, n_iterations):
+        """porrt_bg_refine_policies as arrays: ref_off [n + 1], status [n], expected costs [n], states, original ids, parents, leaf flags"""
+        n = max(int(self._l.porrt_bg_get_policies(self._c, None, None, None, 0)), 0)
+        return self._refined_many_raw(self._n_policies("bg"), n, lambda off, st, cost, xy, oid, par, leaf, cap: self._l.porrt_bg_refine_policies(
+            self._c, int(n_iterations), off, st, cost, xy, oid, par, leaf, cap))
+
+    def refine_policies(self, n_iterations):
+        """every policy of the last extract_policies, refined as refine_policy refines one, in one device call
+        (porrt_bg_refine_policies): a list with ((states [k, 2], original belief node ids, parents, leaf flags), expected cost) per
+        policy -- None where there is none -- and the status array (0 refined, 1 no policy to refine, 2 a shortcut met a raster
+        fault, 3 a piece whose nodes carry different beliefs)"""
+        n = int(self._l.porrt_bg_get_policies(self._c, None, None, None, 0))         # the nodes going in bound the nodes coming out
+        if n < 0:                                                                    # none, or stale: the call says which
+            n = 0
+        return self._refined_many(self._n_policies("bg"), n, lambda off, st, cost, xy, oid, par, leaf, cap: self._l.porrt_bg_refine_policies(
+            self._c, int(n_iterations), off, st, cost, xy, oid, par, leaf, cap))
+
+    def mm_refine_policies(self, n_iterations):
+        """the same for the policies of the last mm_extract_policies (porrt_mm_refine_policies)"""
+        n = int(self._l.porrt_mm_get_policies(self._c, None, None, None, None, 0))
+        if n < 0:
+            n = 0
+        return self._refined_many(self._n_policies("mm"), n, lambda off, st, cost, xy, oid, par, leaf, cap: self._l.porrt_mm_refine_policies(
+            self._c, int(n_iterations), off, st, cost, xy, oid, par, leaf, cap))
+
+    def _n_policies(self, which):
+        """queries of the last extract_policies ("bg") / mm_extract_policies ("mm") of this engine; 0 before the first"""
+        return getattr(self, "_n_pol", {}).get(which, 0)
+
+    def refine_policies_explicit(self, policies, beliefs, n_iterations):
+        """the same on policies given as arrays, checked on this context's raster (porrt_refine_policies): policies is a list of
+        (xy [k, 2], parents (within the policy, -1 for its row 0), original ids, belief rows); an empty policy has status 1"""
+        bel = _f64(beliefs).reshape(len(beliefs), -1)
+        n = len(policies)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        for q, pol in enumerate(policies):
+            off[q + 1] = off[q] + np.uint64(len(pol[1]))
+        total = int(off[n])
+        cat = lambda i, dt, tail=(): (np.ascontiguousarray(np.concatenate([np.asarray(pol[i], dtype=dt).reshape((-1,) + tail) for pol in policies]))
+                                      if total else np.zeros((1,) + tail, dtype=dt))
+        xy, par, oid, row = cat(0, np.float64, (2,)), cat(1, np.int64), cat(2, np.uint64), cat(3, np.uint32)
+        return self._refined_many(n, total, lambda roff, st, cost, oxy, ooid, opar, oleaf, cap: self._l.porrt_refine_policies(
+            self._c, n, off, xy, par, oid, row, bel, bel.shape[0], bel.shape[1], int(n_iterations), roff, st, cost, oxy, ooid, opar, oleaf, cap))
+
+    def refine_policies_info(self):
+        """porrt_refine_policies_info of the last batch refinement: policies, ok, pieces, shortcut_pieces, nodes, distinct_lengths,
+        ms_device (the shortcut launch), ms_wall"""
+        i = RefinePoliciesInfo()
+        self._chk(self._l.porrt_refine_policies_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in RefinePoliciesInfo._fields_}
 
     def refine_info(self):
         a, b = C.c_double(0), C.c_double(0)
