@@ -248,9 +248,12 @@ uint64_t porrt_bg_get_dp_sweep_rows(const porrt_ctx *ctx);
  * belief node 0.  Policy node k (in Policy::add_node order; node 0 is the root) has original_node_id original_ids[k],
  * parent parents[k] (-1 for the root) and is a leaf (expected cost 0) iff is_leaf[k]; its state and belief follow from
  * the id (graph node id / n_beliefs, belief id % n_beliefs).  Returns the number of policy nodes; the arrays are filled
- * when cap holds them (call with cap 0 to size them).  *expected_costs = policy.expected_costs.  The walk is
- * sequential and small: host code, reading one row of the device graph per step.  Error when the root has no finite
- * expected cost (the reference would not terminate). */
+ * when cap holds them (call with cap 0 to size them).  *expected_costs = policy.expected_costs.  The walk runs on the
+ * device as porrt_bg_extract_policies with the one start 0 (into a result of its own: what porrt_bg_get_policies and
+ * porrt_policies_info hand out stays the last batched call's), up to 2^24 policy nodes whatever option
+ * "policy_max_nodes" says.  PORRT_ERR_INVALID when the root has no finite expected cost or the walk returns to a belief
+ * node on its own path (the reference would not terminate) or an assertion of the reference fails; PORRT_ERR_CAPACITY
+ * beyond 2^24 policy nodes or 65535 children of one node. */
 int64_t  porrt_bg_extract_policy(porrt_ctx *ctx, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap, double *expected_costs);
 /* conditional_dijkstra on an explicit belief graph given as host arrays (the form of the reference's own tests,
  * belief_graph.rs:502-567): node i has state xy[2i..], belief vector beliefs[belief_row[i]], type types[i]
@@ -325,9 +328,10 @@ int      porrt_policies_info(const porrt_ctx *ctx, struct porrt_policies_info *o
  * was regrown, the belief graph rebuilt or the expected costs recomputed since).  Refined node k has state xy[2k..], original id
  * original_ids[k] (that of the policy node it came from), parent parents[k] (-1 for the root and for a piece start left unconnected
  * by the quirk) and is a leaf (no children) iff is_leaf[k].  Returns the number of nodes; the arrays and *expected_costs are filled
- * when cap holds them (call with cap 0 to size them: that call does no device work).  One upload, one launch (k_refine_shortcut,
- * one wave per piece of >= 3 nodes), one download on the context's stream.  n_iterations < 2^31; iterations x distinct piece
- * lengths <= 2^26. */
+ * when cap holds them (call with a smaller cap, 0 for one, to size them: that call does no device work and checks the parents
+ * alone).  It is porrt_bg_refine_policies' path with one policy and a result of its own (what porrt_refine_policies_info hands out
+ * stays the last batched call's): a raster fault is PORRT_ERR_RASTER, a piece whose nodes carry different beliefs
+ * PORRT_ERR_INVALID.  n_iterations < 2^31; iterations x distinct piece lengths <= 2^26. */
 int64_t  porrt_bg_refine_policy(porrt_ctx *ctx, uint64_t n_iterations, double *xy, uint64_t *original_ids, int64_t *parents,
                                 uint8_t *is_leaf, uint64_t cap, double *expected_costs);
 /* The same on a policy given as host arrays, checked on the context's raster with its world validities: node i has state xy[2i..],

@@ -406,21 +406,11 @@ struct porrt_ctx {
     uint64_t raster_gen = 1, cls_host_gen = 0, refine_raster_gen = 0;      // set_grid / set_zones; the host classes and the refiner's copy
     bool refine_raster_table = false;      //   (with or without its summed-area table)
     void classify_raster();
-    GrowScratch refine_scratch;            // slot 0: raster, slot 1: everything else of a call
-    hipEvent_t refine_ev[2] = {nullptr, nullptr};
-    double refine_total_s = 0, refine_device_s = 0;
+    GrowScratch refine_scratch;            // slot 0: raster, slots 2-4: a call's uploads, draws and answers
+    hipEvent_t refine_ev[2] = {nullptr, nullptr};      // the TAMP shortcut's (porrt_tamp.hpp)
+    double refine_total_s = 0, refine_device_s = 0;    // the last single call that filled its answer
     bool refine_done = false;
-    struct RefineOut {
-        std::vector<double> xy;
-        std::vector<uint64_t> original;
-        std::vector<int64_t> parent;
-        std::vector<uint8_t> leaf;
-        double cost = 0;
-    };
-    int64_t refine(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief,
-                   const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
-                   RefineOut &out);
-    // ---- the same for many policies in one call (porrt_refine_batch.hpp): refine_scratch slots 2-4, state of its own
+    // ---- one policy or many in one call (porrt_refine_batch.hpp).  refp_info / refp_done: the last BATCHED call's
     struct porrt_refine_policies_info refp_info = {};
     bool refp_done = false;
     bool opt_refine_short_lds = true;      // "refine_short_lds": pieces of <= kRefineShortLdsNodes nodes in a launch of their own with the small LDS array (0: one launch)
@@ -429,7 +419,10 @@ struct porrt_ctx {
     int64_t refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
                             const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
                             uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
-                            int64_t *out_parents, uint8_t *out_leaf, uint64_t cap);
+                            int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, struct porrt_refine_policies_info *own_info);
+    int64_t refine_policy(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief, const double *beliefs,
+                          uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, double *out_xy, uint64_t *out_original,
+                          int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, double *expected_cost);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
     GrowScratch prm_paths_scratch;         // plan_path, one pair or many: device buffers (rows of costs, dirty flags, queries), kept across calls
@@ -1863,17 +1856,8 @@ int porrt_ctx::compute_expected_costs() {
 int porrt_ctx::extract_policy() {
     if (!bg.valid || !dp.valid || bg_graph_tag != results_tag) { set_err("extract_policy: compute the expected costs first (porrt_bg_compute_expected_costs)"); return PORRT_ERR_INVALID; }
     HIPCHK(hipSetDevice(device));
-    const BeliefSpace &bs = bg.cache.space;
-    const size_t B = bg.B;
-    auto belief_of = [B](uint64_t i) { return (uint32_t)(i % B); };
-    auto p_of = [&bs, B](uint64_t parent, uint64_t child) {          // transition_probability (common.rs:187-190)
-        const double *pb = bs.at(parent % B), *cb = bs.at(child % B);
-        double s = 0.0;
-        for (uint32_t w = 0; w < bs.nw; ++w) s = s + (cb[w] > 0.0 ? pb[w] : 0.0);
-        return s;
-    };
     std::string e;
-    int r = dp_extract_policy(dp, true, belief_of, p_of, stream, e);
+    const int r = pol_extract_root(policies_scratch, dp, true, nullptr, stream, e);
     if (r) set_err(e);
     else { pol_tag = results_tag; pol_stamp = bg_stamp; }
     return r;
@@ -1906,7 +1890,7 @@ int64_t porrt_ctx::extract_policies(const uint64_t *starts, uint64_t n, uint64_t
     }
     HIPCHK(hipSetDevice(device));
     std::string e;
-    const int r = pol_extract(policies_scratch, dp.last, true, nullptr, starts, n, opt_policy_max_nodes, stream, policies, e);
+    const int r = pol_extract(policies_scratch, dp.last, true, nullptr, starts, n, opt_policy_max_nodes, 0, stream, policies, e);
     if (r) { set_err(e); return r; }
     if (!e.empty()) set_err(e);
     policies.tag = results_tag; policies.stamp = bg_stamp;
@@ -1915,142 +1899,21 @@ int64_t porrt_ctx::extract_policies(const uint64_t *starts, uint64_t n, uint64_t
     return policies_copy_out(policies, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
 }
 
-// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of a policy given as host arrays: node k
-// has state xy[2k..], parent parents[k] (-1 for the root; children in ascending id order), original id original[k] (passed through)
-// and belief row belief[k] of beliefs (n_rows x nw) with compatibility bits compat[row].  Decomposition, draws and recomposition on
-// the host; the shortcuts of all pieces in one launch (k_refine_shortcut, porrt_refine.hpp): one upload, one launch, one download.
-// Returns the number of nodes of the refined policy; with run = false only that (no device work).
-int64_t porrt_ctx::refine(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief,
-                          const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, bool run,
-                          RefineOut &out) {
-    const double t0 = now_s();
-    if (n == 0 || n >= (1ull << 31) || parents[0] != -1) { set_err("refine_policy: a policy of 1 .. 2^31 nodes whose node 0 is the root"); return PORRT_ERR_INVALID; }
-    for (uint64_t k = 0; k < n; ++k) {
-        if (belief[k] >= n_rows) { set_err("refine_policy: a belief row out of range"); return PORRT_ERR_INVALID; }
-        if (k && (parents[k] < 0 || (uint64_t)parents[k] >= n || (uint64_t)parents[k] == k)) { set_err("refine_policy: a parent out of range"); return PORRT_ERR_INVALID; }
-    }
-    if (n_iter >= (1ull << 31)) { set_err("refine_policy: at most 2^31 - 1 iterations"); return PORRT_ERR_INVALID; }
-    std::vector<std::vector<uint32_t>> pieces, skeleton;
-    refine_decompose(n, parents, pieces, skeleton);
-    for (const auto &pc : pieces)                     // decompose: assert_eq!(belief_state of the piece's first node, of this node)
-        for (uint32_t id : pc)
-            if (belief[id] != belief[pc[0]] && std::memcmp(beliefs + (size_t)belief[id] * nw, beliefs + (size_t)belief[pc[0]] * nw, nw * sizeof(double))) {
-                set_err("refine_policy: a piece whose nodes carry different beliefs (the reference asserts, common.rs:102)");
-                return PORRT_ERR_INVALID;
-            }
-    std::vector<uint32_t> src;
-    refine_recompose(pieces, skeleton, src, out.parent, out.leaf);
-    if (!run) return (int64_t)src.size();
-    if (!has_grid) { set_err("refine_policy: the refiner checks transitions on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
-    HIPCHK(hipSetDevice(device));
-    // piece states in path order, the long pieces' descriptors, one table of draws per distinct length
-    std::vector<double> px, py;
-    std::vector<RefinePiece> longs;
-    std::vector<std::pair<uint32_t, uint32_t>> len_at;          // (length, first draw)
-    std::unordered_map<uint32_t, uint32_t> draws_of;
-    for (const auto &pc : pieces)
-        for (uint32_t id : pc) { px.push_back(xy[2 * id]); py.push_back(xy[2 * id + 1]); }
-    for (size_t i = 0, off = 0; i < pieces.size(); off += pieces[i].size(), ++i) {
-        const uint32_t len = (uint32_t)pieces[i].size();
-        if (len <= 2 || n_iter == 0) continue;                   // partial_shortcut: nothing to do, nothing drawn
-        auto found = draws_of.find(len);
-        uint32_t at = found == draws_of.end() ? 0xFFFFFFFFu : found->second;
-        if (at == 0xFFFFFFFFu) {
-            if ((len_at.size() + 1) * n_iter > (1ull << 26)) { set_err("refine_policy: more than 2^26 draws (iterations x distinct piece lengths)"); return PORRT_ERR_CAPACITY; }
-            at = (uint32_t)(len_at.size() * n_iter);
-            len_at.push_back({len, at});
-            draws_of[len] = at;
-        }
-        longs.push_back({(uint32_t)off, len, at, belief[pieces[i][0]]});
-    }
-    refine_device_s = 0.0;
-    if (!longs.empty()) {
-        // the raster (classes and summed-area table, build_cls's tables) lives in a slot of its own, uploaded once per raster
-        classify_raster();
-        uint8_t *d_raster = nullptr;
-        HIPCHK(refine_scratch.get(0, d_raster, cls.size()));
-        if (refine_raster_gen != raster_gen) {
-            HIPCHK(hipMemcpyAsync(d_raster, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
-            refine_raster_gen = raster_gen;
-        }
-        RunConst g;
-        memset(&g, 0, sizeof g);
-        g.cls = d_raster; g.clr = d_raster + (size_t)W * H; g.sat = opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(W, H)) : nullptr;
-        g.W = W; g.H = H; g.low0 = low[0]; g.low1 = low[1]; g.ppm = ppm; g.domain = domain; g.has_grid = has_grid;
-        g.n_validities = n_validities;
-        for (int i = 0; i < n_validities; ++i) g.validities[i] = validities[i];
-        // one staging area: RunConst | pieces | compat | draws | x | y | error word
-        auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        const size_t nd = len_at.size() * n_iter, ns = px.size();
-        const size_t o_pc = up8(sizeof(RunConst)), o_cp = o_pc + up8(longs.size() * sizeof(RefinePiece)), o_dr = o_cp + up8((size_t)n_rows * 8),
-                     o_x = o_dr + up8(nd * sizeof(uint2)), o_y = o_x + ns * 8, o_err = o_y + ns * 8, bytes = o_err + 16;
-        std::vector<uint8_t> stage(bytes, 0);
-        memcpy(stage.data(), &g, sizeof g);
-        memcpy(stage.data() + o_pc, longs.data(), longs.size() * sizeof(RefinePiece));
-        memcpy(stage.data() + o_cp, compat, (size_t)n_rows * 8);
-        uint2 *dr = (uint2 *)(stage.data() + o_dr);
-        for (const auto &la : len_at) {                          // DiscreteSampler::new() per piece (pto_policy_refiner.rs:172-175)
-            Pcg64 rng;
-            rng.seed_from_u64(0);
-            const uint64_t L = la.first;
-            for (uint64_t it = 0; it < n_iter; ++it) {
-                const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
-                const uint32_t s = (uint32_t)rng.gen_range_usize(L - 2);
-                const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(L - s - 2);
-                dr[la.second + it] = make_uint2(s | (joint << 31), e);
-            }
-        }
-        memcpy(stage.data() + o_x, px.data(), ns * 8);
-        memcpy(stage.data() + o_y, py.data(), ns * 8);
-        uint8_t *d = nullptr;
-        HIPCHK(refine_scratch.get(1, d, bytes));
-        for (int k = 0; k < 2; ++k) if (!refine_ev[k]) HIPCHK(hipEventCreate(&refine_ev[k]));
-        RefineConst rc{};
-        rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = (const unsigned long long *)(d + o_cp);
-        rc.draws = (const uint2 *)(d + o_dr); rc.x = (double *)(d + o_x); rc.y = (double *)(d + o_y); rc.err = (uint32_t *)(d + o_err);
-        rc.n_pieces = (uint32_t)longs.size(); rc.n_iter = (uint32_t)n_iter;
-        HIPCHK(hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipEventRecord(refine_ev[0], stream));
-        hipLaunchKernelGGL(k_refine_shortcut, dim3(rc.n_pieces), dim3(64), 0, stream, rc);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(refine_ev[1], stream));
-        HIPCHK(hipMemcpyAsync(stage.data() + o_x, d + o_x, bytes - o_x, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, refine_ev[0], refine_ev[1]));
-        refine_device_s = 1e-3 * (double)ms;
-        uint32_t err = 0;
-        memcpy(&err, stage.data() + o_err, 4);
-        if (err) { set_err("refine_policy: a shortcut reads outside the raster, a door pixel without zone id or two zones on one segment (the reference panics)"); return PORRT_ERR_RASTER; }
-        memcpy(px.data(), stage.data() + o_x, ns * 8);
-        memcpy(py.data(), stage.data() + o_y, ns * 8);
-    }
-    // recompose: the refined states in piece order (px / py are laid out in exactly that order), then the expected cost
-    const size_t m = src.size();
-    out.xy.resize(2 * m);
-    out.original.resize(m);
-    for (size_t k = 0; k < m; ++k) { out.xy[2 * k] = px[k]; out.xy[2 * k + 1] = py[k]; out.original[k] = original[src[k]]; }
-    out.cost = refine_expected_cost(out.parent, out.xy, [&](uint32_t a, uint32_t b) {       // transition_probability (common.rs:187-190)
-        const double *pb = beliefs + (size_t)belief[src[a]] * nw, *cb = beliefs + (size_t)belief[src[b]] * nw;
-        double sum = 0.0;
-        for (uint32_t w = 0; w < nw; ++w) sum = sum + (cb[w] > 0.0 ? pb[w] : 0.0);
-        return sum;
-    });
-    refine_total_s = now_s() - t0;
-    refine_done = true;
-    return (int64_t)m;
-}
-
-// refine_solution(PartialShortCut(n_iter)) of n policies laid end to end (policy q = rows pol_off[q] .. pol_off[q + 1], parents within
-// the policy), everything on the device (porrt_refine_batch.hpp): one upload, the decomposition, one small download (per policy its
-// counts, per piece of >= 3 nodes its length), the draws of every distinct length made here as refine() makes them and uploaded with
-// the launch order (longest piece first), the shortcuts of all pieces in one launch, offsets, recomposition with the expected costs,
-// one download.  cap = 0 launches no shortcut kernel.  Returns the refined nodes of the policies with status 0.
+// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of n policies laid end to end (policy q =
+// rows pol_off[q] .. pol_off[q + 1]): node k has state xy[2k..], parent parents[k] within its policy (-1 for its row 0, the root;
+// children in ascending id order), original id original[k] (passed through) and belief row belief[k] of beliefs (n_rows x nw) with
+// compatibility bits compat[row].  Everything on the device (porrt_refine_batch.hpp): one upload, the decomposition, one small
+// download (per policy its counts, per piece of >= 3 nodes its length), one table of draws per distinct length (a fresh Pcg64 of seed 0
+// each: the draws do not depend on the commits) uploaded with the launch order (longest piece first), the shortcuts of all pieces in
+// one launch, offsets, recomposition with the expected costs, one download.  cap = 0 launches no shortcut kernel.  own_info: where the
+// single call (refine_policy below) wants the counts and times; nullptr = refp_info / refp_done, what porrt_refine_policies_info hands out.
+// Returns the refined nodes of the policies with status 0.
 int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
                                    const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
                                    uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
-                                   int64_t *out_parents, uint8_t *out_leaf, uint64_t cap) {
+                                   int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, struct porrt_refine_policies_info *own_info) {
     const double t0 = now_s();
+    struct porrt_refine_policies_info &info = own_info ? *own_info : refp_info;
     const std::string W_ = std::string(who) + ": ";
     if (!pol_off || !ref_off || (n && (!status || !expected_costs))) { set_err(W_ + "pol_off, ref_off, status and expected_costs"); return PORRT_ERR_INVALID; }
     if (n >= (1ull << 31) || pol_off[0] != 0) { set_err(W_ + "fewer than 2^31 policies, pol_off[0] = 0"); return PORRT_ERR_INVALID; }
@@ -2082,15 +1945,15 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
             }
         }
     }
-    refp_done = false;
-    refp_info = {};
-    refp_info.policies = n;
+    if (!own_info) refp_done = false;
+    info = {};
+    info.policies = n;
     ref_off[0] = 0;
     if (T == 0) {                                                    // nothing but empty policies: no device work
         for (uint64_t q = 0; q < n; ++q) { ref_off[q + 1] = 0; status[q] = 1; expected_costs[q] = 0.0; }
         if (n) set_err(W_ + "policy 0: no policy to refine");
-        refp_info.ms_wall = 1e3 * (now_s() - t0);
-        refp_done = true;
+        info.ms_wall = 1e3 * (now_s() - t0);
+        if (!own_info) refp_done = true;
         return 0;
     }
     HIPCHK(hipSetDevice(device));
@@ -2150,7 +2013,7 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
     for (uint64_t q = 0; q < n; ++q) {
         if (rec[q].status) continue;
         M += rec[q].rows;
-        refp_info.pieces += rec[q].pieces;
+        info.pieces += rec[q].pieces;
         for (uint32_t j = 0; j < rec[q].longs; ++j) {
             const uint64_t row = pol_off[q] / 3 + j;
             keys.push_back((uint64_t)long_len[row] << 32 | row);
@@ -2163,7 +2026,7 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
             if (shortcuts && (len_at.size() + 1) * n_iter > (1ull << 26)) { set_err(W_ + "more than 2^26 draws (iterations x distinct piece lengths)"); return PORRT_ERR_CAPACITY; }
             len_at.push_back({(uint32_t)(k >> 32), (uint32_t)(len_at.size() * n_iter)});
         }
-    refp_info.distinct_lengths = len_at.size();
+    info.distinct_lengths = len_at.size();
     double ms_device = 0.0;
     if (shortcuts && !keys.empty()) {
         if (!has_grid) { set_err(W_ + "the refiner checks transitions on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
@@ -2209,7 +2072,7 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(refp_ev[1], stream));
-        refp_info.shortcut_pieces = keys.size();
+        info.shortcut_pieces = keys.size();
     }
     // offsets, recomposition and costs; the answers packed in one block: ref_off | cost | status | xy | original ids | parents | leafs
     const size_t r_off = 0, r_cost = r_off + up16((n + 1) * 8), r_st = r_cost + up16(n * 8), r_xy = r_st + up16(n), r_or = r_xy + up16(M * 16),
@@ -2225,7 +2088,7 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
     std::vector<uint8_t> third(bytes3);
     HIPCHK(hipMemcpyAsync(third.data(), d3, bytes3, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    if (refp_info.shortcut_pieces) {
+    if (info.shortcut_pieces) {
         float ms = 0.0f;
         HIPCHK(hipEventElapsedTime(&ms, refp_ev[0], refp_ev[1]));
         ms_device = (double)ms;
@@ -2240,7 +2103,7 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
         if (out_parents) memcpy(out_parents, third.data() + r_pa, total * 8);
         if (out_leaf) memcpy(out_leaf, third.data() + r_lf, total);
     }
-    for (uint64_t q = 0; q < n; ++q) refp_info.ok += status[q] == 0;
+    for (uint64_t q = 0; q < n; ++q) info.ok += status[q] == 0;
     for (uint64_t q = 0; q < n; ++q)
         if (status[q]) {
             static const char *const what[4] = {"", "no policy to refine", "a shortcut reads outside the raster, a door pixel without zone id or two zones on one segment (the reference panics)",
@@ -2248,11 +2111,55 @@ int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *
             set_err(W_ + "policy " + std::to_string(q) + ": " + what[status[q] & 3]);
             break;
         }
-    refp_info.nodes = total;
-    refp_info.ms_device = ms_device;
-    refp_info.ms_wall = 1e3 * (now_s() - t0);
-    refp_done = true;
+    info.nodes = total;
+    info.ms_device = ms_device;
+    info.ms_wall = 1e3 * (now_s() - t0);
+    if (!own_info) refp_done = true;
     return (int64_t)total;
+}
+
+// Rows of a refined policy: decompose reaches a node iff its chain of parents ends at node 0, and recompose gives every node reached
+// one row (a piece left unconnected by the one-node quirk keeps its rows).  -1: parents that refine_policies refuses.
+static int64_t refine_rows(uint64_t n, const int64_t *parents) {
+    if (n && parents[0] != -1) return -1;
+    std::vector<uint8_t> mark(n, 0);                                 // 1 reached, 2 not (or being walked: a cycle is not reached)
+    std::vector<uint64_t> chain;
+    int64_t rows = n ? 1 : 0;
+    if (n) mark[0] = 1;
+    for (uint64_t k = 1; k < n; ++k) {
+        chain.clear();
+        uint64_t j = k;
+        for (; !mark[j]; j = (uint64_t)parents[j]) {
+            if (parents[j] < 0 || (uint64_t)parents[j] >= n || (uint64_t)parents[j] == j) return -1;
+            mark[j] = 2;
+            chain.push_back(j);
+        }
+        if (mark[j] == 1) { for (uint64_t c : chain) mark[c] = 1; rows += (int64_t)chain.size(); }
+    }
+    return rows;
+}
+
+// One policy: a batch of one (refine_policies) with status and info block of its own -- refp_info / refp_done, the last BATCHED call's,
+// are not touched.  Returns the number of nodes of the refined policy always and fills the arrays when cap holds it; a smaller cap is the
+// sizing form, answered on the host (no device work; the beliefs are checked by the call that fills).
+int64_t porrt_ctx::refine_policy(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief, const double *beliefs,
+                                 uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, double *out_xy, uint64_t *out_original,
+                                 int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, double *expected_cost) {
+    const int64_t rows = refine_rows(n, parents);
+    if (rows >= 0 && cap < (uint64_t)rows) return rows;
+    const uint64_t pol_off[2] = {0, n};
+    uint64_t ref_off[2] = {0, 0};
+    uint8_t status = 0;
+    double cost = 0.0;
+    struct porrt_refine_policies_info info;
+    const int64_t m = refine_policies("refine_policy", 1, pol_off, xy, parents, original, belief, beliefs, n_rows, nw, compat, n_iter, ref_off, &status, &cost,
+                                      out_xy, out_original, out_parents, out_leaf, cap, &info);
+    if (m < 0) return m;
+    if (status) return status == 2 ? PORRT_ERR_RASTER : PORRT_ERR_INVALID;      // (refine_policies has set the message)
+    if (expected_cost) *expected_cost = cost;
+    refine_total_s = 1e-3 * info.ms_wall; refine_device_s = 1e-3 * info.ms_device;
+    refine_done = true;
+    return m;
 }
 
 // PRM::init + PRM::grow_graph (prm.rs:33-109); see porrt_prm.hpp.
@@ -2873,10 +2780,8 @@ int porrt_ctx::mm_extract_policy() {
     }
     HIPCHK(hipSetDevice(device));
     const double t0 = now_s();
-    auto belief_of = [&s](uint64_t i) { return s.mode_bid[mm_mode_of(s, i)]; };
-    auto p_of = [&s](uint64_t parent, uint64_t child) { return mm_transition_probability(s, mm_mode_of(s, parent), mm_mode_of(s, child)); };
     std::string e;
-    const int r = dp_extract_policy(s.dp, false, belief_of, p_of, stream, e);
+    const int r = pol_extract_root(policies_scratch, s.dp, false, s.d_bid, stream, e);
     if (r) { set_err(e); return r; }
     const size_t n = s.dp.pol_original.size();
     s.pol_xy.resize(2 * n);
@@ -2903,7 +2808,7 @@ int64_t porrt_ctx::mm_extract_policies(const uint64_t *starts, uint64_t n, uint6
     }
     HIPCHK(hipSetDevice(device));
     std::string e;
-    const int r = pol_extract(policies_scratch, s.dp.last, false, s.d_bid, starts, n, opt_policy_max_nodes, stream, mm_policies, e);
+    const int r = pol_extract(policies_scratch, s.dp.last, false, s.d_bid, starts, n, opt_policy_max_nodes, 0, stream, mm_policies, e);
     if (r) { set_err(e); return r; }
     if (!e.empty()) set_err(e);
     const size_t total = mm_policies.original.size();
@@ -4588,20 +4493,22 @@ int64_t porrt_extract_policies(int device, uint64_t n_nodes, const double *xy, c
         GrowScratch sc;
         PoliciesResult res;
         std::string err;
-        int64_t r = pol_extract(sc, c, false, d_bid, starts, n, policy_max_nodes, nullptr, res, err);
+        int64_t r = pol_extract(sc, c, false, d_bid, starts, n, policy_max_nodes, 0, nullptr, res, err);
         if (r == PORRT_OK) r = policies_copy_out(res, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
         return r;
     } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 
-// copies a refined policy into the caller's arrays when cap holds it
-static void refine_copy_out(const porrt_ctx::RefineOut &o, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *expected_costs) {
-    const size_t m = o.parent.size();
-    if (xy) memcpy(xy, o.xy.data(), 2 * m * sizeof(double));
-    if (original_ids) memcpy(original_ids, o.original.data(), m * sizeof(uint64_t));
-    if (parents) memcpy(parents, o.parent.data(), m * sizeof(int64_t));
-    if (is_leaf) memcpy(is_leaf, o.leaf.data(), m);
-    if (expected_costs) *expected_costs = o.cost;
+// compute_compatibility (common.rs:266-276) of every belief row with the context's world validities
+static std::vector<unsigned long long> refine_compat_rows(const porrt_ctx *c, const double *beliefs, uint32_t n_rows, uint32_t nw) {
+    std::vector<unsigned long long> compat(n_rows, 0ull);
+    for (uint32_t b = 0; b < n_rows; ++b)
+        for (int v = 0; v < c->n_validities; ++v) {
+            bool ok = true;
+            for (uint32_t w = 0; w < nw && ok; ++w) ok = !(beliefs[(size_t)b * nw + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
+            if (ok) compat[b] |= 1ull << v;
+        }
+    return compat;
 }
 
 // PTOPolicyRefiner::refine_solution(PartialShortCut(n_iterations)) of the policy the last porrt_bg_extract_policy handed out
@@ -4624,15 +4531,8 @@ int64_t porrt_bg_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, 
             pxy[2 * k] = c->h_nx[node]; pxy[2 * k + 1] = c->h_ny[node];
             belief[k] = (uint32_t)(id % B);
         }
-        porrt_ctx::RefineOut o;
-        const int64_t m = c->refine(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(),
-                                    (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, false, o);
-        if (m < 0 || cap < (uint64_t)m) return (int)m;        // sizing: no device work
-        const int64_t m2 = c->refine(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(),
-                                     (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, true, o);
-        if (m2 < 0) return (int)m2;
-        refine_copy_out(o, xy, original_ids, parents, is_leaf, expected_costs);
-        return (int)m2;
+        return (int)c->refine_policy(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(), (uint32_t)B, bs.nw,
+                                     c->bg.cache.compat.data(), n_iterations, xy, original_ids, parents, is_leaf, cap, expected_costs);
     });
 }
 
@@ -4643,20 +4543,9 @@ int64_t porrt_refine_policy(porrt_ctx *c, uint64_t n, const double *xy, const in
     if (!c || !n || !xy || !parents || !original_ids || !belief_row || !beliefs || !n_belief_rows) return PORRT_ERR_INVALID;
     return abi_guard([&]() -> int {
         if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policy: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
-        std::vector<unsigned long long> compat(n_belief_rows, 0ull);     // compute_compatibility (common.rs:266-276)
-        for (uint32_t b = 0; b < n_belief_rows; ++b)
-            for (int v = 0; v < c->n_validities; ++v) {
-                bool ok = true;
-                for (uint32_t w = 0; w < n_worlds && ok; ++w) ok = !(beliefs[(size_t)b * n_worlds + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
-                if (ok) compat[b] |= 1ull << v;
-            }
-        porrt_ctx::RefineOut o;
-        const int64_t m = c->refine(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, false, o);
-        if (m < 0 || cap < (uint64_t)m) return (int)m;
-        const int64_t m2 = c->refine(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, true, o);
-        if (m2 < 0) return (int)m2;
-        refine_copy_out(o, out_xy, out_original_ids, out_parents, out_is_leaf, expected_costs);
-        return (int)m2;
+        const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
+        return (int)c->refine_policy(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, out_xy,
+                                     out_original_ids, out_parents, out_is_leaf, cap, expected_costs);
     });
 }
 
@@ -4668,17 +4557,6 @@ int porrt_bg_get_refine_info(const porrt_ctx *c, double *total_s, double *device
 }
 
 // ---- refinement of many policies in one call (porrt_refine_batch.hpp)
-// compute_compatibility (common.rs:266-276) of every belief row with the context's world validities
-static std::vector<unsigned long long> refine_compat_rows(const porrt_ctx *c, const double *beliefs, uint32_t n_rows, uint32_t nw) {
-    std::vector<unsigned long long> compat(n_rows, 0ull);
-    for (uint32_t b = 0; b < n_rows; ++b)
-        for (int v = 0; v < c->n_validities; ++v) {
-            bool ok = true;
-            for (uint32_t w = 0; w < nw && ok; ++w) ok = !(beliefs[(size_t)b * nw + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
-            if (ok) compat[b] |= 1ull << v;
-        }
-    return compat;
-}
 int64_t porrt_bg_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
                                  uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
@@ -4703,7 +4581,7 @@ int64_t porrt_bg_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *
         }
         return c->refine_policies("bg_refine_policies", n, res.off.data(), pxy.data(), res.parent.data(), res.original.data(), belief.data(), bs.vec.data(),
                                   (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents,
-                                  is_leaf, cap);
+                                  is_leaf, cap, nullptr);
     } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 int64_t porrt_mm_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
@@ -4723,7 +4601,7 @@ int64_t porrt_mm_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *
         for (uint64_t k = 0; k < T; ++k) row[k] = mm_mode_of(s, res.original[k]);
         const std::vector<unsigned long long> compat = refine_compat_rows(c, s.beliefs.data(), M, nw);
         return c->refine_policies("mm_refine_policies", n, res.off.data(), res.xy.data(), res.parent.data(), res.original.data(), row.data(), s.beliefs.data(),
-                                  M, nw, compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap);
+                                  M, nw, compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap, nullptr);
     } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 int64_t porrt_refine_policies(porrt_ctx *c, uint64_t n_policies, const uint64_t *pol_off, const double *xy, const int64_t *parents,
@@ -4736,7 +4614,7 @@ int64_t porrt_refine_policies(porrt_ctx *c, uint64_t n_policies, const uint64_t 
         if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policies: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
         const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
         return c->refine_policies("refine_policies", n_policies, pol_off, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds,
-                                  compat.data(), n_iterations, ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap);
+                                  compat.data(), n_iterations, ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap, nullptr);
     } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 int porrt_refine_policies_info(const porrt_ctx *c, struct porrt_refine_policies_info *out) {
@@ -4814,23 +4692,11 @@ int64_t porrt_mm_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, 
         const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
         std::vector<uint32_t> row(n);
         for (uint64_t k = 0; k < n; ++k) row[k] = mm_mode_of(s, s.dp.pol_original[k]);
-        std::vector<unsigned long long> compat(M, 0ull);              // compute_compatibility (common.rs:266-276) of every mode's belief
-        for (uint32_t m = 0; m < M; ++m)
-            for (int v = 0; v < c->n_validities; ++v) {
-                bool ok = true;
-                for (uint32_t w = 0; w < nw && ok; ++w) ok = !(s.beliefs[(size_t)m * nw + w] > 0.0) || ((c->validities[v] >> w) & 1ull);
-                if (ok) compat[m] |= 1ull << v;
-            }
-        porrt_ctx::RefineOut o;
-        const int64_t m = c->refine(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
-                                    compat.data(), n_iterations, false, o);
-        if (m < 0 || cap < (uint64_t)m) return (int)m;                // sizing: no device work
-        const int64_t m2 = c->refine(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
-                                     compat.data(), n_iterations, true, o);
-        if (m2 < 0) return (int)m2;
-        s.t_refine = c->refine_total_s; s.t_refine_device = c->refine_device_s;
-        refine_copy_out(o, xy, ids, parents, is_leaf, expected_cost);
-        return (int)m2;
+        const std::vector<unsigned long long> compat = refine_compat_rows(c, s.beliefs.data(), M, nw);
+        const int64_t m = c->refine_policy(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
+                                           compat.data(), n_iterations, xy, ids, parents, is_leaf, cap, expected_cost);
+        if (m >= 0 && cap >= (uint64_t)m) { s.t_refine = c->refine_total_s; s.t_refine_device = c->refine_device_s; }
+        return (int)m;
     });
 }
 // MapShelfDomainTampPRM::plan (:310-326): grow, belief graph, expected costs, policy; returns the policy's node count

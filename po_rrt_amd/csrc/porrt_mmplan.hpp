@@ -280,14 +280,6 @@ struct MmPlanState {
     void release() { valid = false; dp.release(); costs_gen = policy_gen = ~0ull; }
 };
 
-// transition_probability of two rows of the modes' beliefs (common.rs:187-190)
-static inline double mm_transition_probability(const MmPlanState &s, uint32_t parent_mode, uint32_t child_mode) {
-    const double *pb = s.beliefs.data() + (size_t)parent_mode * s.nw, *cb = s.beliefs.data() + (size_t)child_mode * s.nw;
-    double sum = 0.0;
-    for (uint32_t w = 0; w < s.nw; ++w) sum = sum + (cb[w] > 0.0 ? pb[w] : 0.0);
-    return sum;
-}
-
 static inline uint32_t mm_mode_of(const MmPlanState &s, uint64_t node) {
     return (uint32_t)(std::upper_bound(s.mode_off.begin(), s.mode_off.end(), (uint32_t)node) - s.mode_off.begin()) - 1;
 }

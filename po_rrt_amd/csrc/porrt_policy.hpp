@@ -1,5 +1,6 @@
 // porrt_policy.hpp -- extract_policy (src/belief_graph.rs:184-267) from many start belief nodes, walked on the device: one
-// wave per query, one call for all of them (porrt_bg_extract_policies, porrt_mm_extract_policies, porrt_extract_policies).
+// wave per query, one call for all of them (porrt_bg_extract_policies, porrt_mm_extract_policies, porrt_extract_policies).  The
+// single extraction from belief node 0 (porrt_bg_extract_policy, porrt_mm_extract_policy) is a call with that one start.
 //
 // The expected costs the sweeps of porrt_dp.hpp leave on the device are costs-to-goal of EVERY belief node, so the policy
 // from any of them is determined; nothing in the reference's walk needs the host.  Per popped (policy node, belief node):
@@ -187,11 +188,17 @@ struct PoliciesResult {
     struct porrt_policies_info info = {};
 };
 
+static const char *const kPolStatusText[5] = {"", "its expected cost is not finite: no policy from there",
+                                              "the walk returns to a belief node on its own path (zero-cost edges between nodes at one place); the reference does not terminate here",
+                                              "an assertion of the reference fails (p > 0.0, belief_graph.rs:250, or p * dist[best] <= dist[node], :261)",
+                                              "the policy exceeds policy_max_nodes, or a belief node has more than 65535 children"};
+
 // Walks the policies from starts[0 .. n) on the graph and costs of c (c.dist set; bid = clustering key per node, explicit layout only).
-// Sc: GrowScratch (slots 0-7 are used).  Fills everything of out but tag / stamp / xy / valid.
+// Sc: GrowScratch (slots 0-7 are used).  first_slice: the slice of the first round (0 = the pool shared out among the queries).
+// Fills everything of out but tag / stamp / xy / valid.
 template <class Sc>
 static int pol_extract(Sc &sc, const DpConst &c, bool implicit, const uint32_t *d_bid, const uint64_t *starts, uint64_t n, uint64_t max_nodes,
-                       hipStream_t s, PoliciesResult &out, std::string &err) {
+                       uint64_t first_slice, hipStream_t s, PoliciesResult &out, std::string &err) {
     const double t0 = bg_now();
     out.valid = false;
     out.off.assign(n + 1, 0); out.status.assign(n, 0); out.cost.assign(n, 0.0);
@@ -216,8 +223,8 @@ static int pol_extract(Sc &sc, const DpConst &c, bool implicit, const uint32_t *
     std::vector<unsigned long long> hoff;
     uint64_t slice = 0;
     while (!pending.empty()) {
-        // slice of this round: the pool shared out, at least kPolMinSlice, 16 times the last round's, never above max_nodes
-        const uint64_t share = kPolPoolNodes / pending.size();
+        // slice of this round: first_slice or the pool shared out, at least kPolMinSlice; 16 times the last round's; never above max_nodes
+        const uint64_t share = first_slice ? first_slice : kPolPoolNodes / pending.size();
         uint64_t want = slice ? slice * 16 : (share > kPolMinSlice ? share : kPolMinSlice);
         if (want > max_nodes) want = max_nodes;
         slice = want;
@@ -301,14 +308,33 @@ static int pol_extract(Sc &sc, const DpConst &c, bool implicit, const uint32_t *
     out.info.ms_wall = 1e3 * (bg_now() - t0);
     for (uint64_t q = 0; q < n; ++q)
         if (out.status[q]) {
-            static const char *const what[] = {"", "its expected cost is not finite: no policy from there",
-                                               "the walk returns to a belief node on its own path (zero-cost edges between nodes at one place); the reference does not terminate here",
-                                               "an assertion of the reference fails (p > 0.0, belief_graph.rs:250, or p * dist[best] <= dist[node], :261)",
-                                               "the policy exceeds policy_max_nodes, or a belief node has more than 65535 children"};
             err = "extract_policies: query " + std::to_string(q) + " (start " + std::to_string(starts[q]) + "), status " + std::to_string(out.status[q]) + ": " +
-                  what[out.status[q] <= 4 ? out.status[q] : 4];
+                  kPolStatusText[out.status[q] <= 4 ? out.status[q] : 4];
             break;
         }
+    return PORRT_OK;
+}
+
+// The single extraction (PTO::extract_policy, pto.rs:277-283): the policy from belief node 0 as a batch of one, into a result of its
+// own and from there into st.pol_*.  Its limit is kPolMaxNodesLimit policy nodes; the first walk gets kPolSingleSlice of them (a lone
+// query's share of the pool would be all of it), a longer policy is walked again as any query that outgrows its slice.
+constexpr uint64_t kPolSingleSlice = 512;
+template <class Sc>
+static int pol_extract_root(Sc &sc, DpState &st, bool implicit, const uint32_t *d_bid, hipStream_t s, std::string &err) {
+    const uint64_t root = 0;
+    PoliciesResult res;
+    const int r = pol_extract(sc, st.last, implicit, d_bid, &root, 1, kPolMaxNodesLimit, kPolSingleSlice, s, res, err);
+    if (r) return r;
+    const uint32_t status = res.status[0];
+    if (status) {
+        err = std::string("extract_policy: ") + (status == POL_NO_COST    ? "no policy from the root (its expected cost is not finite; the reference does not terminate here)"
+                                                 : status == POL_CAPACITY ? "more than 2^24 policy nodes, or a belief node with more than 65535 children"
+                                                                          : kPolStatusText[status]);
+        return status == POL_CAPACITY ? PORRT_ERR_CAPACITY : PORRT_ERR_INVALID;
+    }
+    err.clear();
+    st.pol_original = std::move(res.original); st.pol_parent = std::move(res.parent); st.pol_leaf = std::move(res.leaf);
+    st.have_policy = true;
     return PORRT_OK;
 }
 

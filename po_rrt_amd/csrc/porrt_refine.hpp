@@ -11,22 +11,28 @@
 // with the piece's belief (is_transition_valid, :395-423).  The draws never depend on the commits, so they are a function of
 // the piece length alone: the host makes them once per distinct length (engine Pcg64::gen_range_usize) and uploads them.
 //
-// Device (k_refine_shortcut): one wave per piece of >= 3 nodes, all pieces of a policy in one launch.  The iterations run in
+// Device (refine_shortcut_piece): one wave per piece of >= 3 nodes, all pieces of a call in one launch.  The iterations run in
 // order inside the wave; per iteration the lanes stride over [s, e), each forms its candidate and the next one, classifies the
 // two states and the segment with the growth's own state_class / traversed_class (summed-area table first), the verdict is
 // reduced across the wave (first rejected transition in path order: the reference's `&&` stops there, so a raster fault behind
-// it is never reached), and the lanes that own the nodes commit.  Piece states live in LDS up to kRefineLdsNodes nodes;
-// longer pieces work in place in global memory (the same code through a generic pointer).
+// it is never reached), and the lanes that own the nodes commit.  Piece states live in LDS up to kLds nodes; longer pieces work
+// in place in global memory (the same code through a generic pointer).
 //
-// The pieces are put back together on the host (recompose, :324-393) with the expected cost recursion of common.rs:131-154.
+// The pieces are put back together (recompose, :324-393) in piece order, nodes in path order: inside a piece each node is the child
+// of the one before, then the skeleton edges from the end of piece i to the start of each piece its last node's children start.  The
+// expected cost is the recursion of common.rs:131-154 from node 0: the sum over the children in ascending id order of
+// p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
 // Quirk kept from the reference: recompose records a piece's start with `if is_start .. else if is_end` (:348-366), so a
 // one-node piece has a start but no end.  When such a piece branches, its skeleton edges are never added: its successor
-// pieces keep no parent (parents = -1) and the one node becomes a leaf.
+// pieces keep no parent (parents = -1) and the one node becomes a leaf.  Nodes the walk from node 0 does not reach belong to no piece.
+//
+// This file holds what the shortcut of one piece needs, shared with the TAMP planner's path shortcut (k_tamp_shortcut,
+// porrt_tamp.hpp).  Decomposition, launch order, recomposition and expected costs are the kernels of porrt_refine_batch.hpp, one
+// policy or many: they are this specification's only implementation (the single calls are batches of one).
 #pragma once
 #include "porrt_device.hpp"
 
 #include <cmath>
-#include <deque>
 #include <string>
 #include <vector>
 
@@ -142,107 +148,7 @@ __device__ __forceinline__ void refine_shortcut_piece(const RefineConst &c, cons
     if (fault && lane == 0) atomicOr(err_word, ERR_RASTER);
 }
 
-template <bool kTamp>
-__device__ __forceinline__ void refine_shortcut_body(const RefineConst &c) {
-    refine_shortcut_piece<kTamp, kRefineLdsNodes>(c, c.pieces[blockIdx.x], c.err);
-}
-
-__global__ __launch_bounds__(64) void k_refine_shortcut(RefineConst c) { refine_shortcut_body<false>(c); }
-__global__ __launch_bounds__(64) void k_tamp_shortcut(RefineConst c) { refine_shortcut_body<true>(c); }
-
-// ------------------------------------------------------------------------------------------------ host side
-
-// Policy::decompose (common.rs:85-129) of a policy given by its parents (children order = ascending id, the order of
-// extract_policy's add_edge calls).  pieces[i] = policy node ids in path order; skeleton[i] = the pieces its last node's
-// children start.  Nodes the walk from node 0 does not reach belong to no piece.
-static inline void refine_decompose(uint64_t n, const int64_t *parents, std::vector<std::vector<uint32_t>> &pieces,
-                                    std::vector<std::vector<uint32_t>> &skeleton) {
-    std::vector<uint32_t> child_off(n + 1, 0), child_ids;
-    for (uint64_t k = 1; k < n; ++k) if (parents[k] >= 0) ++child_off[(size_t)parents[k] + 1];
-    for (uint64_t k = 0; k < n; ++k) child_off[k + 1] += child_off[k];
-    child_ids.resize(child_off[n]);
-    std::vector<uint32_t> fill(child_off.begin(), child_off.end() - 1);
-    for (uint64_t k = 1; k < n; ++k) if (parents[k] >= 0) child_ids[fill[(size_t)parents[k]]++] = (uint32_t)k;
-    pieces.clear(); skeleton.clear();
-    std::deque<uint32_t> fifo{0};
-    uint32_t n_pieces = 0;
-    while (!fifo.empty()) {
-        const uint32_t id = fifo.front();
-        fifo.pop_front();
-        std::vector<uint32_t> ids, successors;
-        for (uint32_t cur = id;;) {
-            ids.push_back(cur);
-            const uint32_t nc = child_off[cur + 1] - child_off[cur];
-            if (nc == 0) break;                                           // final node
-            if (nc == 1) { cur = child_ids[child_off[cur]]; continue; }   // simple forward
-            for (uint32_t q = child_off[cur]; q < child_off[cur + 1]; ++q) {        // branching
-                fifo.push_back(child_ids[q]);
-                successors.push_back(++n_pieces);
-            }
-            break;
-        }
-        pieces.push_back(std::move(ids));
-        skeleton.push_back(std::move(successors));
-    }
-}
-
-// recompose (pto_policy_refiner.rs:324-393): new node k lists its piece node's id (src), its parent (-1: root, or a piece start
-// left unconnected by the one-node quirk) and whether it has no children.  Pieces in order, nodes in path order; inside a piece
-// each node is the child of the one before; then the skeleton edges, from the end of piece i to the start of each next piece.
-static inline void refine_recompose(const std::vector<std::vector<uint32_t>> &pieces, const std::vector<std::vector<uint32_t>> &skeleton,
-                                    std::vector<uint32_t> &src, std::vector<int64_t> &parent, std::vector<uint8_t> &leaf) {
-    src.clear(); parent.clear();
-    std::vector<int64_t> start(pieces.size(), -1), end(pieces.size(), -1);
-    for (size_t i = 0; i < pieces.size(); ++i)
-        for (size_t j = 0; j < pieces[i].size(); ++j) {
-            const int64_t id = (int64_t)src.size();
-            src.push_back(pieces[i][j]);
-            parent.push_back(j == 0 ? -1 : id - 1);
-            if (j == 0) start[i] = id;                               // is_start ...
-            else if (j + 1 == pieces[i].size()) end[i] = id;         // ... else if is_end: a one-node piece has no end
-        }
-    for (size_t i = 0; i < skeleton.size(); ++i)
-        for (uint32_t nxt : skeleton[i])
-            if (end[i] >= 0 && start[nxt] >= 0) parent[(size_t)start[nxt]] = end[i];
-    leaf.assign(src.size(), 1);
-    for (int64_t p : parent) if (p >= 0) leaf[(size_t)p] = 0;
-}
-
-// Policy::compute_expected_costs_to_goals (common.rs:131-154) from node 0: sum over the children in order of
-// p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
-// Children of a recomposed node are in ascending id order.  Evaluated with an explicit stack (a piece can be long).
-template <class ProbOf>
-static inline double refine_expected_cost(const std::vector<int64_t> &parent, const std::vector<double> &xy, ProbOf q_of) {
-    const size_t n = parent.size();
-    if (n == 0) return 0.0;
-    std::vector<uint32_t> off(n + 1, 0), ids;
-    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ++off[(size_t)parent[k] + 1];
-    for (size_t k = 0; k < n; ++k) off[k + 1] += off[k];
-    ids.resize(off[n]);
-    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
-    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ids[fill[(size_t)parent[k]]++] = (uint32_t)k;
-    struct Frame { uint32_t id, next; double p, acc, term; };
-    std::vector<Frame> st{{0u, off[0], 1.0, 0.0, 0.0}};
-    double ret = 0.0;
-    while (true) {
-        Frame &f = st.back();
-        if (f.next < off[f.id + 1]) {
-            const uint32_t c = ids[f.next++];
-            const double q = q_of(f.id, c);
-            double dx = xy[2 * c] - xy[2 * f.id], d2 = 0.0;
-            d2 += dx * dx;
-            dx = xy[2 * c + 1] - xy[2 * f.id + 1];
-            d2 += dx * dx;
-            f.term = f.p * q * std::sqrt(d2);
-            const double pq = f.p * q;
-            st.push_back({c, off[c], pq, 0.0, 0.0});
-            continue;
-        }
-        ret = f.acc;
-        st.pop_back();
-        if (st.empty()) return ret;
-        st.back().acc += st.back().term + ret;
-    }
-}
+// the TAMP planner's launch (porrt_tamp.hpp): one wave per path, RefineConst::pieces / n_pieces / err are its alone
+__global__ __launch_bounds__(64) void k_tamp_shortcut(RefineConst c) { refine_shortcut_piece<true, kRefineLdsNodes>(c, c.pieces[blockIdx.x], c.err); }
 
 } // namespace porrt

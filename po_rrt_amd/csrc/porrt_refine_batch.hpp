@@ -1,6 +1,6 @@
-// porrt_refine_batch.hpp -- refine_solution(PartialShortCut(n)) (porrt_refine.hpp) of many policies in one call: decomposition,
-// shortcuts, recomposition and expected costs on the device (porrt_bg_refine_policies / porrt_mm_refine_policies /
-// porrt_refine_policies).  The single-policy host code of porrt_refine.hpp is the specification of every step here.
+// porrt_refine_batch.hpp -- refine_solution(PartialShortCut(n)) (specified in porrt_refine.hpp) of one policy or many in one call:
+// decomposition, shortcuts, recomposition and expected costs on the device (porrt_bg_refine_policies / porrt_mm_refine_policies /
+// porrt_refine_policies; porrt_bg_refine_policy / porrt_mm_refine_policy / porrt_refine_policy are batches of one).
 //
 // The policies lie end to end: policy q is rows pol_off[q] .. pol_off[q + 1] of the node arrays, parents index into the policy.
 // Every work array is indexed the same way (a policy works in its own rows of global scratch, so its size is bounded by memory

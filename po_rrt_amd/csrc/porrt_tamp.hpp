@@ -287,6 +287,43 @@ static double tamp_transition_probability(const double *parent, const double *ch
     return s;
 }
 
+// Policy::compute_expected_costs_to_goals (common.rs:131-154) from node 0: sum over the children in order of
+// p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
+// Children in ascending id order.  Evaluated with an explicit stack (a piece can be long).
+template <class ProbOf>
+static inline double tamp_expected_cost(const std::vector<int64_t> &parent, const std::vector<double> &xy, ProbOf q_of) {
+    const size_t n = parent.size();
+    if (n == 0) return 0.0;
+    std::vector<uint32_t> off(n + 1, 0), ids;
+    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ++off[(size_t)parent[k] + 1];
+    for (size_t k = 0; k < n; ++k) off[k + 1] += off[k];
+    ids.resize(off[n]);
+    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < n; ++k) if (parent[k] >= 0) ids[fill[(size_t)parent[k]]++] = (uint32_t)k;
+    struct Frame { uint32_t id, next; double p, acc, term; };
+    std::vector<Frame> st{{0u, off[0], 1.0, 0.0, 0.0}};
+    double ret = 0.0;
+    while (true) {
+        Frame &f = st.back();
+        if (f.next < off[f.id + 1]) {
+            const uint32_t c = ids[f.next++];
+            const double q = q_of(f.id, c);
+            double dx = xy[2 * c] - xy[2 * f.id], d2 = 0.0;
+            d2 += dx * dx;
+            dx = xy[2 * c + 1] - xy[2 * f.id + 1];
+            d2 += dx * dx;
+            f.term = f.p * q * std::sqrt(d2);
+            const double pq = f.p * q;
+            st.push_back({c, off[c], pq, 0.0, 0.0});
+            continue;
+        }
+        ret = f.acc;
+        st.pop_back();
+        if (st.empty()) return ret;
+        st.back().acc += st.back().term + ret;
+    }
+}
+
 // build_policy (:619-663) on the chain root .. leaf
 static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id) {
     std::vector<int64_t> chain;
@@ -337,7 +374,7 @@ static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampN
             prev = id;
         }
     }
-    T.info.expected_cost = refine_expected_cost(T.parents, T.xy, [&](uint32_t a, uint32_t b2) {
+    T.info.expected_cost = tamp_expected_cost(T.parents, T.xy, [&](uint32_t a, uint32_t b2) {
         return tamp_transition_probability(T.beliefs.data() + (size_t)a * nw, T.beliefs.data() + (size_t)b2 * nw, nw);
     });
     return PORRT_OK;

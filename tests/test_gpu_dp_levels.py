@@ -5,7 +5,8 @@ assertion that it actually ran:
   k_dp_level_sweep<1> ("wide": a workgroup = 256 beliefs of one node) when N * W >= option dp_wide_rows (default 2 << 20), with
   k_dp_level_sweep<4> ("split") otherwise; option "dp_wide_levels" says which levels of the last computation ran wide;
 * the sweeps' item stamps repeat after 255 sweeps and outlive levels: computations of more than 510 sweeps;
-* dp_extract_policy fetches a row of more than 255 children with a second copy;
+* the policy walk (k_pol_walk) keeps the first kPolRowCache = 512 children of a policy node in LDS and reads the rest of a longer
+  row again;
 * k_eo_segsort sorts buckets of more than kSegLds = 512 entries from global memory (the PTO graph's adjacency, and the children /
   parents lists of the multi-modal belief graph)."""
 import os
@@ -105,7 +106,7 @@ def test_forced_wide_split_and_default_equal_oracle(eng_mod, name):
     assert all(r < DEFAULT_WIDE_ROWS for r in rows)            # these graphs are small: the default sweeps every level split
     if name == "twelve_worlds":
         assert sorted(set(W[W > 256].tolist())) == [495, 792, 924]     # several 256-belief chunks per node under the forced wide kernel
-    if name == "shelf_2_worlds_until_complete":                # (e): a policy node whose row takes the second copy
+    if name == "shelf_2_worlds_until_complete":                # (e): a policy node with a long row (several passes of the walk's lanes)
         coff = e.belief_graph()[2][0]
         assert np.diff(coff.astype(np.int64))[pol[0].astype(np.int64)].max() > 255
 
@@ -206,7 +207,7 @@ def test_wide_levels_at_the_real_threshold(eng_mod):
 
 def test_dense_graph_long_buckets_and_policy_rows(eng_mod):
     """max_step 0.5, search radius 10: nodes found by more than 512 later ones (k_eo_segsort's global-memory branch) and policy
-    nodes of more than 255 children (dp_extract_policy's second copy), both on lists equal to the oracle's"""
+    nodes of more than 512 children (more than k_pol_walk's row cache; the oracle shows 595), both on lists equal to the oracle's"""
     case = cases.cfg3_near(3000)
     case.update(max_step=0.5, search_radius=10.0)
     e, o = grown_pair(eng_mod, case, 64, [0.5, 0.5])
@@ -220,13 +221,14 @@ def test_dense_graph_long_buckets_and_policy_rows(eng_mod):
     assert np.array_equal(ty, to) and np.array_equal(ceo, coo) and np.array_equal(ce, co) and np.array_equal(peo, poo) and np.array_equal(pe, po)
     infos, do, pol = compare_modes(e, o)
     assert pol is not None
-    assert np.diff(coo.astype(np.int64))[pol[0].astype(np.int64)].max() > 255
+    assert np.diff(coo.astype(np.int64))[pol[0].astype(np.int64)].max() > 512
 
 
-@pytest.mark.parametrize("nw,n,max_step,search_radius,seed", [(6, 600, 0.5, 10.0, 0), (12, 60, 0.5, 8.0, 0)])
+@pytest.mark.parametrize("nw,n,max_step,search_radius,seed", [(6, 1100, 0.5, 10.0, 0), (12, 60, 0.5, 8.0, 0)])
 def test_free_centroid_zones_dense(eng_mod, nw, n, max_step, search_radius, seed):
     """the 6- and 12-goal free-centroid rasters through porrt_mm_* against the numpy restatement, with long roadmap radii: policy rows
-    of more than 255 children, and (12 goals) belief graph rows of more than 512 sorted on the device"""
+    of more than 512 children (more than k_pol_walk's row cache: 526 and 939 in the restatement), and (12 goals) belief graph rows of
+    more than 512 sorted on the device"""
     case = mm.bench_case("map_benchmark_like_%d_free_zone_ids" % nw, seed)
     e, o, bg, dist = mm.both(case, [1.0 / nw] * nw, n, max_step, search_radius, seed)
     assert np.isfinite(dist[0])
@@ -235,6 +237,6 @@ def test_free_centroid_zones_dense(eng_mod, nw, n, max_step, search_radius, seed
     oid, par = mm.assert_policy(e, bg, dist)
     n_children = np.array([len(c) for c in bg["children"]])
     n_parents = np.array([len(c) for c in bg["parents"]])
-    assert n_children[oid.astype(np.int64)].max() > 255
+    assert n_children[oid.astype(np.int64)].max() > 512
     if nw == 12:
         assert max(n_children.max(), n_parents.max()) > 512

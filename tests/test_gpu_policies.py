@@ -157,6 +157,26 @@ def test_context_graph(eng_mod, shelf):
     assert info["max_nodes"] == max(len(g[0][0]) for g in got if g is not None)
 
 
+def test_single_extraction_outgrows_its_first_slice(eng_mod):
+    """The single call walks as a batch of one whose first slice holds kPolSingleSlice = 512 policy nodes; a longer policy is walked
+    again with a slice 16 times as long.  cfg3_near with a step of 0.0018: the oracle's root policy has 546 nodes."""
+    case = cases.cfg3_near(26000)
+    case.update(max_step=0.0018)
+    e = cases.configure(eng_mod.Engine(), case)
+    cases.grow(e, case, K=64)
+    o = cases.configure(orc.Oracle(), case)
+    cases.grow(o, case, K=64, algo=orc.ALGO_BATCHED_KD)
+    e.build_belief_graph([0.5, 0.5])
+    o.build_belief_graph([0.5, 0.5])
+    do = o.expected_costs()
+    want = o.extract_policy(do)
+    assert len(want[0]) > 512
+    e.compute_expected_costs()
+    got, cost = e.extract_policy()
+    assert bits([cost])[0] == bits([do[0]])[0]
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))
+
+
 def test_sixteen_worlds_branching(eng_mod):
     case = cases.cfg_door(paper=True)
     e = cases.configure(eng_mod.Engine(), case)

@@ -1,4 +1,4 @@
-"""GPU parity of the policy refiner (porrt_bg_refine_policy / porrt_refine_policy, k_refine_shortcut): PTOPolicyRefiner::
+"""GPU parity of the policy refiner (porrt_bg_refine_policy / porrt_refine_policy: the batch refiner with one policy): PTOPolicyRefiner::
 refine_solution(PartialShortCut(n)) (src/pto_policy_refiner.rs:87-124) on grown pipelines and on hand-built policies, every result
 compared bit for bit (states, original ids, parents, leafs, expected cost) with the restatement tests/refine_ref.py."""
 import ctypes as C

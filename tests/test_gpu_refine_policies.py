@@ -157,6 +157,56 @@ def test_multi_modal(eng_mod):
     assert n_ok >= 3
 
 
+def batch_state(e, mm=False):
+    """what the getters hand out of the last batched calls: the policies' node arrays, porrt_policies_info, porrt_refine_policies_info"""
+    import ctypes as C
+    get = (lambda *a: e._l.porrt_mm_get_policies(e._c, *a)) if mm else (lambda *a: e._l.porrt_bg_get_policies(e._c, *a))
+    n = int(get(*([None] * (4 if mm else 3)), 0))
+    assert n > 0
+    arrays = [np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)] + ([np.zeros((n, 2))] if mm else [])
+    assert int(get(*[a.ctypes.data_as(C.c_void_p) for a in arrays], n)) == n
+    return [a.tobytes() for a in arrays], e.policies_info(), e.refine_policies_info()
+
+
+def test_single_calls_leave_the_batch_state_alone(shelf):
+    """extract_policy() and refine_policy() are batches of one with results of their own: what the last batched calls left stays"""
+    e = shelf.e
+    try:
+        pols, status = e.extract_policies([0] + [s for s, p in zip(shelf.starts[1:], shelf.pols[1:]) if p is not None][:2])
+        refined, rstatus = e.refine_policies(50)
+        assert list(status) == [0, 0, 0] and list(rstatus) == [0, 0, 0]
+        before = batch_state(e)
+        single, cost = e.extract_policy()
+        single_refined = e.refine_policy(50)
+        assert batch_state(e) == before
+        assert all(np.array_equal(a, b) for a, b in zip(single, pols[0][0])) and cost == pols[0][1]
+        assert_same(single_refined, refined[0])
+    finally:
+        e.extract_policies(shelf.starts)                       # what the other tests of this module refine
+
+
+def test_multi_modal_single_calls_leave_the_batch_state_alone(eng_mod):
+    """the same for mm_extract_policy() / mm_refine_policy() on the two-goal case of test_multi_modal"""
+    c = cases.cfg2(10)
+    c.update(zones="map_benchmark_like_2_goals_zone_ids", visibility=0.5)
+    case = cases.Case(c, seed=0)
+    e = cases.configure(eng_mod.Engine(), case)
+    e.set_discrete_seed(0)
+    e.grow_mm_prm(case.start, [0.5, 0.5], 0.1, 2.0, 1000)
+    e.mm_build_belief_graph()
+    d = e.mm_expected_costs()
+    finite = np.flatnonzero(np.isfinite(d) & (np.arange(len(d)) > 0))
+    pols, status = e.mm_extract_policies([0] + sorted(np.random.default_rng(5).choice(finite, size=2, replace=False).tolist()))
+    refined, rstatus = e.mm_refine_policies(50)
+    assert status[0] == 0 and rstatus[0] == 0
+    before = batch_state(e, mm=True)
+    single, cost = e.mm_extract_policy()
+    single_refined = e.mm_refine_policy(50)
+    assert batch_state(e, mm=True) == before
+    assert all(np.array_equal(a, b) for a, b in zip(single, pols[0][0])) and cost == pols[0][1]
+    assert_same(single_refined, refined[0])
+
+
 def engine_and_oracle(eng_mod, case_or_occ):
     e, o = eng_mod.Engine(), orc.Oracle()
     if isinstance(case_or_occ, np.ndarray):

@@ -1,5 +1,5 @@
-"""porrt_bg_extract_policies (the policy walk on the device, many starts per call) beside Engine.extract_policy (the host walk, one
-device round trip per policy node) on the same graphs in the same process: the 12-shelf belief-space graph of bench.py
+"""porrt_bg_extract_policies (the policy walk on the device, many starts per call) beside Engine.extract_policy (the single call: the same
+walk as a batch of one with a result of its own) on the same graphs in the same process: the 12-shelf belief-space graph of bench.py
 (cfg4, 20 000 iterations, 4095 beliefs, uniform prior) and cfg_map4 seed 1 (the reference's recorded problem, K = 1, 16 worlds).
 Per graph: ms_device / ms_wall of the new call for n = 1 (start 0) and for n = 1024 starts drawn from a fixed seed, after a warm-up
 call, and the wall time of extract_policy() right after a cost run (so that it walks).  Writes profiles/policies.json (or --out).
@@ -28,14 +28,14 @@ def probe(e, reps, n_many=1024, seed=1024):
     starts = np.random.default_rng(seed).integers(0, n, size=n_many).astype(np.uint64)
     starts[0] = 0
     host = []
-    for _ in range(reps):                                       # the baseline: the host walk (a cost run before it, or it hands out its copy)
+    for _ in range(reps):                                       # the single call (a cost run before it, or it hands out its copy)
         e.compute_expected_costs()
         t = time.perf_counter()
         (oid, par, leaf), _ = e.extract_policy()
         host.append(1e3 * (time.perf_counter() - t))
     e.extract_policies([0])                                     # warm-up: code object, pool
     e.extract_policies(starts)
-    out = {"belief_nodes": n, "policy_nodes_from_0": len(oid), "host_walk_ms_wall": median(host), "host_walk_ms_wall_runs": host}
+    out = {"belief_nodes": n, "policy_nodes_from_0": len(oid), "single_call_ms_wall": median(host), "single_call_ms_wall_runs": host}
     for name, st in (("n1", starts[:1]), ("n%d" % n_many, starts)):
         runs = []
         for _ in range(reps):
@@ -48,7 +48,7 @@ def probe(e, reps, n_many=1024, seed=1024):
         assert status[0] == 0 and np.array_equal(got[0][0][0], oid) and np.array_equal(got[0][0][1], par) and np.array_equal(got[0][0][2], leaf)
         out[name] = {"median_by_wall": sorted(runs, key=lambda i: i["ms_wall"])[len(runs) // 2], "runs": runs}
     one, many = out["n1"]["median_by_wall"], out["n%d" % n_many]["median_by_wall"]
-    out["host_walk_over_n1_wall"] = out["host_walk_ms_wall"] / one["ms_wall"]
+    out["single_call_over_n1_wall"] = out["single_call_ms_wall"] / one["ms_wall"]
     out["n%d_over_n1_wall" % n_many] = many["ms_wall"] / one["ms_wall"]
     out["us_per_policy_node_n1_device"] = 1e3 * one["ms_device"] / max(one["nodes"], 1)
     out["us_per_policy_node_n%d_device" % n_many] = 1e3 * many["ms_device"] / max(many["nodes"], 1)
@@ -60,7 +60,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "policies.json"))
     a = ap.parse_args()
-    out = {"what": "policies from n belief nodes in one device call (porrt_bg_extract_policies) beside the host walk (porrt_bg_extract_policy)"}
+    out = {"what": "policies from n belief nodes in one device call (porrt_bg_extract_policies) beside the single call (porrt_bg_extract_policy)"}
     case = cases.cfg4(20000, 20000)
     case.update(start=(0.0, -0.3))
     e = cases.configure(po_rrt_amd.Engine(), case)

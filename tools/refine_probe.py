@@ -1,4 +1,4 @@
-"""Policy refinement on the device (porrt_bg_refine_policy, k_refine_shortcut): one JSON line per case.
+"""Policy refinement on the device (porrt_bg_refine_policy: the batch refiner with one policy): one JSON line per case.
 
 Cases: the reference's recorded problem (cfg_map4: main.rs:893-908, paper_map_4, uniform prior over 16 worlds, K = 256) for five
 seeds at the drivers' 500 and 1500 iterations (main.rs:336,375,442,508,558,597,867,908), and the 12-shelf policy of bench.py's
