@@ -18,6 +18,7 @@
 // known-answer graphs (belief_graph.rs:278-567) run through the same code.
 #pragma once
 #include "porrt_belief.hpp"
+#include "porrt_host.hpp"
 
 namespace porrt {
 
@@ -346,11 +347,7 @@ struct DpState {
     void *d_aux = nullptr;                            // edge weights, belief order, flag scratch
     size_t aux_cap = 0;
     bool layered = false;
-    std::vector<uint64_t> pol_original;               // extract_policy: per policy node, in add_node order
-    std::vector<int64_t> pol_parent;
-    std::vector<uint8_t> pol_leaf;
-    bool have_policy = false;
-    void release() { valid = false; have_policy = false; }
+    void release() { valid = false; }
     void free_device() {
         release();
         if (d_dist) (void)hipFree(d_dist);
@@ -372,11 +369,7 @@ struct DpState {
 
 constexpr uint32_t kDpGroup = 8;                      // sweeps between two looks at the "anything changed" flags
 
-#define DP_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e_); return PORRT_ERR_DEVICE; } \
-    } while (0)
+#define DP_HIP(expr) HIPCHK_ERR(expr)
 
 // Runs the sweeps on a graph whose arrays are already on the device (c.dist / c.flags are filled in here).
 static int dp_run(DpState &st, DpConst c, bool implicit, const std::vector<unsigned long long> &finals, hipStream_t s, std::string &err) {

@@ -10,6 +10,7 @@
 //   - get_best_solution / get_path_to / get_path_cost (src/rrt.rs:183-193, 48-61, 223-227).
 // No CPU fallback exists: without a HIP device porrt_create() fails.
 #include "../../include/porrt_hip.h"
+#include "porrt_host.hpp"
 #include "porrt_device.hpp"
 #include "porrt_group.hpp"
 #include "porrt_belief.hpp"
@@ -35,98 +36,15 @@
 #include <memory>
 #include <vector>
 
-// Nothing is thrown across the C boundary: an entry point whose body can allocate runs inside abi_guard.
-template <class F> static inline int abi_guard(F &&f) noexcept {
+// Nothing is thrown across the C boundary: an entry point whose body can allocate runs inside abi_guard, which returns what the
+// body returns (int or int64_t) or the error code.
+template <class F> static inline auto abi_guard(F &&f) noexcept -> decltype(f()) {
     try { return f(); } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
 }
 
 using namespace porrt;
-typedef unsigned __int128 u128;
 
 namespace {
-
-#define HIPCHK_CTX(ctx, expr)                                                                      \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (ctx)->set_err(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
-            return PORRT_ERR_DEVICE;                                                               \
-        }                                                                                          \
-    } while (0)
-
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_err(std::string(#expr) + ": " + hipGetErrorString(e_));                            \
-            return PORRT_ERR_DEVICE;                                                               \
-        }                                                                                          \
-    } while (0)
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// ---- rand_pcg 0.3 Pcg64 (Lcg128Xsl64) + rand_core 0.6 seed_from_u64 + rand 0.8 gen_range on the host.
-// The device generates the continuous stream (k_gen_samples); the host keeps the authoritative state,
-// draws the rejection-sampled world indices and is the exact fallback when a float draw would retry.
-const u128 PCG_MULT = (((u128)0x2360ED051FC65DA4ULL) << 64) | (u128)0x4385DF649FCCF645ULL;
-struct Pcg64 {
-    u128 state, inc;
-    void from_state_incr(u128 s, u128 i) {
-        state = s; inc = i;
-        state += inc;
-        step();
-    }
-    void step() { state = state * PCG_MULT + inc; }
-    void seed_from_u64(uint64_t s) {
-        const uint64_t MUL = 6364136223846793005ULL, INC = 11634580027462260723ULL;
-        uint32_t w[8];
-        for (int c = 0; c < 8; ++c) {
-            s = s * MUL + INC;
-            uint32_t xs = (uint32_t)(((s >> 18) ^ s) >> 27), rot = (uint32_t)(s >> 59);
-            w[c] = (xs >> rot) | (xs << ((32 - rot) & 31));
-        }
-        uint64_t q[4];
-        for (int i = 0; i < 4; ++i) q[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-        from_state_incr((u128)q[0] | ((u128)q[1] << 64), ((u128)q[2] | ((u128)q[3] << 64)) | 1);
-    }
-    uint64_t next_u64() {
-        step();
-        uint32_t rot = (uint32_t)(state >> 122);
-        uint64_t xsl = (uint64_t)(state >> 64) ^ (uint64_t)state;
-        return (xsl >> rot) | (xsl << ((64 - rot) & 63));
-    }
-    void advance(u128 delta) {
-        u128 am = 1, ap = 0, cm = PCG_MULT, cp = inc;
-        while (delta > 0) {
-            if (delta & 1) { am *= cm; ap = ap * cm + cp; }
-            cp = (cm + 1) * cp;
-            cm *= cm;
-            delta >>= 1;
-        }
-        state = am * state + ap;
-    }
-    double gen_range_f64(double low, double high) {
-        double scale = high - low;
-        for (;;) {
-            uint64_t bits = (next_u64() >> 12) | 0x3FF0000000000000ULL;
-            double v12;
-            memcpy(&v12, &bits, 8);
-            volatile double prod = (v12 - 1.0) * scale;
-            double res = prod + low;
-            if (res < high) return res;
-        }
-    }
-    uint64_t gen_range_usize(uint64_t n) {
-        if (n == 0) return next_u64();
-        uint64_t zone = (n << __builtin_clzll(n)) - 1;
-        for (;;) {
-            u128 m = (u128)next_u64() * (u128)n;
-            if ((uint64_t)m <= zone) return (uint64_t)(m >> 64);
-        }
-    }
-};
 
 // All device buffers live in ONE allocation (2 MiB granules): few large pages instead of dozens of small
 // mappings keeps the dependent, scattered loads of the connect / kd kernels out of page-table walks.
@@ -146,55 +64,9 @@ struct Arena {
     size_t cap = 0;
 };
 
-uint64_t ones(int n) { return n >= 64 ? ~0ULL : ((1ULL << n) - 1); }
-
 } // namespace
 
 #include "porrt_mmprm.hpp"
-
-// Device scratch that outlives a call: numbered slots that only grow (a caller that builds roadmaps again and again pays for its
-// buffers once: a dozen hipMalloc / hipFree pairs cost more than the kernels they serve).
-struct GrowScratch {
-    std::vector<std::pair<void *, size_t>> slots;
-    template <class T> hipError_t get(size_t slot, T *&p, size_t n) {
-        if (slots.size() <= slot) slots.resize(slot + 1, {nullptr, 0});
-        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        if (slots[slot].second < bytes) {
-            if (slots[slot].first) (void)hipFree(slots[slot].first);
-            slots[slot] = {nullptr, 0};
-            void *q = nullptr;
-            const hipError_t e = hipMalloc(&q, bytes + bytes / 8);
-            if (e != hipSuccess) return e;
-            slots[slot] = {q, bytes + bytes / 8};
-        }
-        p = (T *)slots[slot].first;
-        return hipSuccess;
-    }
-    void free_all() { for (auto &sl : slots) if (sl.first) (void)hipFree(sl.first); slots.clear(); }
-    GrowScratch() = default;
-    GrowScratch(const GrowScratch &) = delete;
-    GrowScratch &operator=(const GrowScratch &) = delete;
-    ~GrowScratch() { free_all(); }                                   // (a context frees its slots in porrt_destroy, with its device current)
-};
-
-// The device copies of one call's host arrays (the entry points that take an explicit graph): up() allocates n elements (at least
-// 8 bytes), fills them from src when there is one, and returns nullptr on a device error; the destructor frees every buffer,
-// whichever way the call ends.
-struct DeviceUploads {
-    std::vector<void *> owned;
-    template <class T> T *up(const void *src, size_t n) {
-        void *d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(n * sizeof(T), 8)) != hipSuccess) return nullptr;
-        owned.push_back(d);
-        if (n && src && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return (T *)d;
-    }
-    DeviceUploads() { owned.reserve(16); }                          // (more than any caller uploads: recording a buffer does not allocate)
-    DeviceUploads(const DeviceUploads &) = delete;
-    DeviceUploads &operator=(const DeviceUploads &) = delete;
-    ~DeviceUploads() { for (void *d : owned) (void)hipFree(d); }
-};
-
 #include "porrt_mmplan.hpp"
 #include "porrt_policy.hpp"
 
@@ -388,8 +260,16 @@ struct porrt_ctx {
     DpState dp;                            // porrt_bg_compute_expected_costs: dist per belief node (device)
     int compute_expected_costs();
     int extract_policy();
-    // ---- policies from many belief nodes in one call (porrt_policy.hpp): the last call's answers, on the context's graph and on the multi-modal one
-    PoliciesResult policies, mm_policies;
+    // ---- policies (porrt_policy.hpp), on the context's graph and on the multi-modal one: the last batched call's answers (many belief
+    // nodes in one call) and the last single call's (belief node 0: a result of one query).  A result is stamped with the graph and the
+    // cost run it was walked on (PTO: tag = results_tag, stamp = bg_stamp; multi-modal: tag = mmp.gen, stamp = mm_costs_runs); every
+    // consumer asks the predicates below whether the costs, or a result, still belong to the graph in force.
+    PoliciesResult policies, mm_policies, policy, mm_policy;
+    void mm_policy_states(PoliciesResult &res) const;
+    bool costs_current() const { return bg.valid && dp.valid && bg_graph_tag == results_tag && costs_stamp == bg_stamp; }
+    bool mm_costs_current() const { return mm.valid && mmp.valid && mmp.gen == mm.gen && mmp.costs_gen == mmp.gen && mmp.dp.valid; }
+    bool policies_current(const PoliciesResult &res) const { return res.valid && costs_current() && res.tag == results_tag && res.stamp == bg_stamp; }
+    bool mm_policies_current(const PoliciesResult &res) const { return res.valid && mm_costs_current() && res.tag == mmp.gen && res.stamp == mm_costs_runs; }
     GrowScratch policies_scratch;
     uint32_t opt_policy_max_nodes = 1u << 16;       // "policy_max_nodes": a policy that would have more nodes is status 4
     int policies_last = 0;                 // whose info porrt_policies_info hands out: 1 = policies, 2 = mm_policies
@@ -399,30 +279,22 @@ struct porrt_ctx {
                              int64_t *parents, uint8_t *is_leaf, uint64_t cap);
     int64_t mm_extract_policies(const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs, uint64_t *original_ids,
                                 int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap);
-    // ---- policy refinement (porrt_refine.hpp): the policy porrt_bg_extract_policy last handed out, and what it was made from
+    // ---- policy refinement (porrt_refine.hpp, porrt_refine_batch.hpp)
     uint64_t bg_stamp = 0;                 // belief graph builds and expected-cost runs of this context
-    bool pol_out = false;
-    uint64_t pol_tag = 0, pol_stamp = 0;   // results_tag and bg_stamp when the policy was walked
-    uint64_t raster_gen = 1, cls_host_gen = 0, refine_raster_gen = 0;      // set_grid / set_zones; the host classes and the refiner's copy
-    bool refine_raster_table = false;      //   (with or without its summed-area table)
+    uint64_t raster_gen = 1, cls_host_gen = 0;     // set_grid / set_zones; the host classes
     void classify_raster();
-    GrowScratch refine_scratch;            // slot 0: raster, slots 2-4: a call's uploads, draws and answers
-    hipEvent_t refine_ev[2] = {nullptr, nullptr};      // the TAMP shortcut's (porrt_tamp.hpp)
+    void raster_view(RunConst &g, const uint8_t *d_raster) const;
+    int refine_raster(RunConst &g);
+    RefineHost refine;                     // the refiner's device scratch, events, staging and raster copy
     double refine_total_s = 0, refine_device_s = 0;    // the last single call that filled its answer
     bool refine_done = false;
-    // ---- one policy or many in one call (porrt_refine_batch.hpp).  refp_info / refp_done: the last BATCHED call's
-    struct porrt_refine_policies_info refp_info = {};
+    struct porrt_refine_policies_info refp_info = {};  // the last BATCHED call's
     bool refp_done = false;
     bool opt_refine_short_lds = true;      // "refine_short_lds": pieces of <= kRefineShortLdsNodes nodes in a launch of their own with the small LDS array (0: one launch)
-    hipEvent_t refp_ev[2] = {nullptr, nullptr};
-    std::vector<uint8_t> refp_stage;
-    int64_t refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
-                            const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
-                            uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
-                            int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, struct porrt_refine_policies_info *own_info);
-    int64_t refine_policy(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief, const double *beliefs,
-                          uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, double *out_xy, uint64_t *out_original,
-                          int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, double *expected_cost);
+    struct RefineInBuf { std::vector<double> xy; std::vector<uint32_t> row; std::vector<unsigned long long> compat; };     // what a builder's answer points into
+    RefinePoliciesIn refine_in(const PoliciesResult &res, RefineInBuf &buf) const;
+    RefinePoliciesIn mm_refine_in(const PoliciesResult &res, RefineInBuf &buf) const;
+    int64_t refine_call(const char *who, bool single, const RefinePoliciesIn &in, uint64_t n_iter, const RefinePoliciesOut &out, double *expected_cost);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
     GrowScratch prm_paths_scratch;         // plan_path, one pair or many: device buffers (rows of costs, dirty flags, queries), kept across calls
@@ -1253,9 +1125,7 @@ int porrt_ctx::grow_once(const double start[2], double max_step, double search_r
     }
     c.kd_rec = d_kdrec.p; c.g_x = d_gx.p; c.g_y = d_gy.p; c.kd_up = d_kdup.p; c.kd_depth = d_kddepth.p; c.kd_gexit = d_kdgexit.p;
     c.g_id = d_gid.p; c.g_cap = (uint32_t)std::min<uint64_t>(d_gid.n, 0xFFFFFFFFull);
-    c.cls = d_cls.p; c.clr = d_cls.p + (size_t)W * H; c.sat = opt_box_table ? (const uint32_t *)(d_cls.p + cls_sat_offset(W, H)) : nullptr; c.W = W; c.H = H; c.low0 = low[0]; c.low1 = low[1]; c.ppm = ppm; c.domain = domain; c.has_grid = has_grid;
-    c.n_validities = n_validities;
-    for (int i = 0; i < n_validities; ++i) c.validities[i] = validities[i];
+    raster_view(c, d_cls.p);
     c.all_worlds = ones(n_worlds);
     c.goal_kind = goal_kind; c.G = G; c.g_l1 = g_l1;
     for (uint32_t g = 0; g < G; ++g) { c.gcx[g] = gcx[g]; c.gcy[g] = gcy[g]; c.gmask[g] = gmask[g]; }
@@ -1821,8 +1691,7 @@ int porrt_ctx::build_belief_graph(const double *start_belief, uint32_t n_worlds_
 int porrt_ctx::compute_expected_costs() {
     if (!bg.valid || bg_graph_tag != results_tag) { set_err("compute_expected_costs: build the belief graph first (porrt_build_belief_graph)"); return PORRT_ERR_INVALID; }
     HIPCHK(hipSetDevice(device));
-    ++bg_stamp;
-    dp.have_policy = false;                           // a policy walked on the costs before this run is not handed out again
+    ++bg_stamp;                                       // (a policy walked on the costs before this run is not handed out again)
     int r = download(DL_TREE | DL_MASKS);
     if (r) return r;
     const BeliefSpace &bs = bg.cache.space;
@@ -1854,13 +1723,14 @@ int porrt_ctx::compute_expected_costs() {
 
 // PTO::extract_policy (pto.rs:277-283, belief_graph.rs:177-263) on the expected costs of the last compute_expected_costs.
 int porrt_ctx::extract_policy() {
-    if (!bg.valid || !dp.valid || bg_graph_tag != results_tag) { set_err("extract_policy: compute the expected costs first (porrt_bg_compute_expected_costs)"); return PORRT_ERR_INVALID; }
+    if (!costs_current()) { set_err("extract_policy: compute the expected costs first (porrt_bg_compute_expected_costs)"); return PORRT_ERR_INVALID; }
     HIPCHK(hipSetDevice(device));
     std::string e;
-    const int r = pol_extract_root(policies_scratch, dp, true, nullptr, stream, e);
-    if (r) set_err(e);
-    else { pol_tag = results_tag; pol_stamp = bg_stamp; }
-    return r;
+    const int r = pol_extract_root(policies_scratch, dp, true, nullptr, stream, policy, e);
+    if (r) { set_err(e); return r; }
+    policy.tag = results_tag; policy.stamp = bg_stamp;
+    policy.valid = true;
+    return PORRT_OK;
 }
 
 // copies the answers of an extract_policies call into the caller's arrays (the node arrays when cap holds the total)
@@ -1884,7 +1754,7 @@ int64_t porrt_ctx::extract_policies(const uint64_t *starts, uint64_t n, uint64_t
                                     int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     policies.valid = false;
     if (!pol_off || (n && (!starts || !status || !expected_costs))) { set_err("extract_policies: starts, pol_off, status and expected_costs"); return PORRT_ERR_INVALID; }
-    if (!bg.valid || !dp.valid || bg_graph_tag != results_tag || costs_stamp != bg_stamp) {
+    if (!costs_current()) {
         set_err("extract_policies: compute the expected costs first (porrt_bg_compute_expected_costs)");
         return PORRT_ERR_INVALID;
     }
@@ -1899,266 +1769,45 @@ int64_t porrt_ctx::extract_policies(const uint64_t *starts, uint64_t n, uint64_t
     return policies_copy_out(policies, pol_off, status, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
 }
 
-// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of n policies laid end to end (policy q =
-// rows pol_off[q] .. pol_off[q + 1]): node k has state xy[2k..], parent parents[k] within its policy (-1 for its row 0, the root;
-// children in ascending id order), original id original[k] (passed through) and belief row belief[k] of beliefs (n_rows x nw) with
-// compatibility bits compat[row].  Everything on the device (porrt_refine_batch.hpp): one upload, the decomposition, one small
-// download (per policy its counts, per piece of >= 3 nodes its length), one table of draws per distinct length (a fresh Pcg64 of seed 0
-// each: the draws do not depend on the commits) uploaded with the launch order (longest piece first), the shortcuts of all pieces in
-// one launch, offsets, recomposition with the expected costs, one download.  cap = 0 launches no shortcut kernel.  own_info: where the
-// single call (refine_policy below) wants the counts and times; nullptr = refp_info / refp_done, what porrt_refine_policies_info hands out.
-// Returns the refined nodes of the policies with status 0.
-int64_t porrt_ctx::refine_policies(const char *who, uint64_t n, const uint64_t *pol_off, const double *xy, const int64_t *parents, const uint64_t *original,
-                                   const uint32_t *belief, const double *beliefs, uint32_t n_rows, uint32_t nw, const unsigned long long *compat,
-                                   uint64_t n_iter, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy, uint64_t *out_original,
-                                   int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, struct porrt_refine_policies_info *own_info) {
-    const double t0 = now_s();
-    struct porrt_refine_policies_info &info = own_info ? *own_info : refp_info;
-    const std::string W_ = std::string(who) + ": ";
-    if (!pol_off || !ref_off || (n && (!status || !expected_costs))) { set_err(W_ + "pol_off, ref_off, status and expected_costs"); return PORRT_ERR_INVALID; }
-    if (n >= (1ull << 31) || pol_off[0] != 0) { set_err(W_ + "fewer than 2^31 policies, pol_off[0] = 0"); return PORRT_ERR_INVALID; }
-    for (uint64_t q = 0; q < n; ++q)
-        if (pol_off[q + 1] < pol_off[q]) { set_err(W_ + "pol_off must not decrease"); return PORRT_ERR_INVALID; }
-    const uint64_t T = pol_off[n];
-    if (T >= (1ull << 31)) { set_err(W_ + "fewer than 2^31 nodes in all"); return PORRT_ERR_INVALID; }
-    if (n_iter >= (1ull << 31)) { set_err(W_ + "at most 2^31 - 1 iterations"); return PORRT_ERR_INVALID; }
-    if (T && (!xy || !parents || !original || !belief || !beliefs || !n_rows || !nw)) { set_err(W_ + "the policies' arrays"); return PORRT_ERR_INVALID; }
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    // the upload: RunConst | pol_off | compat | beliefs | xy | original ids | parents (checked, 32 bits) | belief rows
-    const size_t o_off = up16(sizeof(RunConst)), o_cp = o_off + up16((n + 1) * 8), o_bel = o_cp + up16((size_t)n_rows * 8),
-                 o_xy = o_bel + up16((size_t)n_rows * nw * 8), o_or = o_xy + up16(T * 16), o_pa = o_or + up16(T * 8), o_br = o_pa + up16(T * 4),
-                 up_bytes = o_br + up16(T * 4);
-    refp_stage.resize(up_bytes);
-    uint8_t *stage = refp_stage.data();
-    {
-        int32_t *pa = (int32_t *)(stage + o_pa);
-        for (uint64_t q = 0; q < n; ++q) {
-            const uint64_t b = pol_off[q], m = pol_off[q + 1] - b;
-            for (uint64_t k = 0; k < m; ++k) {
-                const int64_t p = parents[b + k];
-                if (belief[b + k] >= n_rows) { set_err(W_ + "a belief row out of range (policy " + std::to_string(q) + ")"); return PORRT_ERR_INVALID; }
-                if (k == 0 ? p != -1 : (p < 0 || (uint64_t)p >= m || (uint64_t)p == k)) {
-                    set_err(W_ + "a parent out of range, or a row 0 that is no root (policy " + std::to_string(q) + ")");
-                    return PORRT_ERR_INVALID;
-                }
-                pa[b + k] = (int32_t)p;
-            }
-        }
+// the raster fields of a RunConst from the context, on the device copy d_raster of the classified raster (classes | clearance | table)
+void porrt_ctx::raster_view(RunConst &g, const uint8_t *d_raster) const {
+    g.cls = d_raster; g.clr = d_raster + (size_t)W * H; g.sat = opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(W, H)) : nullptr;
+    g.W = W; g.H = H; g.low0 = low[0]; g.low1 = low[1]; g.ppm = ppm; g.domain = domain; g.has_grid = has_grid;
+    g.n_validities = n_validities;
+    for (int i = 0; i < n_validities; ++i) g.validities[i] = validities[i];
+}
+
+// the refiner's device copy of the classified raster (slot 0 of its scratch), uploaded once per raster, and g's view of it
+int porrt_ctx::refine_raster(RunConst &g) {
+    classify_raster();
+    uint8_t *d = nullptr;
+    HIPCHK(refine.scratch.get(0, d, cls.size()));
+    if (refine.raster_gen != raster_gen) {
+        HIPCHK(hipMemcpyAsync(d, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
+        refine.raster_gen = raster_gen;
     }
-    if (!own_info) refp_done = false;
-    info = {};
-    info.policies = n;
-    ref_off[0] = 0;
-    if (T == 0) {                                                    // nothing but empty policies: no device work
-        for (uint64_t q = 0; q < n; ++q) { ref_off[q + 1] = 0; status[q] = 1; expected_costs[q] = 0.0; }
-        if (n) set_err(W_ + "policy 0: no policy to refine");
-        info.ms_wall = 1e3 * (now_s() - t0);
-        if (!own_info) refp_done = true;
-        return 0;
-    }
+    raster_view(g, d);
+    return PORRT_OK;
+}
+
+// The refiner (porrt_refine_batch.hpp) on the context's raster.  Many policies: the counts and times go to refp_info / refp_done, what
+// porrt_refine_policies_info hands out.  single: one policy, a batch of one with an info block of its own -- refp_info / refp_done are not
+// touched.  A call that refuses its arguments, or only sizes, leaves the info block alone.
+int64_t porrt_ctx::refine_call(const char *who, bool single, const RefinePoliciesIn &in, uint64_t n_iter, const RefinePoliciesOut &out, double *expected_cost) {
     HIPCHK(hipSetDevice(device));
-    const bool shortcuts = cap != 0 && n_iter != 0;
     RunConst g;
     memset(&g, 0, sizeof g);
-    if (has_grid) {
-        // the raster (classes and summed-area table) in the refiner's slot 0, uploaded once per raster
-        classify_raster();
-        uint8_t *d_raster = nullptr;
-        HIPCHK(refine_scratch.get(0, d_raster, cls.size()));
-        if (refine_raster_gen != raster_gen) {
-            HIPCHK(hipMemcpyAsync(d_raster, cls.data(), cls.size(), hipMemcpyHostToDevice, stream));
-            refine_raster_gen = raster_gen;
-        }
-        g.cls = d_raster; g.clr = d_raster + (size_t)W * H; g.sat = opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(W, H)) : nullptr;
-        g.W = W; g.H = H; g.low0 = low[0]; g.low1 = low[1]; g.ppm = ppm; g.domain = domain; g.has_grid = has_grid;
-        g.n_validities = n_validities;
-        for (int i = 0; i < n_validities; ++i) g.validities[i] = validities[i];
-    }
-    memcpy(stage, &g, sizeof g);
-    memcpy(stage + o_off, pol_off, (n + 1) * 8);
-    memcpy(stage + o_cp, compat, (size_t)n_rows * 8);
-    memcpy(stage + o_bel, beliefs, (size_t)n_rows * nw * 8);
-    memcpy(stage + o_xy, xy, T * 16);
-    memcpy(stage + o_or, original, T * 8);
-    memcpy(stage + o_br, belief, T * 4);
-    // the work arrays behind it; the first download (records | lengths of the long pieces) in one piece at the end
-    const size_t L = T / 3 + 1;
-    size_t at = up_bytes;
-    auto take = [&](size_t bytes) { const size_t o = at; at += up16(bytes); return o; };
-    const size_t w_link = take(T * 8), w_next = take(T * 4), w_src = take(T * 4), w_par = take(T * 4), w_leaf = take(T), w_any = take(T * sizeof(RefinePolAny)),
-                 w_longs = take(L * sizeof(RefinePolPiece)), w_x = take(T * 8), w_y = take(T * 8), w_q = take(T * 8), w_t = take(T * 8), w_p = take(T * 8),
-                 w_v = take(T * 8), w_err = take(n * 4), w_rec = take(n * sizeof(RefinePolRecord)), w_len = take(L * 4), bytes = at;
-    uint8_t *d = nullptr;
-    HIPCHK(refine_scratch.get(2, d, bytes));
-    RefinePolConst pc{};
-    pc.pol_off = (const unsigned long long *)(d + o_off); pc.in_xy = (const double *)(d + o_xy); pc.in_orig = (const unsigned long long *)(d + o_or);
-    pc.in_parent = (const int32_t *)(d + o_pa); pc.in_belief = (const uint32_t *)(d + o_br); pc.beliefs = (const double *)(d + o_bel);
-    pc.nw = nw; pc.n_policies = (uint32_t)n;
-    pc.link = (uint2 *)(d + w_link); pc.next = (uint32_t *)(d + w_next); pc.src = (uint32_t *)(d + w_src); pc.par = (int32_t *)(d + w_par);
-    pc.leaf = d + w_leaf; pc.any = (RefinePolAny *)(d + w_any); pc.longs = (RefinePolPiece *)(d + w_longs); pc.long_len = (uint32_t *)(d + w_len);
-    pc.rec = (RefinePolRecord *)(d + w_rec); pc.x = (double *)(d + w_x); pc.y = (double *)(d + w_y);
-    pc.wq = (double *)(d + w_q); pc.wt = (double *)(d + w_t); pc.wp = (double *)(d + w_p); pc.wv = (double *)(d + w_v);
-    pc.pol_err = (uint32_t *)(d + w_err);
-    HIPCHK(hipMemcpyAsync(d, stage, up_bytes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_refine_policies_decompose, dim3((uint32_t)n), dim3(64), 0, stream, pc);
-    HIPCHK(hipGetLastError());
-    std::vector<uint8_t> first(bytes - w_rec);
-    HIPCHK(hipMemcpyAsync(first.data(), d + w_rec, bytes - w_rec, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    const RefinePolRecord *rec = (const RefinePolRecord *)first.data();
-    const uint32_t *long_len = (const uint32_t *)(first.data() + (w_len - w_rec));
-    // the launch order (longest first) and one table of draws per distinct length
-    uint64_t M = 0;
-    std::vector<uint64_t> keys;                                      // length << 32 | row of longs
-    for (uint64_t q = 0; q < n; ++q) {
-        if (rec[q].status) continue;
-        M += rec[q].rows;
-        info.pieces += rec[q].pieces;
-        for (uint32_t j = 0; j < rec[q].longs; ++j) {
-            const uint64_t row = pol_off[q] / 3 + j;
-            keys.push_back((uint64_t)long_len[row] << 32 | row);
-        }
-    }
-    std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
-    std::vector<std::pair<uint32_t, uint32_t>> len_at;               // (length, first draw), longest first
-    for (uint64_t k : keys)
-        if (len_at.empty() || len_at.back().first != (uint32_t)(k >> 32)) {
-            if (shortcuts && (len_at.size() + 1) * n_iter > (1ull << 26)) { set_err(W_ + "more than 2^26 draws (iterations x distinct piece lengths)"); return PORRT_ERR_CAPACITY; }
-            len_at.push_back({(uint32_t)(k >> 32), (uint32_t)(len_at.size() * n_iter)});
-        }
-    info.distinct_lengths = len_at.size();
-    double ms_device = 0.0;
-    if (shortcuts && !keys.empty()) {
-        if (!has_grid) { set_err(W_ + "the refiner checks transitions on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
-        const size_t nd = len_at.size() * n_iter, o_dr = up16(keys.size() * sizeof(uint2)), bytes2 = o_dr + nd * sizeof(uint2);
-        std::vector<uint8_t> second(bytes2);
-        uint2 *order = (uint2 *)second.data(), *dr = (uint2 *)(second.data() + o_dr);
-        size_t li = 0, n_big = 0;
-        for (size_t k = 0; k < keys.size(); ++k) {
-            const uint32_t len = (uint32_t)(keys[k] >> 32);
-            while (len_at[li].first != len) ++li;
-            order[k] = make_uint2((uint32_t)keys[k], len_at[li].second);
-            if (len > kRefineShortLdsNodes) ++n_big;
-        }
-        for (const auto &la : len_at) {                              // DiscreteSampler::new() per piece (pto_policy_refiner.rs:172-175)
-            Pcg64 rng;
-            rng.seed_from_u64(0);
-            const uint64_t Ln = la.first;
-            for (uint64_t it = 0; it < n_iter; ++it) {
-                const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
-                const uint32_t s = (uint32_t)rng.gen_range_usize(Ln - 2);
-                const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(Ln - s - 2);
-                dr[la.second + it] = make_uint2(s | (joint << 31), e);
-            }
-        }
-        uint8_t *d2 = nullptr;
-        HIPCHK(refine_scratch.get(4, d2, bytes2));
-        for (int k = 0; k < 2; ++k) if (!refp_ev[k]) HIPCHK(hipEventCreate(&refp_ev[k]));
-        RefinePolLaunch ln{};
-        ln.rc.rc = (const RunConst *)d; ln.rc.draws = (const uint2 *)(d2 + o_dr); ln.rc.compat = (const unsigned long long *)(d + o_cp);
-        ln.rc.x = pc.x; ln.rc.y = pc.y; ln.rc.n_pieces = (uint32_t)keys.size(); ln.rc.n_iter = (uint32_t)n_iter;
-        ln.longs = pc.longs; ln.order = (const uint2 *)d2; ln.pol_err = pc.pol_err;
-        HIPCHK(hipMemcpyAsync(d2, second.data(), bytes2, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipEventRecord(refp_ev[0], stream));
-        const size_t n_first = opt_refine_short_lds ? n_big : keys.size();
-        if (n_first) {
-            ln.first = 0;
-            hipLaunchKernelGGL(k_refine_policies_shortcut<kRefineLdsNodes>, dim3((uint32_t)n_first), dim3(64), 0, stream, ln);
-            HIPCHK(hipGetLastError());
-        }
-        if (n_first < keys.size()) {                                 // the short pieces: a quarter of the LDS per wave
-            ln.first = (uint32_t)n_first;
-            hipLaunchKernelGGL(k_refine_policies_shortcut<kRefineShortLdsNodes>, dim3((uint32_t)(keys.size() - n_first)), dim3(64), 0, stream, ln);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(refp_ev[1], stream));
-        info.shortcut_pieces = keys.size();
-    }
-    // offsets, recomposition and costs; the answers packed in one block: ref_off | cost | status | xy | original ids | parents | leafs
-    const size_t r_off = 0, r_cost = r_off + up16((n + 1) * 8), r_st = r_cost + up16(n * 8), r_xy = r_st + up16(n), r_or = r_xy + up16(M * 16),
-                 r_pa = r_or + up16(M * 8), r_lf = r_pa + up16(M * 8), bytes3 = r_lf + up16(M);
-    uint8_t *d3 = nullptr;
-    HIPCHK(refine_scratch.get(3, d3, bytes3));
-    pc.ref_off = (unsigned long long *)(d3 + r_off); pc.cost = (double *)(d3 + r_cost); pc.status = d3 + r_st; pc.out_xy = (double *)(d3 + r_xy);
-    pc.out_orig = (unsigned long long *)(d3 + r_or); pc.out_parent = (long long *)(d3 + r_pa); pc.out_leaf = d3 + r_lf;
-    hipLaunchKernelGGL(k_refine_policies_offsets, dim3(1), dim3(256), 0, stream, pc);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_refine_policies_recompose, dim3((uint32_t)n), dim3(64), 0, stream, pc);
-    HIPCHK(hipGetLastError());
-    std::vector<uint8_t> third(bytes3);
-    HIPCHK(hipMemcpyAsync(third.data(), d3, bytes3, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (info.shortcut_pieces) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, refp_ev[0], refp_ev[1]));
-        ms_device = (double)ms;
-    }
-    memcpy(ref_off, third.data() + r_off, (n + 1) * 8);
-    memcpy(expected_costs, third.data() + r_cost, n * 8);
-    memcpy(status, third.data() + r_st, n);
-    const uint64_t total = ref_off[n];
-    if (total && total <= cap) {
-        if (out_xy) memcpy(out_xy, third.data() + r_xy, total * 16);
-        if (out_original) memcpy(out_original, third.data() + r_or, total * 8);
-        if (out_parents) memcpy(out_parents, third.data() + r_pa, total * 8);
-        if (out_leaf) memcpy(out_leaf, third.data() + r_lf, total);
-    }
-    for (uint64_t q = 0; q < n; ++q) info.ok += status[q] == 0;
-    for (uint64_t q = 0; q < n; ++q)
-        if (status[q]) {
-            static const char *const what[4] = {"", "no policy to refine", "a shortcut reads outside the raster, a door pixel without zone id or two zones on one segment (the reference panics)",
-                                                "a piece whose nodes carry different beliefs (the reference asserts, common.rs:102)"};
-            set_err(W_ + "policy " + std::to_string(q) + ": " + what[status[q] & 3]);
-            break;
-        }
-    info.nodes = total;
-    info.ms_device = ms_device;
-    info.ms_wall = 1e3 * (now_s() - t0);
-    if (!own_info) refp_done = true;
-    return (int64_t)total;
-}
-
-// Rows of a refined policy: decompose reaches a node iff its chain of parents ends at node 0, and recompose gives every node reached
-// one row (a piece left unconnected by the one-node quirk keeps its rows).  -1: parents that refine_policies refuses.
-static int64_t refine_rows(uint64_t n, const int64_t *parents) {
-    if (n && parents[0] != -1) return -1;
-    std::vector<uint8_t> mark(n, 0);                                 // 1 reached, 2 not (or being walked: a cycle is not reached)
-    std::vector<uint64_t> chain;
-    int64_t rows = n ? 1 : 0;
-    if (n) mark[0] = 1;
-    for (uint64_t k = 1; k < n; ++k) {
-        chain.clear();
-        uint64_t j = k;
-        for (; !mark[j]; j = (uint64_t)parents[j]) {
-            if (parents[j] < 0 || (uint64_t)parents[j] >= n || (uint64_t)parents[j] == j) return -1;
-            mark[j] = 2;
-            chain.push_back(j);
-        }
-        if (mark[j] == 1) { for (uint64_t c : chain) mark[c] = 1; rows += (int64_t)chain.size(); }
-    }
-    return rows;
-}
-
-// One policy: a batch of one (refine_policies) with status and info block of its own -- refp_info / refp_done, the last BATCHED call's,
-// are not touched.  Returns the number of nodes of the refined policy always and fills the arrays when cap holds it; a smaller cap is the
-// sizing form, answered on the host (no device work; the beliefs are checked by the call that fills).
-int64_t porrt_ctx::refine_policy(uint64_t n, const double *xy, const int64_t *parents, const uint64_t *original, const uint32_t *belief, const double *beliefs,
-                                 uint32_t n_rows, uint32_t nw, const unsigned long long *compat, uint64_t n_iter, double *out_xy, uint64_t *out_original,
-                                 int64_t *out_parents, uint8_t *out_leaf, uint64_t cap, double *expected_cost) {
-    const int64_t rows = refine_rows(n, parents);
-    if (rows >= 0 && cap < (uint64_t)rows) return rows;
-    const uint64_t pol_off[2] = {0, n};
-    uint64_t ref_off[2] = {0, 0};
-    uint8_t status = 0;
-    double cost = 0.0;
+    int r = PORRT_OK;
+    if (has_grid && (r = refine_raster(g))) return r;
+    std::string e;
     struct porrt_refine_policies_info info;
-    const int64_t m = refine_policies("refine_policy", 1, pol_off, xy, parents, original, belief, beliefs, n_rows, nw, compat, n_iter, ref_off, &status, &cost,
-                                      out_xy, out_original, out_parents, out_leaf, cap, &info);
-    if (m < 0) return m;
-    if (status) return status == 2 ? PORRT_ERR_RASTER : PORRT_ERR_INVALID;      // (refine_policies has set the message)
-    if (expected_cost) *expected_cost = cost;
-    refine_total_s = 1e-3 * info.ms_wall; refine_device_s = 1e-3 * info.ms_device;
-    refine_done = true;
+    info.policies = ~0ull;
+    const int64_t m = single ? porrt::refine_policy(refine, in, n_iter, out, expected_cost, g, opt_refine_short_lds, stream, info, e)
+                             : porrt::refine_policies(refine, who, in, n_iter, out, g, opt_refine_short_lds, stream, info, e);
+    if (!e.empty()) set_err(e);
+    if (info.policies == ~0ull) return m;
+    if (!single) { refp_info = info; refp_done = m >= 0; }
+    else if (m >= 0) { refine_total_s = 1e-3 * info.ms_wall; refine_device_s = 1e-3 * info.ms_device; refine_done = true; }
     return m;
 }
 
@@ -2213,9 +1862,7 @@ int porrt_ctx::grow_prm(const double start[2], double max_step, double search_ra
     HIPCHK(hipMemsetAsync(d_finalflag.p, 0, N, stream));
     memset(&rc, 0, sizeof rc);
     rc.nx = d_nx.p; rc.ny = d_ny.p; rc.vid = d_vid.p;
-    rc.cls = d_cls.p; rc.clr = d_cls.p + (size_t)W * H; rc.sat = opt_box_table ? (const uint32_t *)(d_cls.p + cls_sat_offset(W, H)) : nullptr; rc.W = W; rc.H = H; rc.low0 = low[0]; rc.low1 = low[1]; rc.ppm = ppm; rc.domain = domain; rc.has_grid = has_grid;
-    rc.n_validities = n_validities;
-    for (int i = 0; i < n_validities; ++i) rc.validities[i] = validities[i];
+    raster_view(rc, d_cls.p);
     rc.all_worlds = ones(n_worlds);
     rc.visibility = visibility;
     rc.rad_T2 = d_radT2.p;
@@ -2366,9 +2013,7 @@ int porrt_ctx::roadmaps_of_modes(double max_step, double search_radius) {
     rad_uploaded = 0;
     if ((r = ensure_radius_table(max_step, search_radius, max_n + 2))) return r;
     memset(&rc, 0, sizeof rc);
-    rc.cls = d_cls.p; rc.clr = d_cls.p + (size_t)W * H; rc.sat = opt_box_table ? (const uint32_t *)(d_cls.p + cls_sat_offset(W, H)) : nullptr; rc.W = W; rc.H = H; rc.low0 = low[0]; rc.low1 = low[1]; rc.ppm = ppm; rc.domain = domain; rc.has_grid = has_grid;
-    rc.n_validities = n_validities;
-    for (int i = 0; i < n_validities; ++i) rc.validities[i] = validities[i];
+    raster_view(rc, d_cls.p);
     rc.all_worlds = ones(n_worlds);
     rc.visibility = visibility;
     rc.rad_T2 = d_radT2.p;
@@ -2748,8 +2393,7 @@ int porrt_ctx::mm_compute_expected_costs() {
     MmPlanState &s = mmp;
     if (!mm.valid || !s.valid || s.gen != mm.gen) { set_err("mm_compute_expected_costs: build the belief graph of the last porrt_grow_mm_prm first (porrt_mm_build_belief_graph)"); return PORRT_ERR_INVALID; }
     HIPCHK(hipSetDevice(device));
-    s.costs_gen = s.policy_gen = ~0ull;
-    s.dp.have_policy = false;
+    s.costs_gen = ~0ull;
     ++mm_costs_runs;
     const double t0 = now_s();
     std::string e;
@@ -2771,28 +2415,35 @@ int porrt_ctx::mm_compute_expected_costs() {
     return PORRT_OK;
 }
 
+// the states of a result's policy nodes, from the modes' roadmaps
+void porrt_ctx::mm_policy_states(PoliciesResult &res) const {
+    const MmPlanState &s = mmp;
+    const size_t total = res.original.size();
+    res.xy.resize(2 * total);
+    for (size_t k = 0; k < total; ++k) {
+        const uint64_t id = res.original[k];
+        const uint32_t m = mm_mode_of(s, id);
+        const uint64_t local = id - s.mode_off[m];
+        res.xy[2 * k] = mm.modes[m].xy[2 * local]; res.xy[2 * k + 1] = mm.modes[m].xy[2 * local + 1];
+    }
+}
+
 // extract_policy (:479-485, belief_graph.rs:177-263) from belief node 0, clustered by belief id; the nodes' states with it
 int porrt_ctx::mm_extract_policy() {
     MmPlanState &s = mmp;
-    if (!mm.valid || !s.valid || s.gen != mm.gen || s.costs_gen != s.gen || !s.dp.valid) {
+    if (!mm_costs_current()) {
         set_err("mm_extract_policy: compute the expected costs of the last belief graph first (porrt_mm_compute_expected_costs)");
         return PORRT_ERR_INVALID;
     }
     HIPCHK(hipSetDevice(device));
     const double t0 = now_s();
     std::string e;
-    const int r = pol_extract_root(policies_scratch, s.dp, false, s.d_bid, stream, e);
+    const int r = pol_extract_root(policies_scratch, s.dp, false, s.d_bid, stream, mm_policy, e);
     if (r) { set_err(e); return r; }
-    const size_t n = s.dp.pol_original.size();
-    s.pol_xy.resize(2 * n);
-    for (size_t k = 0; k < n; ++k) {
-        const uint64_t id = s.dp.pol_original[k];
-        const uint32_t m = mm_mode_of(s, id);
-        const uint64_t local = id - s.mode_off[m];
-        s.pol_xy[2 * k] = mm.modes[m].xy[2 * local]; s.pol_xy[2 * k + 1] = mm.modes[m].xy[2 * local + 1];
-    }
+    mm_policy_states(mm_policy);
     s.t_extract = now_s() - t0;
-    s.policy_gen = s.gen;
+    mm_policy.tag = s.gen; mm_policy.stamp = mm_costs_runs;
+    mm_policy.valid = true;
     return PORRT_OK;
 }
 
@@ -2802,7 +2453,7 @@ int64_t porrt_ctx::mm_extract_policies(const uint64_t *starts, uint64_t n, uint6
     MmPlanState &s = mmp;
     mm_policies.valid = false;
     if (!pol_off || (n && (!starts || !status || !expected_costs))) { set_err("mm_extract_policies: starts, pol_off, status and expected_costs"); return PORRT_ERR_INVALID; }
-    if (!mm.valid || !s.valid || s.gen != mm.gen || s.costs_gen != s.gen || !s.dp.valid) {
+    if (!mm_costs_current()) {
         set_err("mm_extract_policies: compute the expected costs of the last belief graph first (porrt_mm_compute_expected_costs)");
         return PORRT_ERR_INVALID;
     }
@@ -2811,14 +2462,7 @@ int64_t porrt_ctx::mm_extract_policies(const uint64_t *starts, uint64_t n, uint6
     const int r = pol_extract(policies_scratch, s.dp.last, false, s.d_bid, starts, n, opt_policy_max_nodes, 0, stream, mm_policies, e);
     if (r) { set_err(e); return r; }
     if (!e.empty()) set_err(e);
-    const size_t total = mm_policies.original.size();
-    mm_policies.xy.resize(2 * total);
-    for (size_t k = 0; k < total; ++k) {
-        const uint64_t id = mm_policies.original[k];
-        const uint32_t m = mm_mode_of(s, id);
-        const uint64_t local = id - s.mode_off[m];
-        mm_policies.xy[2 * k] = mm.modes[m].xy[2 * local]; mm_policies.xy[2 * k + 1] = mm.modes[m].xy[2 * local + 1];
-    }
+    mm_policy_states(mm_policies);
     mm_policies.tag = s.gen; mm_policies.stamp = mm_costs_runs;
     mm_policies.valid = true;
     policies_last = 2;
@@ -3705,12 +3349,10 @@ void porrt_destroy(porrt_ctx *c) {
     if (c->d_batch_out) (void)hipFree(c->d_batch_out);
     c->mm_scratch.free_all();
     c->mmp_scratch.free_all();
-    c->refine_scratch.free_all();
+    c->refine.free_device();
     c->prm_paths_scratch.free_all();
     c->qmdp_scratch.free_all();
     c->policies_scratch.free_all();
-    for (int k = 0; k < 2; ++k) if (c->refine_ev[k]) (void)hipEventDestroy(c->refine_ev[k]);
-    for (int k = 0; k < 2; ++k) if (c->refp_ev[k]) (void)hipEventDestroy(c->refp_ev[k]);
     for (int k = 0; k < 2; ++k) if (c->d_rcarr_c[k]) (void)hipFree(c->d_rcarr_c[k]);
     if (c->d_live_idx) (void)hipFree(c->d_live_idx);
     if (c->d_active) (void)hipFree(c->d_active);
@@ -4399,36 +4041,27 @@ uint64_t porrt_bg_get_dp_sweep_rows(const porrt_ctx *c) { return c && c->dp.vali
 // PTO::extract_policy: returns the number of policy nodes (or a negative error); fills the arrays when they hold that many
 int64_t porrt_bg_extract_policy(porrt_ctx *c, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap, double *expected_costs) {
     if (!c) return PORRT_ERR_INVALID;
-    if (!c->dp.have_policy) {
-        int r = c->extract_policy();
-        if (r) return r;
-    }
-    const uint64_t n = c->dp.pol_original.size();
-    if (expected_costs && hipMemcpy(expected_costs, c->dp.d_dist, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
-    c->pol_out = true;
-    if (cap >= n) {
-        for (uint64_t k = 0; k < n; ++k) {
-            if (original_ids) original_ids[k] = c->dp.pol_original[k];
-            if (parents) parents[k] = c->dp.pol_parent[k];
-            if (is_leaf) is_leaf[k] = c->dp.pol_leaf[k];
+    return abi_guard([&]() -> int64_t {
+        if (!c->policies_current(c->policy)) {
+            const int r = c->extract_policy();
+            if (r) return r;
         }
-    }
-    return (int64_t)n;
+        return policies_copy_out(c->policy, nullptr, nullptr, expected_costs, original_ids, parents, is_leaf, nullptr, cap);
+    });
 }
 
 // ---- policies from many belief nodes in one call (porrt_policy.hpp)
 int64_t porrt_bg_extract_policies(porrt_ctx *c, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs,
                                   uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
-    try { return c->extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, cap); }
-    catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+    return abi_guard([&]() -> int64_t { return c->extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, cap); });
 }
 int64_t porrt_bg_get_policies(const porrt_ctx *c, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
     porrt_ctx *m = const_cast<porrt_ctx *>(c);                      // (for the error text only)
     const PoliciesResult &res = c->policies;
     if (!res.valid) { m->set_err("bg_get_policies: no answers: call porrt_bg_extract_policies first"); return PORRT_ERR_INVALID; }
-    if (!c->bg.valid || !c->dp.valid || c->bg_graph_tag != c->results_tag || res.tag != c->results_tag || res.stamp != c->bg_stamp || c->costs_stamp != c->bg_stamp) {
+    if (!c->policies_current(res)) {
         m->set_err("bg_get_policies: the graph, the belief graph or the expected costs changed since porrt_bg_extract_policies");
         return PORRT_ERR_INVALID;
     }
@@ -4437,16 +4070,14 @@ int64_t porrt_bg_get_policies(const porrt_ctx *c, uint64_t *original_ids, int64_
 int64_t porrt_mm_extract_policies(porrt_ctx *c, const uint64_t *starts, uint64_t n, uint64_t *pol_off, uint8_t *status, double *expected_costs,
                                   uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
-    try { return c->mm_extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, xy, cap); }
-    catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+    return abi_guard([&]() -> int64_t { return c->mm_extract_policies(starts, n, pol_off, status, expected_costs, original_ids, parents, is_leaf, xy, cap); });
 }
 int64_t porrt_mm_get_policies(const porrt_ctx *c, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
     porrt_ctx *m = const_cast<porrt_ctx *>(c);
     const PoliciesResult &res = c->mm_policies;
-    const MmPlanState &s = c->mmp;
     if (!res.valid) { m->set_err("mm_get_policies: no answers: call porrt_mm_extract_policies first"); return PORRT_ERR_INVALID; }
-    if (!c->mm.valid || !s.valid || s.gen != c->mm.gen || s.costs_gen != s.gen || !s.dp.valid || res.tag != s.gen || res.stamp != c->mm_costs_runs) {
+    if (!c->mm_policies_current(res)) {
         m->set_err("mm_get_policies: the modes, the belief graph or the expected costs changed since porrt_mm_extract_policies");
         return PORRT_ERR_INVALID;
     }
@@ -4511,28 +4142,46 @@ static std::vector<unsigned long long> refine_compat_rows(const porrt_ctx *c, co
     return compat;
 }
 
+// What the refiner reads of a result of the context's graph (after download(DL_TREE)): build_path_piece's state and belief of every
+// policy node, with the belief space and compatibilities the belief graph was built on
+RefinePoliciesIn porrt_ctx::refine_in(const PoliciesResult &res, RefineInBuf &buf) const {
+    const uint64_t T = res.off.back(), B = bg.B;
+    const BeliefSpace &bs = bg.cache.space;
+    buf.xy.resize(2 * T); buf.row.resize(T);
+    for (uint64_t k = 0; k < T; ++k) {
+        const uint64_t id = res.original[k], node = id / B;
+        buf.xy[2 * k] = h_nx[node]; buf.xy[2 * k + 1] = h_ny[node];
+        buf.row[k] = (uint32_t)(id % B);
+    }
+    return RefinePoliciesIn{res.status.size(), res.off.data(), buf.xy.data(), res.parent.data(), res.original.data(), buf.row.data(), bs.vec.data(), (uint32_t)B, bs.nw,
+                            bg.cache.compat.data()};
+}
+// the same of a result of the multi-modal graph: its own states, the mode of every policy node into row, the modes' beliefs
+RefinePoliciesIn porrt_ctx::mm_refine_in(const PoliciesResult &res, RefineInBuf &buf) const {
+    const MmPlanState &s = mmp;
+    const uint64_t T = res.off.back();
+    const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
+    buf.row.resize(T);
+    for (uint64_t k = 0; k < T; ++k) buf.row[k] = mm_mode_of(s, res.original[k]);
+    buf.compat = refine_compat_rows(this, s.beliefs.data(), M, nw);
+    return RefinePoliciesIn{res.status.size(), res.off.data(), res.xy.data(), res.parent.data(), res.original.data(), buf.row.data(), s.beliefs.data(), M, nw,
+                            buf.compat.data()};
+}
+
 // PTOPolicyRefiner::refine_solution(PartialShortCut(n_iterations)) of the policy the last porrt_bg_extract_policy handed out
 int64_t porrt_bg_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf,
                                uint64_t cap, double *expected_costs) {
     if (!c) return PORRT_ERR_INVALID;
-    return abi_guard([&]() -> int {
-        if (!c->pol_out || !c->dp.have_policy || !c->bg.valid || !c->have_results || c->pol_tag != c->results_tag || c->pol_stamp != c->bg_stamp) {
+    return abi_guard([&]() -> int64_t {
+        if (!c->have_results || !c->policies_current(c->policy)) {
             c->set_err("refine_policy: no policy to refine -- call porrt_bg_extract_policy after the last growth, belief graph and expected costs");
             return PORRT_ERR_INVALID;
         }
-        int r = c->download(porrt_ctx::DL_TREE);
+        const int r = c->download(porrt_ctx::DL_TREE);
         if (r) return r;
-        const uint64_t n = c->dp.pol_original.size(), B = c->bg.B;
-        const BeliefSpace &bs = c->bg.cache.space;
-        std::vector<double> pxy(2 * n);
-        std::vector<uint32_t> belief(n);
-        for (uint64_t k = 0; k < n; ++k) {                    // build_path_piece: the belief graph node's state and belief
-            const uint64_t id = c->dp.pol_original[k], node = id / B;
-            pxy[2 * k] = c->h_nx[node]; pxy[2 * k + 1] = c->h_ny[node];
-            belief[k] = (uint32_t)(id % B);
-        }
-        return (int)c->refine_policy(n, pxy.data(), c->dp.pol_parent.data(), c->dp.pol_original.data(), belief.data(), bs.vec.data(), (uint32_t)B, bs.nw,
-                                     c->bg.cache.compat.data(), n_iterations, xy, original_ids, parents, is_leaf, cap, expected_costs);
+        porrt_ctx::RefineInBuf buf;
+        return c->refine_call("refine_policy", true, c->refine_in(c->policy, buf), n_iterations, RefinePoliciesOut{nullptr, nullptr, nullptr, xy, original_ids, parents, is_leaf, cap},
+                                expected_costs);
     });
 }
 
@@ -4541,11 +4190,12 @@ int64_t porrt_refine_policy(porrt_ctx *c, uint64_t n, const double *xy, const in
                             const double *beliefs, uint32_t n_belief_rows, uint32_t n_worlds, uint64_t n_iterations, double *out_xy,
                             uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap, double *expected_costs) {
     if (!c || !n || !xy || !parents || !original_ids || !belief_row || !beliefs || !n_belief_rows) return PORRT_ERR_INVALID;
-    return abi_guard([&]() -> int {
+    return abi_guard([&]() -> int64_t {
         if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policy: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
         const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
-        return (int)c->refine_policy(n, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data(), n_iterations, out_xy,
-                                     out_original_ids, out_parents, out_is_leaf, cap, expected_costs);
+        const uint64_t pol_off[2] = {0, n};
+        return c->refine_call("refine_policy", true, RefinePoliciesIn{1, pol_off, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data()}, n_iterations,
+                                RefinePoliciesOut{nullptr, nullptr, nullptr, out_xy, out_original_ids, out_parents, out_is_leaf, cap}, expected_costs);
     });
 }
 
@@ -4560,62 +4210,47 @@ int porrt_bg_get_refine_info(const porrt_ctx *c, double *total_s, double *device
 int64_t porrt_bg_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
                                  uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
-    try {
+    return abi_guard([&]() -> int64_t {
         const PoliciesResult &res = c->policies;
         if (!res.valid) { c->set_err("bg_refine_policies: no policies to refine: call porrt_bg_extract_policies first"); return PORRT_ERR_INVALID; }
-        if (!c->bg.valid || !c->dp.valid || !c->have_results || c->bg_graph_tag != c->results_tag || res.tag != c->results_tag || res.stamp != c->bg_stamp ||
-            c->costs_stamp != c->bg_stamp) {
+        if (!c->have_results || !c->policies_current(res)) {
             c->set_err("bg_refine_policies: the graph, the belief graph or the expected costs changed since porrt_bg_extract_policies");
             return PORRT_ERR_INVALID;
         }
         const int r = c->download(porrt_ctx::DL_TREE);
         if (r) return r;
-        const uint64_t n = res.status.size(), T = res.off.back(), B = c->bg.B;
-        const BeliefSpace &bs = c->bg.cache.space;
-        std::vector<double> pxy(2 * T);
-        std::vector<uint32_t> belief(T);
-        for (uint64_t k = 0; k < T; ++k) {                    // build_path_piece: the belief graph node's state and belief
-            const uint64_t id = res.original[k], node = id / B;
-            pxy[2 * k] = c->h_nx[node]; pxy[2 * k + 1] = c->h_ny[node];
-            belief[k] = (uint32_t)(id % B);
-        }
-        return c->refine_policies("bg_refine_policies", n, res.off.data(), pxy.data(), res.parent.data(), res.original.data(), belief.data(), bs.vec.data(),
-                                  (uint32_t)B, bs.nw, c->bg.cache.compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents,
-                                  is_leaf, cap, nullptr);
-    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+        porrt_ctx::RefineInBuf buf;
+        return c->refine_call("bg_refine_policies", false, c->refine_in(res, buf), n_iterations,
+                              RefinePoliciesOut{ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap}, nullptr);
+    });
 }
 int64_t porrt_mm_refine_policies(porrt_ctx *c, uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
                                  uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
-    try {
+    return abi_guard([&]() -> int64_t {
         const PoliciesResult &res = c->mm_policies;
-        const MmPlanState &s = c->mmp;
         if (!res.valid) { c->set_err("mm_refine_policies: no policies to refine: call porrt_mm_extract_policies first"); return PORRT_ERR_INVALID; }
-        if (!c->mm.valid || !s.valid || s.gen != c->mm.gen || s.costs_gen != s.gen || !s.dp.valid || res.tag != s.gen || res.stamp != c->mm_costs_runs) {
+        if (!c->mm_policies_current(res)) {
             c->set_err("mm_refine_policies: the modes, the belief graph or the expected costs changed since porrt_mm_extract_policies");
             return PORRT_ERR_INVALID;
         }
-        const uint64_t n = res.status.size(), T = res.off.back();
-        const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
-        std::vector<uint32_t> row(T);
-        for (uint64_t k = 0; k < T; ++k) row[k] = mm_mode_of(s, res.original[k]);
-        const std::vector<unsigned long long> compat = refine_compat_rows(c, s.beliefs.data(), M, nw);
-        return c->refine_policies("mm_refine_policies", n, res.off.data(), res.xy.data(), res.parent.data(), res.original.data(), row.data(), s.beliefs.data(),
-                                  M, nw, compat.data(), n_iterations, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap, nullptr);
-    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+        porrt_ctx::RefineInBuf buf;
+        return c->refine_call("mm_refine_policies", false, c->mm_refine_in(res, buf), n_iterations,
+                              RefinePoliciesOut{ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap}, nullptr);
+    });
 }
 int64_t porrt_refine_policies(porrt_ctx *c, uint64_t n_policies, const uint64_t *pol_off, const double *xy, const int64_t *parents,
                               const uint64_t *original_ids, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows, uint32_t n_worlds,
                               uint64_t n_iterations, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy,
                               uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap) {
     if (!c) return PORRT_ERR_INVALID;
-    try {
+    return abi_guard([&]() -> int64_t {
         if (!pol_off || !beliefs || !n_belief_rows) { c->set_err("refine_policies: pol_off and the beliefs"); return PORRT_ERR_INVALID; }
         if ((int)n_worlds != c->n_worlds) { c->set_err("refine_policies: the beliefs need one probability per world of the context"); return PORRT_ERR_INVALID; }
         const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
-        return c->refine_policies("refine_policies", n_policies, pol_off, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds,
-                                  compat.data(), n_iterations, ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap, nullptr);
-    } catch (const std::bad_alloc &) { return PORRT_ERR_NOMEM; } catch (...) { return PORRT_ERR_INVALID; }
+        return c->refine_call("refine_policies", false, RefinePoliciesIn{n_policies, pol_off, xy, parents, original_ids, belief_row, beliefs, n_belief_rows, n_worlds, compat.data()},
+                              n_iterations, RefinePoliciesOut{ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap}, nullptr);
+    });
 }
 int porrt_refine_policies_info(const porrt_ctx *c, struct porrt_refine_policies_info *out) {
     if (!c || !out || !c->refp_done) return PORRT_ERR_INVALID;
@@ -4654,49 +4289,33 @@ int porrt_mm_compute_expected_costs(porrt_ctx *c) {
     return abi_guard([&]() -> int { return c->mm_compute_expected_costs(); });
 }
 int porrt_mm_get_expected_costs(const porrt_ctx *c, double *out) {
-    if (!mm_graph_ok(c) || !out || c->mmp.costs_gen != c->mmp.gen || !c->mmp.dp.valid) return PORRT_ERR_INVALID;
+    if (!c || !out || !c->mm_costs_current()) return PORRT_ERR_INVALID;
     if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(out, c->mmp.dp.d_dist, c->mmp.NT * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
     return PORRT_OK;
 }
 int64_t porrt_mm_extract_policy(porrt_ctx *c, uint64_t *ids, int64_t *parents, uint8_t *is_leaf, double *xy, uint64_t cap, double *expected_cost) {
     if (!c) return PORRT_ERR_INVALID;
-    return abi_guard([&]() -> int {
-        MmPlanState &s = c->mmp;
-        if (!(s.policy_gen == s.gen && s.dp.have_policy && mm_graph_ok(c) && s.costs_gen == s.gen)) {
+    return abi_guard([&]() -> int64_t {
+        if (!c->mm_policies_current(c->mm_policy)) {
             const int r = c->mm_extract_policy();
             if (r) return r;
         }
-        const uint64_t n = s.dp.pol_original.size();
-        if (expected_cost && hipMemcpy(expected_cost, s.dp.d_dist, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return PORRT_ERR_DEVICE;
-        if (cap >= n) {
-            for (uint64_t k = 0; k < n; ++k) {
-                if (ids) ids[k] = s.dp.pol_original[k];
-                if (parents) parents[k] = s.dp.pol_parent[k];
-                if (is_leaf) is_leaf[k] = s.dp.pol_leaf[k];
-            }
-            if (xy) memcpy(xy, s.pol_xy.data(), 2 * n * sizeof(double));
-        }
-        return (int)n;
+        return policies_copy_out(c->mm_policy, nullptr, nullptr, expected_cost, ids, parents, is_leaf, xy, cap);
     });
 }
 int64_t porrt_mm_refine_policy(porrt_ctx *c, uint64_t n_iterations, double *xy, uint64_t *ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap,
                                double *expected_cost) {
     if (!c) return PORRT_ERR_INVALID;
-    return abi_guard([&]() -> int {
-        MmPlanState &s = c->mmp;
-        if (!mm_graph_ok(c) || s.costs_gen != s.gen || s.policy_gen != s.gen || !s.dp.have_policy) {
+    return abi_guard([&]() -> int64_t {
+        if (!c->mm_policies_current(c->mm_policy)) {
             c->set_err("mm_refine_policy: no policy to refine -- call porrt_mm_extract_policy after the last porrt_grow_mm_prm, belief graph and expected costs");
             return PORRT_ERR_INVALID;
         }
-        const uint64_t n = s.dp.pol_original.size();
-        const uint32_t nw = s.nw, M = (uint32_t)s.n_modes;
-        std::vector<uint32_t> row(n);
-        for (uint64_t k = 0; k < n; ++k) row[k] = mm_mode_of(s, s.dp.pol_original[k]);
-        const std::vector<unsigned long long> compat = refine_compat_rows(c, s.beliefs.data(), M, nw);
-        const int64_t m = c->refine_policy(n, s.pol_xy.data(), s.dp.pol_parent.data(), s.dp.pol_original.data(), row.data(), s.beliefs.data(), M, nw,
-                                           compat.data(), n_iterations, xy, ids, parents, is_leaf, cap, expected_cost);
-        if (m >= 0 && cap >= (uint64_t)m) { s.t_refine = c->refine_total_s; s.t_refine_device = c->refine_device_s; }
-        return (int)m;
+        porrt_ctx::RefineInBuf buf;
+        const int64_t m = c->refine_call("refine_policy", true, c->mm_refine_in(c->mm_policy, buf), n_iterations, RefinePoliciesOut{nullptr, nullptr, nullptr, xy, ids, parents, is_leaf, cap},
+                                           expected_cost);
+        if (m >= 0 && cap >= (uint64_t)m) { c->mmp.t_refine = c->refine_total_s; c->mmp.t_refine_device = c->refine_device_s; }
+        return m;
     });
 }
 // MapShelfDomainTampPRM::plan (:310-326): grow, belief graph, expected costs, policy; returns the policy's node count
@@ -4709,7 +4328,7 @@ int64_t porrt_mm_plan(porrt_ctx *c, const double start[2], const double *initial
         c->mmp.t_grow = now_s() - t0;
         if (r) return r;
         if ((r = c->mm_build_belief_graph()) || (r = c->mm_compute_expected_costs()) || (r = c->mm_extract_policy())) return r;
-        return (int)c->mmp.dp.pol_original.size();
+        return (int)c->mm_policy.original.size();
     });
 }
 // seconds of the last steps: grow (porrt_mm_plan only), build, build on the device, expected costs, on the device, policy walk, refine, on the device
@@ -4721,7 +4340,7 @@ int porrt_mm_get_plan_seconds(const porrt_ctx *c, double *out, uint32_t n) {
     return PORRT_OK;
 }
 int porrt_mm_get_dp_info(const porrt_ctx *c, uint32_t *levels, uint32_t *launches, uint64_t *sweeps, int *level_schedule) {
-    if (!mm_graph_ok(c) || c->mmp.costs_gen != c->mmp.gen) return PORRT_ERR_INVALID;
+    if (!c || !c->mm_costs_current()) return PORRT_ERR_INVALID;
     const MmPlanState &s = c->mmp;
     if (levels) *levels = s.levels;
     if (launches) *launches = s.launches;

@@ -268,16 +268,15 @@ struct MmPlanState {
     DpConst c{};                                                 // device arrays of the graph (explicit layout)
     uint32_t *d_mode_off = nullptr, *d_bid = nullptr;
     double t_build = 0, t_build_device = 0;
-    // the expected costs (valid for costs_gen == gen) and the policy walked on them
+    // the expected costs (valid for costs_gen == gen)
     DpState dp;
-    uint64_t costs_gen = ~0ull, policy_gen = ~0ull;
+    uint64_t costs_gen = ~0ull;
     uint32_t levels = 0, launches = 0;
     unsigned long long level_sweeps = 0, max_mode_sweeps = 0;
     double t_costs = 0, t_costs_device = 0, t_extract = 0, t_refine = 0, t_refine_device = 0, t_grow = 0;
-    std::vector<double> pol_xy;
     uint32_t lds_cap = kMmLdsNodes;                              // option "mm_lds_nodes"
     bool use_levels = false;                                     // option "mm_levels": the level schedule (slower than the sweeps)
-    void release() { valid = false; dp.release(); costs_gen = policy_gen = ~0ull; }
+    void release() { valid = false; dp.release(); costs_gen = ~0ull; }
 };
 
 static inline uint32_t mm_mode_of(const MmPlanState &s, uint64_t node) {

@@ -194,10 +194,9 @@ static const char *const kPolStatusText[5] = {"", "its expected cost is not fini
                                               "the policy exceeds policy_max_nodes, or a belief node has more than 65535 children"};
 
 // Walks the policies from starts[0 .. n) on the graph and costs of c (c.dist set; bid = clustering key per node, explicit layout only).
-// Sc: GrowScratch (slots 0-7 are used).  first_slice: the slice of the first round (0 = the pool shared out among the queries).
+// Slots 0-7 of sc are used.  first_slice: the slice of the first round (0 = the pool shared out among the queries).
 // Fills everything of out but tag / stamp / xy / valid.
-template <class Sc>
-static int pol_extract(Sc &sc, const DpConst &c, bool implicit, const uint32_t *d_bid, const uint64_t *starts, uint64_t n, uint64_t max_nodes,
+static int pol_extract(GrowScratch &sc, const DpConst &c, bool implicit, const uint32_t *d_bid, const uint64_t *starts, uint64_t n, uint64_t max_nodes,
                        uint64_t first_slice, hipStream_t s, PoliciesResult &out, std::string &err) {
     const double t0 = bg_now();
     out.valid = false;
@@ -315,14 +314,13 @@ static int pol_extract(Sc &sc, const DpConst &c, bool implicit, const uint32_t *
     return PORRT_OK;
 }
 
-// The single extraction (PTO::extract_policy, pto.rs:277-283): the policy from belief node 0 as a batch of one, into a result of its
-// own and from there into st.pol_*.  Its limit is kPolMaxNodesLimit policy nodes; the first walk gets kPolSingleSlice of them (a lone
-// query's share of the pool would be all of it), a longer policy is walked again as any query that outgrows its slice.
+// The single extraction (PTO::extract_policy, pto.rs:277-283): the policy from belief node 0 as a batch of one, into a result of the
+// caller's (one query; tag / stamp / xy / valid are the caller's to set).  Its limit is kPolMaxNodesLimit policy nodes; the first walk
+// gets kPolSingleSlice of them (a lone query's share of the pool would be all of it), a longer policy is walked again as any query
+// that outgrows its slice.
 constexpr uint64_t kPolSingleSlice = 512;
-template <class Sc>
-static int pol_extract_root(Sc &sc, DpState &st, bool implicit, const uint32_t *d_bid, hipStream_t s, std::string &err) {
+static int pol_extract_root(GrowScratch &sc, const DpState &st, bool implicit, const uint32_t *d_bid, hipStream_t s, PoliciesResult &res, std::string &err) {
     const uint64_t root = 0;
-    PoliciesResult res;
     const int r = pol_extract(sc, st.last, implicit, d_bid, &root, 1, kPolMaxNodesLimit, kPolSingleSlice, s, res, err);
     if (r) return r;
     const uint32_t status = res.status[0];
@@ -333,8 +331,6 @@ static int pol_extract_root(Sc &sc, DpState &st, bool implicit, const uint32_t *
         return status == POL_CAPACITY ? PORRT_ERR_CAPACITY : PORRT_ERR_INVALID;
     }
     err.clear();
-    st.pol_original = std::move(res.original); st.pol_parent = std::move(res.parent); st.pol_leaf = std::move(res.leaf);
-    st.have_policy = true;
     return PORRT_OK;
 }
 

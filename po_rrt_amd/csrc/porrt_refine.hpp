@@ -9,7 +9,7 @@
 //     commit all of [s, e) iff every transition candidate(j) -> candidate(j + 1) and candidate(e - 1) -> state(e) is valid
 // where valid = both states have a validity (state_validity) and the segment's validity (transition_validator) is compatible
 // with the piece's belief (is_transition_valid, :395-423).  The draws never depend on the commits, so they are a function of
-// the piece length alone: the host makes them once per distinct length (engine Pcg64::gen_range_usize) and uploads them.
+// the piece length alone: the host makes them once per distinct length (shortcut_draws, porrt_refine_batch.hpp) and uploads them.
 //
 // Device (refine_shortcut_piece): one wave per piece of >= 3 nodes, all pieces of a call in one launch.  The iterations run in
 // order inside the wave; per iteration the lanes stride over [s, e), each forms its candidate and the next one, classifies the

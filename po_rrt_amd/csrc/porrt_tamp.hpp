@@ -203,20 +203,10 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
     if (longs.empty()) return PORRT_OK;
     if (ns >= (1ull << 31)) { c->set_err("tamp_shortcut: too many states"); return PORRT_ERR_INVALID; }
     HIPCHK_CTX(c, hipSetDevice(c->device));
-    c->classify_raster();
-    uint8_t *d_raster = nullptr;
-    HIPCHK_CTX(c, c->refine_scratch.get(0, d_raster, c->cls.size()));
-    if (c->refine_raster_gen != c->raster_gen) {
-        HIPCHK_CTX(c, hipMemcpyAsync(d_raster, c->cls.data(), c->cls.size(), hipMemcpyHostToDevice, c->stream));
-        c->refine_raster_gen = c->raster_gen;
-    }
     RunConst g;
     memset(&g, 0, sizeof g);
-    g.cls = d_raster; g.clr = d_raster + (size_t)c->W * c->H;
-    g.sat = c->opt_box_table ? (const uint32_t *)(d_raster + cls_sat_offset(c->W, c->H)) : nullptr;
-    g.W = c->W; g.H = c->H; g.low0 = c->low[0]; g.low1 = c->low[1]; g.ppm = c->ppm; g.domain = c->domain; g.has_grid = c->has_grid;
-    g.n_validities = c->n_validities;
-    for (int i = 0; i < c->n_validities; ++i) g.validities[i] = c->validities[i];
+    const int r = c->refine_raster(g);
+    if (r) return r;
     // one staging area: RunConst | paths | draws | x | y | error word
     auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t nd = len_at.size() * n_iter;
@@ -226,35 +216,25 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
     memcpy(stage.data(), &g, sizeof g);
     memcpy(stage.data() + o_pc, longs.data(), longs.size() * sizeof(RefinePiece));
     uint2 *dr = (uint2 *)(stage.data() + o_dr);
-    for (const auto &la : len_at) {              // DiscreteSampler::new() per path (:576-584): partial_shortcut's sequence
-        Pcg64 rng;
-        rng.seed_from_u64(0);
-        const uint64_t L = la.first;
-        for (uint32_t it = 0; it < n_iter; ++it) {
-            const uint32_t joint = (uint32_t)rng.gen_range_usize(2);
-            const uint32_t s = (uint32_t)rng.gen_range_usize(L - 2);
-            const uint32_t e = s + 2 + (uint32_t)rng.gen_range_usize(L - s - 2);
-            dr[la.second + it] = make_uint2(s | (joint << 31), e);
-        }
-    }
+    for (const auto &la : len_at) shortcut_draws(la.first, n_iter, dr + la.second);      // DiscreteSampler::new() per path (:576-584)
     double *sx = (double *)(stage.data() + o_x), *sy = (double *)(stage.data() + o_y);
     for (size_t k = 0; k < ns; ++k) { sx[k] = xy[2 * k]; sy[k] = xy[2 * k + 1]; }
     uint8_t *d = nullptr;
     HIPCHK_CTX(c, T.scratch.get(3, d, bytes));
-    for (int k = 0; k < 2; ++k) if (!c->refine_ev[k]) HIPCHK_CTX(c, hipEventCreate(&c->refine_ev[k]));
+    HIPCHK_CTX(c, c->refine.events());
     RefineConst rc{};
     rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = nullptr;
     rc.draws = (const uint2 *)(d + o_dr); rc.x = (double *)(d + o_x); rc.y = (double *)(d + o_y); rc.err = (uint32_t *)(d + o_err);
     rc.n_pieces = (uint32_t)longs.size(); rc.n_iter = n_iter;
     HIPCHK_CTX(c, hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK_CTX(c, hipEventRecord(c->refine_ev[0], c->stream));
+    HIPCHK_CTX(c, hipEventRecord(c->refine.ev[0], c->stream));
     hipLaunchKernelGGL(k_tamp_shortcut, dim3(rc.n_pieces), dim3(64), 0, c->stream, rc);
     HIPCHK_CTX(c, hipGetLastError());
-    HIPCHK_CTX(c, hipEventRecord(c->refine_ev[1], c->stream));
+    HIPCHK_CTX(c, hipEventRecord(c->refine.ev[1], c->stream));
     HIPCHK_CTX(c, hipMemcpyAsync(stage.data() + o_x, d + o_x, bytes - o_x, hipMemcpyDeviceToHost, c->stream));
     HIPCHK_CTX(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    HIPCHK_CTX(c, hipEventElapsedTime(&ms, c->refine_ev[0], c->refine_ev[1]));
+    HIPCHK_CTX(c, hipEventElapsedTime(&ms, c->refine.ev[0], c->refine.ev[1]));
     if (dev_s) *dev_s = 1e-3 * (double)ms;
     uint32_t err = 0;
     memcpy(&err, stage.data() + o_err, 4);

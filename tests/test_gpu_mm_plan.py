@@ -172,3 +172,31 @@ def test_stale_and_missing_steps_are_errors():
             call()
     e.mm_build_belief_graph()
     assert len(e.mm_expected_costs()) != len(d)
+
+
+def test_single_and_batched_extraction_share_their_states():
+    """mm_extract_policy() and mm_extract_policies([0])[0] hand out the same states, bit for bit.  On the two-shelf case the root's cost
+    is +inf, so both refuse there and the states of whatever policies the finite starts have are checked against the graph's; the
+    two-goal case has a policy from the root."""
+    case = cases.cfg3(1500, 1500)
+    e, o, bg, dist = both(case, [0.5, 0.5], 2000, 0.1, 2.0, 0)
+    assert_dist(e.mm_expected_costs(), dist)
+    assert not np.isfinite(dist[0])
+    with pytest.raises(RuntimeError):
+        e.mm_extract_policy()
+    starts = [0] + np.flatnonzero(np.isfinite(dist))[:8].tolist()
+    got, status = e.mm_extract_policies(starts)
+    assert status[0] == 1 and got[0] is None
+    for g in (g for g in got if g is not None):
+        oid, xy = g[0][0], g[0][3]
+        assert np.array_equal(xy.view(np.uint64), bg["xy"][oid.astype(np.int64)].view(np.uint64))
+    case = bench_case("map_benchmark_like_2_goals_zone_ids", 0)
+    e, o, bg, dist = both(case, [0.5, 0.5], 1000, 0.1, 2.0, 0)
+    e.mm_expected_costs()
+    (oid, par, leaf, xy), cost = e.mm_extract_policy()
+    got, status = e.mm_extract_policies([0])
+    assert status[0] == 0
+    (oid_b, par_b, leaf_b, xy_b), cost_b = got[0]
+    assert np.array_equal(oid, oid_b) and np.array_equal(par, par_b) and np.array_equal(leaf, leaf_b)
+    assert xy.tobytes() == xy_b.tobytes() and np.float64(cost).view(np.uint64) == np.float64(cost_b).view(np.uint64)
+    assert np.array_equal(xy.view(np.uint64), bg["xy"][oid.astype(np.int64)].view(np.uint64))

@@ -341,3 +341,45 @@ def test_interface(eng_mod, shelf):
     with pytest.raises(eng_mod.PorrtError):
         e.extract_policies([0])
     assert L.porrt_bg_get_policies(c, None, None, None, 0) < 0
+
+
+# ---------------------------------------------------------------------------------------------- the single extraction's store
+
+def test_single_extraction_refuses_costs_of_another_belief_graph(eng_mod):
+    """a belief graph rebuilt without a new cost run: the single extraction refuses as the batched one does, whether a policy was
+    walked on the old costs (it is not handed out again) or not (nothing is walked on the old costs)"""
+    case = cases.cfg3_near(1500)
+    e = cases.configure(eng_mod.Engine(), case)
+    cases.grow(e, case, K=64)
+    for walked_before in (True, False):
+        e.build_belief_graph([0.5, 0.5])
+        e.compute_expected_costs()
+        if walked_before:
+            e.extract_policy()
+        e.build_belief_graph([0.9, 0.1])
+        with pytest.raises(eng_mod.PorrtError) as ei:
+            e.extract_policy()
+        assert ei.value.code == -1 and "compute the expected costs first" in str(ei.value)
+        with pytest.raises(eng_mod.PorrtError):
+            e.extract_policies([0])
+    e.compute_expected_costs()
+    single, cost = e.extract_policy()
+    got, status = e.extract_policies([0])
+    assert status[0] == 0 and all(np.array_equal(a, b) for a, b in zip(got[0][0], single))
+    assert bits([got[0][1]])[0] == bits([cost])[0]
+    G, d, _ = context_ref(e)
+    assert_answers(got, status, ref.extract_policies(G, d, [0]), "the rebuilt graph")
+
+
+def test_single_and_batched_results_are_kept_apart(eng_mod, shelf):
+    e, _, _, d, _ = shelf
+    first, cost1 = e.extract_policy()
+    again, cost2 = e.extract_policy()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, again)) and bits([cost1])[0] == bits([cost2])[0]
+    starts = [5, 17, 0, 3]
+    got, status = e.extract_policies(starts)
+    info = e.policies_info()
+    third, cost3 = e.extract_policy()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, third)) and bits([cost1])[0] == bits([cost3])[0]
+    assert e.policies_info() == info and info["queries"] == len(starts) and info["ok"] == (status == 0).sum()
+    assert info["nodes"] == sum(len(g[0][0]) for g in got if g is not None)
