@@ -226,20 +226,24 @@ def test_the_walk_that_does_not_end(eng_mod):
 def test_multi_modal(eng_mod):
     """The smallest case of test_gpu_mm_plan.py: test_benchmark_two_goals, seed 0 (3123 belief nodes, 3 modes, a finite root).  Its
     test_two_shelves is larger (6243) and its root has no finite cost, so there is no single extraction to compare start 0 with.
-    On the oracle's graph of this case policies_ref gives status 0 for 43 of the 50 drawn starts and status 1 for the other 7."""
+    The reference walks the ORACLE's growth (mm_plan_ref on oracle/mmprm.c), not the engine's own belief graph: a wrong roadmap is
+    not walked consistently on both sides.  There policies_ref gives status 0 for 43 of the 50 drawn starts and status 1 for the
+    other 7."""
+    import mm_plan_ref
     c = cases.cfg2(10)
     c.update(zones="map_benchmark_like_2_goals_zone_ids", visibility=0.5)
     case = cases.Case(c, seed=0)
     e = cases.configure(eng_mod.Engine(), case)
+    o = cases.configure(orc.Oracle(), case)
     e.set_discrete_seed(0)
-    mm = e.grow_mm_prm(case.start, [0.5, 0.5], 0.1, 2.0, 1000)
+    o.set_discrete_seed(0)
+    e.grow_mm_prm(case.start, [0.5, 0.5], 0.1, 2.0, 1000)
+    _, obg, odist = mm_plan_ref.plan(o, case.start, [0.5, 0.5], 0.1, 2.0, 1000)
     e.mm_build_belief_graph()
     d = e.mm_expected_costs()
-    bg = e.mm_belief_graph()
-    xy = np.concatenate([m["xy"] for m in mm["modes"]])
-    moff = bg["mode_offsets"].astype(np.int64)
-    mode_of = np.repeat(np.arange(len(mm["modes"])), np.diff(moff))
-    G = ref.Graph(xy, mode_of, [m["belief"] for m in mm["modes"]], bg["belief_ids"], bg["children"][0], bg["children"][1])
+    assert np.array_equal(bits(d), bits(odist))
+    xy = obg["xy"]
+    G = ref.graph_of_lists(xy, obg["belief_vec"], obg["beliefs"], obg["belief_ids"], obg["children"])
     (oid, par, leaf, pxy), cost0 = e.mm_extract_policy()
     rng = np.random.default_rng(5)
     starts = [0] + rng.integers(0, len(d), size=50).tolist()
@@ -247,7 +251,7 @@ def test_multi_modal(eng_mod):
     assert status[0] == 0 and got[0][1] == cost0
     for a, b in zip(got[0][0], (oid, par, leaf, pxy)):
         assert np.array_equal(a, b)
-    assert_answers(got, status, ref.extract_policies(G, d, starts), "multi-modal")
+    assert_answers(got, status, ref.extract_policies(G, odist, starts), "multi-modal")
     for g in got:
         if g is not None:
             assert np.array_equal(bits(g[0][3]), bits(xy[g[0][0].astype(np.int64)]))

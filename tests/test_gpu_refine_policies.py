@@ -126,7 +126,10 @@ def test_grown_door_four_worlds(eng_mod):
 
 
 def test_multi_modal(eng_mod):
+    """every policy of the batch against the single-policy call on the same arrays AND against refine_ref on the policy that
+    policies_ref walks on the ORACLE's growth from the same start"""
     import mm_plan_ref
+    import policies_ref
     c = cases.cfg2(10)
     c.update(zones="map_benchmark_like_2_goals_zone_ids", visibility=0.5)
     case = cases.Case(c, seed=0)
@@ -138,9 +141,13 @@ def test_multi_modal(eng_mod):
     _, bg, dist = mm_plan_ref.plan(o, case.start, [0.5, 0.5], 0.1, 2.0, 1000)
     e.mm_build_belief_graph()
     d = e.mm_expected_costs()
+    assert np.array_equal(d.view(np.uint64), dist.view(np.uint64))
     finite = np.flatnonzero(np.isfinite(d) & (np.arange(len(d)) > 0))
     starts = [0] + sorted(np.random.default_rng(5).choice(finite, size=5, replace=False).tolist())
+    G = policies_ref.graph_of_lists(bg["xy"], bg["belief_vec"], bg["beliefs"], bg["belief_ids"], bg["children"])
+    walked = policies_ref.extract_policies(G, dist, starts)
     pols, ext_status = e.mm_extract_policies(starts)
+    assert ext_status.tolist() == [w[0] for w in walked]
     got, status = e.mm_refine_policies(500)
     assert len(got) == len(starts) and status[0] == 0
     e.mm_extract_policy()
@@ -153,6 +160,9 @@ def test_multi_modal(eng_mod):
         (oid, par, leaf, xy), _ = pols[q]
         row = bg["belief_vec"][oid.astype(np.int64)]
         assert_same(got[q], e.refine_policy_explicit(xy, par, oid, row, bg["beliefs"], 500))
+        oid_o, par_o, _ = walked[q][1]
+        i = oid_o.astype(np.int64)
+        assert_same(got[q], rp.restate(o, (bg["xy"][i], par_o, oid_o, bg["belief_vec"][i]), bg["beliefs"], 500))
         n_ok += 1
     assert n_ok >= 3
 
