@@ -163,6 +163,25 @@ public:
         for (size_t id : get_firstly_final_node_ids(tree, finals)) { auto p = tree.get_path_to(id); double c = path_cost(p); out.push_back({std::move(p), c}); }
         return {std::move(out), std::move(tree)};
     }
+    // RRT::get_solutions (rrt.rs:195-221) of the last plan / plan_several / plan_batch, walked on the device (porrt_solutions: no
+    // tree is downloaded): the firstly final nodes in ASCENDING NODE ID (the reference's order is a HashSet's), each with its path
+    // from the root and the path's cost.  plan_several above keeps its host walk over the downloaded tree.
+    std::vector<Solution> solutions() {
+        porrt_ctx *c = ctx_.get();
+        uint64_t ns = 0, nst = 0;
+        ctx_.check(porrt_solutions(&c, 1, &ns, &nst, nullptr, nullptr, nullptr, 0, nullptr, 0));
+        std::vector<uint64_t> ids(ns), lens(ns);
+        std::vector<double> costs(ns), xy(2 * nst);
+        if (ns) ctx_.check(porrt_solutions(&c, 1, &ns, &nst, ids.data(), lens.data(), costs.data(), ns, xy.data(), nst));
+        std::vector<Solution> out;
+        size_t at = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            std::vector<State> p(lens[s]);
+            for (size_t k = 0; k < lens[s]; ++k, ++at) p[k] = {xy[2 * at], xy[2 * at + 1]};
+            out.push_back({std::move(p), costs[s]});
+        }
+        return out;
+    }
     // Many independent queries at once (the TAMP layer's pattern, map_shelves_tamp_rrt.rs:163-291): every planner keeps
     // its own map, sampler state and result; all of them advance in one launch sequence (porrt_grow_batch), each running the
     // loop of rrt.rs:109 with the caller's n_iter_min / n_iter_max (the TAMP search passes 2500 / 10000, main.rs:532).  Same
@@ -720,7 +739,9 @@ enum class TampSearch { AStar, BranchAndBound, BranchAndBoundMultipleViewPoints 
 
 // MapShelfDomainTampRRT (map_shelves_tamp_rrt.rs:135-291): plan(.., TampSearch::BranchAndBound) on the device
 // (porrt_tamp_rrt_plan).  AStar and BranchAndBoundMultipleViewPoints throw: their expansion order cannot be
-// pinned.  The stream mode, wave width and pool size are the context's options tamp_streams / tamp_wave / tamp_pool.
+// pinned.  plan_multiple_viewpoints (:293-430, porrt_tamp_rrt_plan_viewpoints) is the latter with the viewpoints
+// of a query walked in ascending node id -- one of the orders the reference may take, which is why it is a method of its own.
+// The stream mode, wave width and pool size are the context's options tamp_streams / tamp_wave / tamp_pool.
 class MapShelfDomainTampRRT {
 public:
     MapShelfDomainTampRRT(const ContinuousSampler &cs, const DiscreteSampler &ds, const MapShelfDomain &m, double goal_radius, int device = 0)
@@ -731,11 +752,29 @@ public:
     }
     Policy plan(State start, const BeliefState &initial_belief_state, double max_step, double search_radius, size_t n_iter_min,
                 size_t n_iter_max, TampSearch search, uint32_t batch_K = 128) {
+        if (search == TampSearch::BranchAndBoundMultipleViewPoints)
+            throw std::runtime_error("MapShelfDomainTampRRT: TampSearch::BranchAndBoundMultipleViewPoints walks a HashSet; "
+                                     "plan_multiple_viewpoints() offers it with the viewpoints in ascending node id");
         if (search != TampSearch::BranchAndBound) throw std::runtime_error("MapShelfDomainTampRRT: only TampSearch::BranchAndBound is supported");
         const int64_t r = porrt_tamp_rrt_plan(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(), max_step,
                                               search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
+        return read_policy(r, initial_belief_state.size());
+    }
+    // plan_branch_bound_multiple_viewpoints (:293-430), viewpoints in ascending node id.  max_viewpoints is ours, not the
+    // reference's: 0 = all, n = the n cheapest solutions of every observation query.
+    Policy plan_multiple_viewpoints(State start, const BeliefState &initial_belief_state, double max_step, double search_radius, size_t n_iter_min,
+                                    size_t n_iter_max, uint32_t max_viewpoints = 0, uint32_t batch_K = 128) {
+        const int64_t r = porrt_tamp_rrt_plan_viewpoints(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(),
+                                                         max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K, max_viewpoints);
+        return read_policy(r, initial_belief_state.size());
+    }
+    porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
+    porrt_tamp_viewpoints_info viewpoints_info() const { porrt_tamp_viewpoints_info i; ctx_.check(porrt_tamp_rrt_get_viewpoints_info(ctx_.get(), &i)); return i; }
+    const Context &context() const { return ctx_; }
+private:
+    Policy read_policy(int64_t r, size_t nw) {
         if (r < 0) ctx_.check((int)r);
-        const size_t n = (size_t)r, nw = initial_belief_state.size();
+        const size_t n = (size_t)r;
         std::vector<double> xy(2 * n), bel(n * nw);
         std::vector<int64_t> par(n);
         std::vector<uint8_t> leaf(n);
@@ -753,9 +792,6 @@ public:
         }
         return policy;
     }
-    porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
-    const Context &context() const { return ctx_; }
-private:
     Context ctx_;
     double goal_radius_;
 };

@@ -696,6 +696,48 @@ int      porrt_best_paths(porrt_ctx *const *ctxs, uint32_t n_ctx, double *xy, ui
 /* the planner's shortcut on explicit paths, on the device: path i = states [offsets[i], offsets[i + 1]) of xy (n x 2); out like xy */
 int      porrt_tamp_shortcut_paths(porrt_ctx *ctx, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out);
 
+/* ---- RRT::get_solutions (src/rrt.rs:195-246) of many grown RRT* trees in one device call: every "firstly
+ * final" node of a tree -- a final node whose parent is not final -- with its path from the root and that path's cost (folded from
+ * 0.0 in path order, rrt.rs:223-227).  The reference returns them in the order of a HashSet; here they come in ASCENDING NODE ID.
+ * n_solutions[q], n_states[q]: solutions of context q and the states of all their paths (either may be NULL).  With ids == NULL the
+ * call is a size query.  Otherwise the solutions come concatenated context by context, ascending id within a context: ids, lens
+ * (states per path) and costs hold cap_solutions entries, xy cap_states states (x y), the paths root first one after another.
+ * Nothing is truncated: PORRT_ERR_CAPACITY if a cap is too small.  Runs of the argument that are exactly a leader's last
+ * porrt_grow_batch get one launch; other contexts go one by one.  A context without a solution has count 0 (no error).
+ * PORRT_ERR_INVALID for NULL, a context without results or with PTO / PRM results.  No tree is downloaded. */
+int      porrt_solutions(porrt_ctx *const *ctxs, uint32_t n_ctx, uint64_t *n_solutions, uint64_t *n_states, uint64_t *ids, uint64_t *lens,
+                         double *costs, uint64_t cap_solutions, double *xy, uint64_t cap_states);
+
+/* ---- MapShelfDomainTampRRT::plan(.., TampSearch::BranchAndBoundMultipleViewPoints) (map_shelves_tamp_rrt.rs:293-430, DESIGN.md
+ * section 21): the branch and bound of porrt_tamp_rrt_plan in which the observation query of a (search node, zone) pair keeps all
+ * its solutions (RRT::plan_several) and every one of them -- a viewpoint -- becomes a child, with a pickup query of its own.
+ * A separate entry point on purpose: porrt_tamp_rrt_plan with "tamp_search" 2 stays refused, because the reference walks the
+ * viewpoints in the order of a HashSet.  What is offered here is the reference's search with that set walked in ASCENDING NODE ID:
+ * one of the orders the reference may take, not one we can claim it took.
+ * max_viewpoints is ours, not the reference's: 0 keeps all viewpoints (the reference); n > 0 keeps, per observation query, the n
+ * solutions of lowest cost (ties: the lower id), still walked in ascending id.
+ * "tamp_streams" 0: one continuous stream; per (node, zone) the observation query, then its viewpoints' pickup queries in ascending
+ * id.  1 (default): the observation query of (u, t) runs on a stream seeded ho = splitmix64(u.h ^ (t + 1)) (root h = the sampler
+ * seed), the pickup query of the viewpoint of rank j (0-based, in the kept list) on h = splitmix64(ho ^ ((j + 1) << 32)), which is
+ * the child's h: the pickup does NOT continue the observation stream (unlike BranchAndBound).  "tamp_wave", "tamp_pool" as above.
+ * An observation query without solutions makes no children (no error); a pickup query without a path is PORRT_ERR_NO_PATH
+ * (fail_query 1, fail_node = the id the child would have got); a search without a leaf is PORRT_ERR_NO_PATH with fail_node -1.
+ * The policy and the info come through porrt_tamp_rrt_policy / porrt_tamp_rrt_get_info: a later plan of either kind replaces the
+ * earlier one. */
+typedef struct {
+    uint64_t observation_queries, pickup_queries;
+    uint64_t viewpoints_found, viewpoints_kept;    /* solutions of all observation queries; those left after max_viewpoints */
+    uint64_t largest_set;                          /* the most solutions one observation query gave */
+    double   solutions_s;                          /* seconds spent gathering solutions (porrt_solutions' device path) */
+    uint32_t max_viewpoints;
+    uint32_t n_ranks;                              /* levels of the best leaf */
+    uint32_t ranks[64];                            /* the viewpoint rank chosen at each of them (beside zone_order) */
+} porrt_tamp_viewpoints_info;                      /* all zero after porrt_tamp_rrt_plan */
+int64_t  porrt_tamp_rrt_plan_viewpoints(porrt_ctx *ctx, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                                        double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K,
+                                        uint32_t max_viewpoints);
+int      porrt_tamp_rrt_get_viewpoints_info(const porrt_ctx *ctx, porrt_tamp_viewpoints_info *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3297,6 +3297,7 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
 }
 
 #include "porrt_tamp.hpp"
+#include "porrt_tamp_viewpoints.hpp"
 
 extern "C" {
 
@@ -4483,6 +4484,7 @@ int64_t porrt_tamp_rrt_plan(porrt_ctx *c, const double start[2], const double *i
     if (!c) return PORRT_ERR_INVALID;
     int64_t out = 0;
     const int r = abi_guard([&]() {
+        if (c->tamp) memset(&((TampState *)c->tamp.get())->vinfo, 0, sizeof(porrt_tamp_viewpoints_info));
         const int64_t n = tamp_plan(c, start, initial_belief, n_worlds, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K);
         out = n;
         return n < 0 ? (int)n : (int)PORRT_OK;
@@ -4509,6 +4511,54 @@ int porrt_tamp_rrt_get_info(const porrt_ctx *cc, porrt_tamp_info *out) {
     if (!cc->tamp) { memset(out, 0, sizeof *out); out->fail_node = -1; out->fail_zone = -1; out->fail_query = -1; return PORRT_OK; }
     *out = ((const TampState *)cc->tamp.get())->info;
     return PORRT_OK;
+}
+
+// ---- MapShelfDomainTampRRT::plan(.., BranchAndBoundMultipleViewPoints) with the viewpoints in ascending node id (porrt_tamp_viewpoints.hpp)
+int64_t porrt_tamp_rrt_plan_viewpoints(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                                       double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K,
+                                       uint32_t max_viewpoints) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() {
+        const int64_t n = tamp_plan_viewpoints(c, start, initial_belief, n_worlds, max_step, search_radius, n_iter_min, n_iter_max, goal_radius,
+                                               batch_K, max_viewpoints);
+        out = n;
+        return n < 0 ? (int)n : (int)PORRT_OK;
+    });
+    return r < 0 ? r : out;
+}
+
+int porrt_tamp_rrt_get_viewpoints_info(const porrt_ctx *cc, porrt_tamp_viewpoints_info *out) {
+    if (!cc || !out) return PORRT_ERR_INVALID;
+    if (!cc->tamp) { memset(out, 0, sizeof *out); return PORRT_OK; }
+    *out = ((const TampState *)cc->tamp.get())->vinfo;
+    return PORRT_OK;
+}
+
+// RRT::get_solutions of every context, on the device (porrt_solutions.hpp)
+int porrt_solutions(porrt_ctx *const *ctxs, uint32_t n_ctx, uint64_t *n_solutions, uint64_t *n_states, uint64_t *ids, uint64_t *lens,
+                    double *costs, uint64_t cap_solutions, double *xy, uint64_t cap_states) {
+    if (!ctxs || !n_ctx) return PORRT_ERR_INVALID;
+    for (uint32_t q = 0; q < n_ctx; ++q) if (!ctxs[q]) return PORRT_ERR_INVALID;
+    porrt_ctx *c = ctxs[0];
+    if (ids && (!lens || !costs || !xy)) { c->set_err("solutions: ids, lens, costs and xy go together"); return PORRT_ERR_INVALID; }
+    return abi_guard([&]() {
+        TampState &T = tamp_state(c);
+        SolGather G;
+        int r = solutions_select(c, T, ctxs, n_ctx, G);
+        if (r < 0) return r;
+        for (uint32_t q = 0; q < n_ctx; ++q) {
+            const bool has = G.rows[q].status == kSolOk;
+            if (n_solutions) n_solutions[q] = has ? G.rows[q].count : 0;
+            if (n_states) n_states[q] = has ? G.rows[q].n_states : 0;
+        }
+        if (!ids) return (int)PORRT_OK;
+        if (G.n_solutions > cap_solutions || G.n_states > cap_states) {
+            c->set_err("solutions: " + std::to_string(G.n_solutions) + " solutions of " + std::to_string(G.n_states) + " states do not fit the caps");
+            return (int)PORRT_ERR_CAPACITY;
+        }
+        return solutions_write(c, T, G, ids, lens, costs, xy);
+    });
 }
 
 int porrt_best_paths(porrt_ctx *const *ctxs, uint32_t n_ctx, double *xy, uint64_t cap, uint64_t *lens, double *costs) {

@@ -53,14 +53,15 @@ struct TampState {
     int device = 0;
     std::vector<porrt_ctx *> pool;
     uint64_t pool_raster_gen = 0;
-    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging
+    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging, 4 .. 10: porrt_solutions.hpp
     bool valid = false;
     uint32_t nw = 0;
     std::vector<double> xy, beliefs;
     std::vector<int64_t> parents;
     std::vector<uint8_t> leaf;
     porrt_tamp_info info;
-    TampState() { memset(&info, 0, sizeof info); info.fail_node = -1; info.fail_zone = -1; info.fail_query = -1; }
+    porrt_tamp_viewpoints_info vinfo;          // what porrt_tamp_rrt_plan_viewpoints adds (porrt_tamp_viewpoints.hpp); zero after a plan of the other kind
+    TampState() { memset(&info, 0, sizeof info); memset(&vinfo, 0, sizeof vinfo); info.fail_node = -1; info.fail_zone = -1; info.fail_query = -1; }
     ~TampState() {
         for (porrt_ctx *p : pool) porrt_destroy(p);
         (void)hipSetDevice(device);

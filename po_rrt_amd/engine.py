@@ -45,6 +45,7 @@ SYMBOLS = [
     "porrt_graph_file_num_nodes", "porrt_graph_file_num_children", "porrt_graph_file_num_parents", "porrt_graph_file_num_validities",
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
     "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
+    "porrt_solutions", "porrt_tamp_rrt_plan_viewpoints", "porrt_tamp_rrt_get_viewpoints_info",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
@@ -67,6 +68,13 @@ class TampInfo(C.Structure):
                 ("total_s", C.c_double), ("grow_s", C.c_double), ("path_s", C.c_double), ("shortcut_s", C.c_double),
                 ("search_s", C.c_double), ("pool_s", C.c_double), ("goals_s", C.c_double),
                 ("streams", C.c_uint32), ("wave", C.c_uint32), ("pool", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class TampViewpointsInfo(C.Structure):
+    """porrt_tamp_viewpoints_info"""
+    _fields_ = [("observation_queries", C.c_uint64), ("pickup_queries", C.c_uint64), ("viewpoints_found", C.c_uint64),
+                ("viewpoints_kept", C.c_uint64), ("largest_set", C.c_uint64), ("solutions_s", C.c_double),
+                ("max_viewpoints", C.c_uint32), ("n_ranks", C.c_uint32), ("ranks", C.c_uint32 * 64)]
 
 
 class PrmPathsInfo(C.Structure):
@@ -240,6 +248,11 @@ def load_library():
     sig("porrt_tamp_rrt_plan", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_double, C.c_uint32)
     sig("porrt_tamp_rrt_policy", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
     sig("porrt_tamp_rrt_get_info", C.c_int, vp, C.POINTER(TampInfo))
+    sig("porrt_tamp_rrt_plan_viewpoints", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_double,
+        C.c_uint32, C.c_uint32)
+    sig("porrt_tamp_rrt_get_viewpoints_info", C.c_int, vp, C.POINTER(TampViewpointsInfo))
+    sig("porrt_solutions", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+        C.c_void_p, C.c_uint64)
     sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
     sig("porrt_tamp_shortcut_paths", C.c_int, vp, C.c_void_p, _u64p, C.c_uint64, C.c_void_p)
     sig("porrt_qmdp_plan", C.c_int, vp)
@@ -399,13 +412,61 @@ class Engine:
                                                        goal_radius, batch_K))
         finally:
             self.set_option("tamp_search", keep)
+        return self._tamp_policy(n, b.size)
+
+    def _tamp_policy(self, n, nw):
         xy, par = np.zeros((n, 2)), np.zeros(n, dtype=np.int64)
-        leaf, bel = np.zeros(n, dtype=np.uint8), np.zeros((n, b.size))
+        leaf, bel = np.zeros(n, dtype=np.uint8), np.zeros((n, nw))
         cost = C.c_double(0.0)
         self._chk(self._l.porrt_tamp_rrt_policy(self._c, xy.ctypes.data, par.ctypes.data, leaf.ctypes.data, bel.ctypes.data, n,
                                                 C.byref(cost)))
         out = dict(xy=xy, parents=par, is_leaf=leaf, beliefs=bel, expected_cost=cost.value)
         out.update(self.tamp_info())
+        return out
+
+    def plan_tamp_rrt_viewpoints(self, start, belief, max_step=0.1, search_radius=2.0, n_iter_min=2500, n_iter_max=10000, goal_radius=0.05,
+                                 batch_K=128, max_viewpoints=0):
+        """MapShelfDomainTampRRT::plan(.., BranchAndBoundMultipleViewPoints) with the viewpoints of a query walked in ascending
+        node id (porrt_tamp_rrt_plan_viewpoints): the dict of plan_tamp_rrt plus tamp_viewpoints_info().  max_viewpoints (ours, not
+        the reference's): 0 = all, n = the n cheapest solutions per observation query."""
+        b = _f64(belief)
+        n = self._chk(self._l.porrt_tamp_rrt_plan_viewpoints(self._c, _f64(start), b, b.size, max_step, search_radius, n_iter_min, n_iter_max,
+                                                              goal_radius, batch_K, max_viewpoints))
+        out = self._tamp_policy(n, b.size)
+        out.update(self.tamp_viewpoints_info())
+        return out
+
+    def tamp_viewpoints_info(self):
+        i = TampViewpointsInfo()
+        self._chk(self._l.porrt_tamp_rrt_get_viewpoints_info(self._c, C.byref(i)))
+        d = {k: getattr(i, k) for k, _ in TampViewpointsInfo._fields_ if k not in ("ranks", "n_ranks")}
+        d["viewpoint_ranks"] = [int(i.ranks[k]) for k in range(i.n_ranks)]
+        return d
+
+    def solutions(self):
+        """RRT::get_solutions (rrt.rs:195-246) of the last grow, on the device: [(id, path n x 2, cost)] in ascending node id"""
+        return Engine.solutions_batch([self])[0]
+
+    @staticmethod
+    def solutions_batch(engines):
+        """porrt_solutions: per engine [(id, path n x 2, cost)], all trees walked in one device call (no tree is downloaded)"""
+        L, e0, n = engines[0]._l, engines[0], len(engines)
+        arr = (C.c_void_p * n)(*[e._c for e in engines])
+        ns, nst = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        e0._chk(L.porrt_solutions(arr, n, ns.ctypes.data, nst.ctypes.data, None, None, None, 0, None, 0))
+        S, X = int(ns.sum()), int(nst.sum())
+        ids, lens = np.zeros(max(S, 1), dtype=np.uint64), np.zeros(max(S, 1), dtype=np.uint64)
+        costs, xy = np.zeros(max(S, 1)), np.zeros((max(X, 1), 2))
+        e0._chk(L.porrt_solutions(arr, n, ns.ctypes.data, nst.ctypes.data, ids.ctypes.data, lens.ctypes.data, costs.ctypes.data, S,
+                                  xy.ctypes.data, X))
+        out, s, at = [], 0, 0
+        for q in range(n):
+            row = []
+            for _ in range(int(ns[q])):
+                k = int(lens[s])
+                row.append((int(ids[s]), xy[at:at + k].copy(), float(costs[s])))
+                s, at = s + 1, at + k
+            out.append(row)
         return out
 
     def tamp_info(self):
