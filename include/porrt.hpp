@@ -317,6 +317,15 @@ struct Policy {
     }
 };
 
+// pto_policy_refiner.rs:18-21
+struct RefinmentStrategy {
+    enum Kind { kReparent, kPartialShortCut } kind;
+    double radius;
+    size_t n_iterations;
+    static RefinmentStrategy Reparent(double radius) { return {kReparent, radius, 0}; }
+    static RefinmentStrategy PartialShortCut(size_t n_iterations) { return {kPartialShortCut, 0.0, n_iterations}; }
+};
+
 class PTO {
 public:
     uint32_t batch_K = 256;
@@ -467,15 +476,24 @@ public:
     // PTOPolicyRefiner::new(&policy, ..).refine_solution(RefinmentStrategy::PartialShortCut(n_iterations)) (pto_policy_refiner.rs:87-124)
     // of the policy extract_policy() returned last: node states are the refined ones; a piece start the reference's recompose leaves
     // unconnected (after a one-node piece that branches) has no parent
-    Policy refine_policy(size_t n_iterations) {
+    Policy refine_policy(size_t n_iterations) { return refine_policy(RefinmentStrategy::PartialShortCut(n_iterations)); }
+    // refine_solution(strategy).  Reparent(radius) (pto_policy_refiner.rs:209-322) runs through porrt_bg_reparent_policy, with rules of
+    // ours where the reference pins none: bit-equal queue priorities pop in ascending tree node id, a push replaces a queued node's
+    // priority, and the options reparent_max_tree_nodes / reparent_max_pops_per_node cap a piece (PORRT_ERR_CAPACITY).  Its nodes are
+    // belief-graph nodes: original_node_id and belief_state are each node's own, and a piece may come out longer than it went in.
+    Policy refine_policy(const RefinmentStrategy &strategy) {
         Policy policy;
-        const int64_t n = porrt_bg_refine_policy(ctx_.get(), n_iterations, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        auto call = [&](double *xy, uint64_t *oid, int64_t *par, uint8_t *leaf, uint64_t cap, double *cost) {
+            return strategy.kind == RefinmentStrategy::kReparent ? porrt_bg_reparent_policy(ctx_.get(), strategy.radius, xy, oid, par, leaf, cap, cost)
+                                                                 : porrt_bg_refine_policy(ctx_.get(), strategy.n_iterations, xy, oid, par, leaf, cap, cost);
+        };
+        const int64_t n = call(nullptr, nullptr, nullptr, nullptr, 0, nullptr);
         if (n < 0) ctx_.check((int)n);
         std::vector<double> xy(2 * (size_t)n);
         std::vector<uint64_t> oid((size_t)n);
         std::vector<int64_t> par((size_t)n);
         std::vector<uint8_t> leaf((size_t)n);
-        const int64_t m = porrt_bg_refine_policy(ctx_.get(), n_iterations, xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)n, &policy.expected_costs);
+        const int64_t m = call(xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)n, &policy.expected_costs);
         if (m < 0) ctx_.check((int)m);
         const size_t nb = porrt_bg_num_beliefs(ctx_.get());
         std::vector<double> flat(nb * (size_t)n_worlds());

@@ -322,7 +322,8 @@ int      porrt_policies_info(const porrt_ctx *ctx, struct porrt_policies_info *o
  * pieces after it; expected_costs by common.rs:131-154 (norm2).  Deterministic: bit for bit the reference's output.
  * Quirk kept: recompose marks a piece's first node as its start and only a LATER node as its end (`if is_start .. else if is_end`,
  * :348-366), so a one-node piece that branches gets no skeleton edges -- the pieces after it keep parent -1 and it becomes a leaf.
- * RefinmentStrategy::Reparent is not offered.
+ * RefinmentStrategy::Reparent is offered through entry points of its own, with rules of ours where the reference's text pins
+ * none: porrt_bg_reparent_policies below.
  *
  * porrt_bg_refine_policy refines the policy the last porrt_bg_extract_policy handed out (an error if there is none, or if the graph
  * was regrown, the belief graph rebuilt or the expected costs recomputed since).  Refined node k has state xy[2k..], original id
@@ -386,6 +387,64 @@ int64_t  porrt_refine_policies(porrt_ctx *ctx, uint64_t n_policies, const uint64
  * porrt_bg_get_refine_info calls device_s) and of the whole call. */
 struct porrt_refine_policies_info { uint64_t policies, ok, pieces, shortcut_pieces, nodes, distinct_lengths; double ms_device, ms_wall; };
 int      porrt_refine_policies_info(const porrt_ctx *ctx, struct porrt_refine_policies_info *out);
+
+/* ---- the other strategy: PTOPolicyRefiner::refine_solution(RefinmentStrategy::Reparent(radius)) (pto_policy_refiner.rs:209-322), of
+ * one policy or many in one call, on the device.  Per piece of the policy (the decomposition above): build_tree makes the piece's path
+ * a tree and adds belief-graph offsprings within `radius` of a path node; reparent pops the tree's nodes by distance from the root and
+ * hangs every valid neighbour within 0.5 * radius (is_transition_valid under the belief of the piece's first node) under the popped
+ * node when that is strictly shorter; recompose takes the chain from the piece's last path node up to the root.  States never move: a
+ * recomposed node is a belief-graph node, original_ids[k] is ITS id and the expected cost uses ITS belief; a piece may come out shorter
+ * or longer than it went in, so the output is not bounded by the input.  What reads like mistakes in the reference is reproduced (an
+ * offspring is measured from the path node and its edge costs that distance; a grandchild is never tested itself, its children are and
+ * hang from its parent; the visited filter at push time; the upward sum `cost += link.cost` recomputed on every use; priorities of a
+ * reparented node's descendants stay stale; the one-node quirk above).
+ * OURS, NOT THE REFERENCE'S, because the reference's text does not pin them (its queue orders priorities with an Ord that never says
+ * Equal, common.rs:231-253, so bit-equal priorities pop in whatever order the priority_queue crate's heap leaves them):
+ *   - among bit-equal priorities the node with the LOWEST TREE ID is popped (tree ids: the path in order, then offsprings as added);
+ *   - a push on a node in the queue replaces its priority, higher or lower; on a node already popped it inserts it again (the crate's
+ *     documented push, recalled, not verified);
+ *   - no kd-tree is built: the order of a node's neighbours only orders the pushes of one pop, which changes nothing under these rules;
+ *   - two caps that make a policy fail loudly, per piece and independent of what else the call holds: option
+ *     "reparent_max_tree_nodes" (C, default 16384, 1 .. 2^15): a tree of more than C nodes, more than 16 C entries in build_tree's FIFO
+ *     at a time, or more than 256 C pairs of tree nodes within 0.5 * radius of each other are status 4; more pops than
+ *     "reparent_max_pops_per_node" (default 64, 1 .. 64) x the tree's nodes are status 5 (the loop is believed to end, not proven to).
+ *
+ * porrt_bg_reparent_policies works on the policies of the last porrt_bg_extract_policies, under the staleness rule of
+ * porrt_bg_refine_policies.  status[q]: 0 refined; 1 nothing to refine; 2 a transition check reads outside the raster, a door pixel
+ * without zone id or two zones on one segment (every node's checks are made, as every node is popped at least once); 3 a piece whose
+ * input nodes carry different beliefs; 4 and 5 the caps.  Precedence: 3, then over the policy's pieces 4, 2, 5.  A policy with nonzero
+ * status has no nodes and cost +0.0 and does not void the others; porrt_last_error names the first.  The call always does the device
+ * work and keeps the result on the context; it writes ref_off (n + 1), status and expected_costs, returns the total number of nodes
+ * and writes the node arrays only when cap holds the total.  porrt_bg_get_reparented_policies hands the kept result out again without
+ * recomputing (an error when there is none or once the graph, the belief graph or the expected costs have changed).
+ * porrt_bg_reparent_policy refines the policy of the last porrt_bg_extract_policy: a batch of one through the same path with a result
+ * of its own; status 2 is PORRT_ERR_RASTER, 3 PORRT_ERR_INVALID, 4 and 5 PORRT_ERR_CAPACITY; the arrays are written when cap holds them.
+ * porrt_reparent_policies is the explicit form: the belief graph as host arrays (node g: state xy[2g..], belief vector
+ * beliefs[belief_row[g]], children child_ids[child_off[g] .. child_off[g + 1]] in list order, as porrt_extract_policies takes them),
+ * the policies laid end to end (pol_off; original_ids = belief-graph node ids, parents within the policy, -1 for its row 0); states
+ * and beliefs come from the graph; checked on the context's raster with its world validities.  PORRT_ERR_INVALID before any launch for
+ * an id, child or parent out of range, non-finite states, n_worlds != porrt_n_worlds(ctx), or a radius that is negative, NaN or
+ * infinite.  radius = 0.0 is legal: only zero-distance children and copies take part. */
+int64_t  porrt_bg_reparent_policies(porrt_ctx *ctx, double radius, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                    uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_bg_get_reparented_policies(const porrt_ctx *ctx, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                          uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_bg_reparent_policy(porrt_ctx *ctx, double radius, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf,
+                                  uint64_t cap, double *expected_costs);
+int64_t  porrt_reparent_policies(porrt_ctx *ctx, uint64_t n_nodes, const double *xy, const uint32_t *belief_row, const double *beliefs,
+                                 uint32_t n_belief_rows, uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids,
+                                 uint64_t n_policies, const uint64_t *pol_off, const uint64_t *original_ids, const int64_t *parents,
+                                 double radius, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *out_xy,
+                                 uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap);
+/* Counts and times of the context's last porrt_bg_reparent_policies or porrt_reparent_policies: policies given, those with status 0,
+ * pieces worked on, tree nodes in all and of the largest tree, valid-neighbour pairs, pops, reparents, nodes returned, rounds (of as
+ * many pieces as the scratch budget holds); milliseconds per stage (HIP events: build_tree, the neighbour relation, the pop loops,
+ * recomposition with costs) and of the whole call. */
+struct porrt_reparent_policies_info {
+    uint64_t policies, ok, pieces, tree_nodes, max_tree, pairs, pops, reparents, nodes, rounds;
+    double ms_tube, ms_neighbours, ms_pop, ms_recompose, ms_wall;
+};
+int      porrt_reparent_policies_info(const porrt_ctx *ctx, struct porrt_reparent_policies_info *out);
 
 /* ---- the QMDP policy extractor: QMdpPolicyExtractor (src/qmdp_policy_extractor.rs) on the graph of the last
  * porrt_grow(mode PORRT_MODE_PTO) of this context -- no belief graph: one cost-to-goal field per world and a greedy walk.

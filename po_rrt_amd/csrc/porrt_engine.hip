@@ -19,6 +19,7 @@
 #include "porrt_edges.hpp"
 #include "porrt_refine.hpp"
 #include "porrt_refine_batch.hpp"
+#include "porrt_reparent.hpp"
 #include "porrt_qmdp.hpp"
 
 #include <algorithm>
@@ -295,6 +296,13 @@ struct porrt_ctx {
     RefinePoliciesIn refine_in(const PoliciesResult &res, RefineInBuf &buf) const;
     RefinePoliciesIn mm_refine_in(const PoliciesResult &res, RefineInBuf &buf) const;
     int64_t refine_call(const char *who, bool single, const RefinePoliciesIn &in, uint64_t n_iter, const RefinePoliciesOut &out, double *expected_cost);
+    // ---- the Reparent strategy (porrt_reparent.hpp)
+    ReparentResult reparented;             // the last porrt_bg_reparent_policies' answers (stale under policies_current's rule)
+    struct porrt_reparent_policies_info rp_info = {};  // the last BATCHED call's
+    bool rp_done = false;
+    uint32_t opt_reparent_max_tree_nodes = 16384;      // "reparent_max_tree_nodes": a piece whose tree would hold more is status 4
+    uint32_t opt_reparent_max_pops_per_node = 64;      // "reparent_max_pops_per_node": more pops than this x tree nodes is status 5
+    int64_t reparent_call(const char *who, bool single, const ReparentGraph &gr, const RefinePoliciesIn &in, double radius, ReparentResult &res);
     PrmState prm;                          // porrt_grow_prm: grid scratch
     PrmPathsResult prm_paths;              // porrt_prm_plan_paths: the last call's answers (stale once results_tag moves on)
     GrowScratch prm_paths_scratch;         // plan_path, one pair or many: device buffers (rows of costs, dirty flags, queries), kept across calls
@@ -1808,6 +1816,24 @@ int64_t porrt_ctx::refine_call(const char *who, bool single, const RefinePolicie
     if (info.policies == ~0ull) return m;
     if (!single) { refp_info = info; refp_done = m >= 0; }
     else if (m >= 0) { refine_total_s = 1e-3 * info.ms_wall; refine_device_s = 1e-3 * info.ms_device; refine_done = true; }
+    return m;
+}
+
+// The Reparent strategy (porrt_reparent.hpp) on the context's raster, into res.  Many policies: the counts and times go to rp_info /
+// rp_done; single: a batch of one that leaves them alone.
+int64_t porrt_ctx::reparent_call(const char *who, bool single, const ReparentGraph &gr, const RefinePoliciesIn &in, double radius, ReparentResult &res) {
+    HIPCHK(hipSetDevice(device));
+    RunConst g;
+    memset(&g, 0, sizeof g);
+    int r = PORRT_OK;
+    if (has_grid && (r = refine_raster(g))) return r;
+    std::string e;
+    struct porrt_reparent_policies_info info;
+    info.policies = ~0ull;
+    const int64_t m = porrt::reparent_policies(refine, who, gr, in, radius, opt_reparent_max_tree_nodes, opt_reparent_max_pops_per_node, res, g, stream, info, e);
+    if (!e.empty()) set_err(e);
+    if (info.policies == ~0ull) return m;
+    if (!single) { rp_info = info; rp_done = m >= 0; }
     return m;
 }
 
@@ -4259,6 +4285,117 @@ int porrt_refine_policies_info(const porrt_ctx *c, struct porrt_refine_policies_
     return PORRT_OK;
 }
 
+// ---- refine_solution(Reparent(radius)) (porrt_reparent.hpp)
+// the context's belief graph as the Reparent strategy reads it: the graph the expected costs were computed on
+static ReparentGraph reparent_bg_graph(const porrt_ctx *c) {
+    const DpConst &d = c->dp.last;
+    return ReparentGraph{d.nx, d.ny, nullptr, d.child_off, d.child_id, d.B, d.n};
+}
+int64_t porrt_bg_reparent_policies(porrt_ctx *c, double radius, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                   uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int64_t {
+        const PoliciesResult &res = c->policies;
+        c->reparented.valid = false;
+        if (!res.valid) { c->set_err("bg_reparent_policies: no policies to refine: call porrt_bg_extract_policies first"); return PORRT_ERR_INVALID; }
+        if (!c->have_results || !c->policies_current(res)) {
+            c->set_err("bg_reparent_policies: the graph, the belief graph or the expected costs changed since porrt_bg_extract_policies");
+            return PORRT_ERR_INVALID;
+        }
+        if (!ref_off || (!res.status.empty() && (!status || !expected_costs))) { c->set_err("bg_reparent_policies: ref_off, status and expected_costs"); return PORRT_ERR_INVALID; }
+        const int r = c->download(porrt_ctx::DL_TREE);
+        if (r) return r;
+        porrt_ctx::RefineInBuf buf;
+        const int64_t m = c->reparent_call("bg_reparent_policies", false, reparent_bg_graph(c), c->refine_in(res, buf), radius, c->reparented);
+        if (m < 0) return m;
+        c->reparented.tag = res.tag; c->reparented.stamp = res.stamp;
+        return reparent_copy_out(c->reparented, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap);
+    });
+}
+int64_t porrt_bg_get_reparented_policies(const porrt_ctx *c, uint64_t *ref_off, uint8_t *status, double *expected_costs, double *xy,
+                                         uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);                      // (for the error text only)
+    const ReparentResult &res = c->reparented;
+    if (!res.valid) { m->set_err("bg_get_reparented_policies: no answers: call porrt_bg_reparent_policies first"); return PORRT_ERR_INVALID; }
+    if (!c->have_results || !c->costs_current() || res.tag != c->results_tag || res.stamp != c->bg_stamp) {
+        m->set_err("bg_get_reparented_policies: the graph, the belief graph or the expected costs changed since porrt_bg_reparent_policies");
+        return PORRT_ERR_INVALID;
+    }
+    return reparent_copy_out(res, ref_off, status, expected_costs, xy, original_ids, parents, is_leaf, cap);
+}
+int64_t porrt_bg_reparent_policy(porrt_ctx *c, double radius, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap,
+                                 double *expected_costs) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int64_t {
+        if (!c->have_results || !c->policies_current(c->policy)) {
+            c->set_err("reparent_policy: no policy to refine -- call porrt_bg_extract_policy after the last growth, belief graph and expected costs");
+            return PORRT_ERR_INVALID;
+        }
+        const int r = c->download(porrt_ctx::DL_TREE);
+        if (r) return r;
+        porrt_ctx::RefineInBuf buf;
+        ReparentResult one;
+        const int64_t m = c->reparent_call("reparent_policy", true, reparent_bg_graph(c), c->refine_in(c->policy, buf), radius, one);
+        if (m < 0) return m;
+        const uint8_t st = one.status.empty() ? 1 : one.status[0];
+        if (st) return st == 2 ? PORRT_ERR_RASTER : st >= 4 ? PORRT_ERR_CAPACITY : PORRT_ERR_INVALID;     // (reparent_policies has set the message)
+        if ((uint64_t)m <= cap && expected_costs) *expected_costs = one.cost[0];
+        return reparent_copy_out(one, nullptr, nullptr, nullptr, xy, original_ids, parents, is_leaf, cap);
+    });
+}
+int64_t porrt_reparent_policies(porrt_ctx *c, uint64_t n_nodes, const double *xy, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows,
+                                uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids, uint64_t n_policies, const uint64_t *pol_off,
+                                const uint64_t *original_ids, const int64_t *parents, double radius, uint64_t *ref_off, uint8_t *status, double *expected_costs,
+                                double *out_xy, uint64_t *out_original_ids, int64_t *out_parents, uint8_t *out_is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int64_t {
+        const char *W_ = "reparent_policies: ";
+        auto bad = [&](const char *what) { c->set_err(std::string(W_) + what); return (int64_t)PORRT_ERR_INVALID; };
+        if (!n_nodes || n_nodes >= 0xFFFFFFFFull || !xy || !belief_row || !beliefs || !n_belief_rows || !child_off) return bad("the graph's arrays (fewer than 2^32 - 1 nodes)");
+        if (!pol_off || !ref_off || (n_policies && (!status || !expected_costs))) return bad("pol_off, ref_off, status and expected_costs");
+        if ((int)n_worlds != c->n_worlds) return bad("the beliefs need one probability per world of the context");
+        if (!(radius >= 0.0) || std::isinf(radius)) return bad("the radius must be finite and not negative");
+        if (child_off[0] != 0) return bad("child_off[0] = 0");
+        for (uint64_t i = 0; i < n_nodes; ++i) {
+            if (belief_row[i] >= n_belief_rows || child_off[i + 1] < child_off[i]) return bad("a belief row out of range, or child_off decreases");
+            if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) return bad("a state that is not finite");
+        }
+        const uint64_t nc = child_off[n_nodes];
+        if (nc && !child_ids) return bad("child_ids");
+        for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n_nodes) return bad("a child id out of range");
+        if (n_policies >= (1ull << 31) || pol_off[0] != 0) return bad("fewer than 2^31 policies, pol_off[0] = 0");
+        for (uint64_t q = 0; q < n_policies; ++q) if (pol_off[q + 1] < pol_off[q]) return bad("pol_off must not decrease");
+        const uint64_t T = pol_off[n_policies];
+        if (T && (!original_ids || !parents)) return bad("the policies' arrays");
+        std::vector<double> pxy(2 * T);                              // the policy nodes' states and belief rows: the graph's
+        std::vector<uint32_t> prow(T);
+        for (uint64_t k = 0; k < T; ++k) {
+            if (original_ids[k] >= n_nodes) return bad("an original id that is no node of the graph");
+            pxy[2 * k] = xy[2 * original_ids[k]]; pxy[2 * k + 1] = xy[2 * original_ids[k] + 1];
+            prow[k] = belief_row[original_ids[k]];
+        }
+        if (hipSetDevice(c->device) != hipSuccess) return (int64_t)PORRT_ERR_DEVICE;
+        std::vector<double> hx(n_nodes), hy(n_nodes);
+        for (uint64_t i = 0; i < n_nodes; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
+        DeviceUploads dev;
+        ReparentGraph gr{dev.up<double>(hx.data(), n_nodes), dev.up<double>(hy.data(), n_nodes), dev.up<uint32_t>(belief_row, n_nodes),
+                         dev.up<unsigned long long>(child_off, n_nodes + 1), dev.up<uint32_t>(child_ids, nc), 1u, n_nodes};
+        if (!(gr.nx && gr.ny && gr.bvec && gr.child_off && gr.child_id)) { c->set_err(std::string(W_) + "no device memory for the graph"); return (int64_t)PORRT_ERR_DEVICE; }
+        const std::vector<unsigned long long> compat = refine_compat_rows(c, beliefs, n_belief_rows, n_worlds);
+        ReparentResult res;
+        const int64_t m = c->reparent_call("reparent_policies", false, gr,
+                                           RefinePoliciesIn{n_policies, pol_off, pxy.data(), parents, original_ids, prow.data(), beliefs, n_belief_rows, n_worlds, compat.data()}, radius, res);
+        if (m < 0) return m;
+        return reparent_copy_out(res, ref_off, status, expected_costs, out_xy, out_original_ids, out_parents, out_is_leaf, cap);
+    });
+}
+int porrt_reparent_policies_info(const porrt_ctx *c, struct porrt_reparent_policies_info *out) {
+    if (!c || !out || !c->rp_done) return PORRT_ERR_INVALID;
+    *out = c->rp_info;
+    return PORRT_OK;
+}
+
 // ---- the rest of MapShelfDomainTampPRM::plan on the modes of the last porrt_grow_mm_prm (porrt_mmplan.hpp)
 int porrt_mm_build_belief_graph(porrt_ctx *c) {
     if (!c) return PORRT_ERR_INVALID;
@@ -4681,6 +4818,8 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
     else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
     else if (!strcmp(name, "refine_short_lds")) *value = c->opt_refine_short_lds ? 1 : 0;
+    else if (!strcmp(name, "reparent_max_tree_nodes")) *value = c->opt_reparent_max_tree_nodes;
+    else if (!strcmp(name, "reparent_max_pops_per_node")) *value = c->opt_reparent_max_pops_per_node;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -4698,6 +4837,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "mm_lds_nodes")) c->mmp.lds_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, kMmLdsNodes));
     else if (!strcmp(name, "box_table")) { c->opt_box_table = value != 0; c->cls_dirty = true; }
     else if (!strcmp(name, "refine_short_lds")) c->opt_refine_short_lds = value != 0;
+    else if (!strcmp(name, "reparent_max_tree_nodes")) { if (value < 1 || value > (int64_t)kReparentMaxTreeNodesLimit) { c->set_err("reparent_max_tree_nodes: 1 .. 2^15"); return PORRT_ERR_INVALID; } c->opt_reparent_max_tree_nodes = (uint32_t)value; }
+    else if (!strcmp(name, "reparent_max_pops_per_node")) { if (value < 1 || value > 64) { c->set_err("reparent_max_pops_per_node: 1 .. 64"); return PORRT_ERR_INVALID; } c->opt_reparent_max_pops_per_node = (uint32_t)value; }
     else if (!strcmp(name, "gtrack_side")) c->opt_gtrack_side = value != 0;
     else if (!strcmp(name, "pipeline")) {
 #ifndef PORRT_DEV_NONCOOP

@@ -305,7 +305,13 @@ struct RefineHost {
     std::vector<uint8_t> stage;
     uint64_t raster_gen = 0;                         // the raster slot 0 holds (0 = none)
     hipError_t events() { hipError_t e = hipSuccess; for (int k = 0; k < 2 && e == hipSuccess; ++k) if (!ev[k]) e = hipEventCreate(&ev[k]); return e; }
-    void free_device() { scratch.free_all(); for (int k = 0; k < 2; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); ev[k] = nullptr; } }
+    hipEvent_t rp_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // between the stages of a Reparent round (porrt_reparent.hpp; slots 5-9 are its)
+    hipError_t rp_events() { hipError_t e = hipSuccess; for (int k = 0; k < 5 && e == hipSuccess; ++k) if (!rp_ev[k]) e = hipEventCreate(&rp_ev[k]); return e; }
+    void free_device() {
+        scratch.free_all();
+        for (int k = 0; k < 2; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); ev[k] = nullptr; }
+        for (int k = 0; k < 5; ++k) { if (rp_ev[k]) (void)hipEventDestroy(rp_ev[k]); rp_ev[k] = nullptr; }
+    }
 };
 
 // partial_shortcut's draws for a piece of len >= 3 nodes: DiscreteSampler::new() (Pcg64, seed 0), then per iteration
@@ -321,26 +327,31 @@ static void shortcut_draws(uint64_t len, uint64_t n_iter, uint2 *out) {
     }
 }
 
-// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of the policies of `in`, checked on the raster
-// g describes (all zero: no grid).  Everything on the device: one upload, the decomposition, one small download (per policy its counts,
-// per piece of >= 3 nodes its length), one table of draws per distinct length (the draws do not depend on the commits) uploaded with the
-// launch order (longest piece first), the shortcuts of all pieces in one launch (short_lds: pieces of <= kRefineShortLdsNodes nodes in a
-// launch of their own), offsets, recomposition with the expected costs, one download.  out.cap = 0 launches no shortcut kernel.  Fills
-// info (counts and times of this call) and, where a policy's status is not 0 or the call fails, err (prefixed with who).
-// Returns the refined nodes of the policies with status 0.
-static int64_t refine_policies(RefineHost &h, const char *who, const RefinePoliciesIn &in, uint64_t n_iter, const RefinePoliciesOut &out, const RunConst &g,
-                               bool short_lds, hipStream_t stream, struct porrt_refine_policies_info &info, std::string &err) {
-    const double t0 = now_s();
+// What the decomposition of a call leaves: the device tables (pc; the raster view g sits at the start of d, the compatibility rows at
+// d + o_cp), and on the host per policy its record and per long piece its length.
+struct RefineDecomposed {
+    RefinePolConst pc{};
+    uint8_t *d = nullptr;
+    size_t o_cp = 0;
+    uint64_t T = 0;                                                  // policy nodes in all
+    std::vector<uint8_t> first;
+    const RefinePolRecord *rec = nullptr;
+    const uint32_t *long_len = nullptr;
+};
+
+// Checks the policies of `in`, uploads them with g and decomposes them (k_refine_policies_decompose), into slot 2 of h's scratch.
+// Returns 0, an error code (err says why), or 1 when the policies are all empty (nothing uploaded).
+static int refine_decompose(RefineHost &h, const std::string &W_, const RefinePoliciesIn &in, const RefinePoliciesOut &out, const RunConst &g, hipStream_t stream,
+                            RefineDecomposed &dc, std::string &err) {
     const uint64_t n = in.n;
     const uint32_t n_rows = in.n_rows, nw = in.nw;
-    const std::string W_ = std::string(who) + ": ";
     if (!in.pol_off || !out.ref_off || (n && (!out.status || !out.cost))) { err = W_ + "pol_off, ref_off, status and expected_costs"; return PORRT_ERR_INVALID; }
     if (n >= (1ull << 31) || in.pol_off[0] != 0) { err = W_ + "fewer than 2^31 policies, pol_off[0] = 0"; return PORRT_ERR_INVALID; }
     for (uint64_t q = 0; q < n; ++q)
         if (in.pol_off[q + 1] < in.pol_off[q]) { err = W_ + "pol_off must not decrease"; return PORRT_ERR_INVALID; }
     const uint64_t T = in.pol_off[n];
+    dc.T = T;
     if (T >= (1ull << 31)) { err = W_ + "fewer than 2^31 nodes in all"; return PORRT_ERR_INVALID; }
-    if (n_iter >= (1ull << 31)) { err = W_ + "at most 2^31 - 1 iterations"; return PORRT_ERR_INVALID; }
     if (T && (!in.xy || !in.parents || !in.original || !in.belief || !in.beliefs || !n_rows || !nw)) { err = W_ + "the policies' arrays"; return PORRT_ERR_INVALID; }
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     // the upload: RunConst | pol_off | compat | beliefs | xy | original ids | parents (checked, 32 bits) | belief rows
@@ -364,16 +375,7 @@ static int64_t refine_policies(RefineHost &h, const char *who, const RefinePolic
             }
         }
     }
-    info = {};
-    info.policies = n;
-    out.ref_off[0] = 0;
-    if (T == 0) {                                                    // nothing but empty policies: no launch
-        for (uint64_t q = 0; q < n; ++q) { out.ref_off[q + 1] = 0; out.status[q] = 1; out.cost[q] = 0.0; }
-        if (n) err = W_ + "policy 0: no policy to refine";
-        info.ms_wall = 1e3 * (now_s() - t0);
-        return 0;
-    }
-    const bool shortcuts = out.cap != 0 && n_iter != 0;
+    if (T == 0) return 1;
     memcpy(stage, &g, sizeof g);
     memcpy(stage + o_off, in.pol_off, (n + 1) * 8);
     memcpy(stage + o_cp, in.compat, (size_t)n_rows * 8);
@@ -390,7 +392,7 @@ static int64_t refine_policies(RefineHost &h, const char *who, const RefinePolic
                  w_v = take(T * 8), w_err = take(n * 4), w_rec = take(n * sizeof(RefinePolRecord)), w_len = take(L * 4), bytes = at;
     uint8_t *d = nullptr;
     HIPCHK_ERR(h.scratch.get(2, d, bytes));
-    RefinePolConst pc{};
+    RefinePolConst &pc = dc.pc;
     pc.pol_off = (const unsigned long long *)(d + o_off); pc.in_xy = (const double *)(d + o_xy); pc.in_orig = (const unsigned long long *)(d + o_or);
     pc.in_parent = (const int32_t *)(d + o_pa); pc.in_belief = (const uint32_t *)(d + o_br); pc.beliefs = (const double *)(d + o_bel);
     pc.nw = nw; pc.n_policies = (uint32_t)n;
@@ -402,11 +404,47 @@ static int64_t refine_policies(RefineHost &h, const char *who, const RefinePolic
     HIPCHK_ERR(hipMemcpyAsync(d, stage, up_bytes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_refine_policies_decompose, dim3((uint32_t)n), dim3(64), 0, stream, pc);
     HIPCHK_ERR(hipGetLastError());
-    std::vector<uint8_t> first(bytes - w_rec);
-    HIPCHK_ERR(hipMemcpyAsync(first.data(), d + w_rec, bytes - w_rec, hipMemcpyDeviceToHost, stream));
+    dc.first.resize(bytes - w_rec);
+    HIPCHK_ERR(hipMemcpyAsync(dc.first.data(), d + w_rec, bytes - w_rec, hipMemcpyDeviceToHost, stream));
     HIPCHK_ERR(hipStreamSynchronize(stream));
-    const RefinePolRecord *rec = (const RefinePolRecord *)first.data();
-    const uint32_t *long_len = (const uint32_t *)(first.data() + (w_len - w_rec));
+    dc.d = d; dc.o_cp = o_cp;
+    dc.rec = (const RefinePolRecord *)dc.first.data();
+    dc.long_len = (const uint32_t *)(dc.first.data() + (w_len - w_rec));
+    return 0;
+}
+
+// PTOPolicyRefiner::refine_solution(PartialShortCut(n_iter)) (pto_policy_refiner.rs:87-124) of the policies of `in`, checked on the raster
+// g describes (all zero: no grid).  Everything on the device: one upload, the decomposition, one small download (per policy its counts,
+// per piece of >= 3 nodes its length; refine_decompose, shared with the Reparent strategy of porrt_reparent.hpp), one table of draws per
+// distinct length (the draws do not depend on the commits) uploaded with the launch order (longest piece first), the shortcuts of all
+// pieces in one launch (short_lds: pieces of <= kRefineShortLdsNodes nodes in a launch of their own), offsets, recomposition with the
+// expected costs, one download.  out.cap = 0 launches no shortcut kernel.  Fills info (counts and times of this call) and, where a
+// policy's status is not 0 or the call fails, err (prefixed with who).  Returns the refined nodes of the policies with status 0.
+static int64_t refine_policies(RefineHost &h, const char *who, const RefinePoliciesIn &in, uint64_t n_iter, const RefinePoliciesOut &out, const RunConst &g,
+                               bool short_lds, hipStream_t stream, struct porrt_refine_policies_info &info, std::string &err) {
+    const double t0 = now_s();
+    const uint64_t n = in.n;
+    const std::string W_ = std::string(who) + ": ";
+    if (n_iter >= (1ull << 31)) { err = W_ + "at most 2^31 - 1 iterations"; return PORRT_ERR_INVALID; }
+    RefineDecomposed dc;
+    const int dr_ = refine_decompose(h, W_, in, out, g, stream, dc, err);
+    if (dr_ < 0) return dr_;
+    info = {};
+    info.policies = n;
+    out.ref_off[0] = 0;
+    if (dr_ == 1) {                                                  // nothing but empty policies: no launch
+        for (uint64_t q = 0; q < n; ++q) { out.ref_off[q + 1] = 0; out.status[q] = 1; out.cost[q] = 0.0; }
+        if (n) err = W_ + "policy 0: no policy to refine";
+        info.ms_wall = 1e3 * (now_s() - t0);
+        return 0;
+    }
+    const bool shortcuts = out.cap != 0 && n_iter != 0;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    RefinePolConst &pc = dc.pc;
+    uint8_t *const d = dc.d;
+    const size_t o_cp = dc.o_cp;
+    const RefinePolRecord *rec = dc.rec;
+    const uint32_t *long_len = dc.long_len;
     // the launch order (longest first) and one table of draws per distinct length
     uint64_t M = 0;
     std::vector<uint64_t> keys;                                      // length << 32 | row of longs

@@ -50,6 +50,8 @@ SYMBOLS = [
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
     "porrt_bg_refine_policies", "porrt_mm_refine_policies", "porrt_refine_policies", "porrt_refine_policies_info",
+    "porrt_bg_reparent_policies", "porrt_bg_get_reparented_policies", "porrt_bg_reparent_policy", "porrt_reparent_policies",
+    "porrt_reparent_policies_info",
 ]
 
 
@@ -100,6 +102,12 @@ class RefinePoliciesInfo(C.Structure):
     """struct porrt_refine_policies_info"""
     _fields_ = [("policies", C.c_uint64), ("ok", C.c_uint64), ("pieces", C.c_uint64), ("shortcut_pieces", C.c_uint64), ("nodes", C.c_uint64),
                 ("distinct_lengths", C.c_uint64), ("ms_device", C.c_double), ("ms_wall", C.c_double)]
+
+
+class ReparentPoliciesInfo(C.Structure):
+    """struct porrt_reparent_policies_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("policies", "ok", "pieces", "tree_nodes", "max_tree", "pairs", "pops", "reparents", "nodes", "rounds")] + \
+               [(k, C.c_double) for k in ("ms_tube", "ms_neighbours", "ms_pop", "ms_recompose", "ms_wall")]
 
 
 class TreeDeviceView(C.Structure):
@@ -272,6 +280,12 @@ def load_library():
     sig("porrt_refine_policies", C.c_int64, vp, C.c_uint64, _u64p, _f64p, _i64p, _u64p, _u32p, _f64p, C.c_uint32, C.c_uint32, C.c_uint64,
         _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_refine_policies_info", C.c_int, vp, C.POINTER(RefinePoliciesInfo))
+    sig("porrt_bg_reparent_policies", C.c_int64, vp, C.c_double, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_bg_get_reparented_policies", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_bg_reparent_policy", C.c_int64, vp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
+    sig("porrt_reparent_policies", C.c_int64, vp, C.c_uint64, _f64p, _u32p, _f64p, C.c_uint32, C.c_uint32, _u64p, _u32p, C.c_uint64, _u64p, _u64p, _i64p,
+        C.c_double, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_reparent_policies_info", C.c_int, vp, C.POINTER(ReparentPoliciesInfo))
     _LIB = L
     return L
 
@@ -879,6 +893,76 @@ class Engine:
         i = RefinePoliciesInfo()
         self._chk(self._l.porrt_refine_policies_info(self._c, C.byref(i)))
         return {k: getattr(i, k) for k, _ in RefinePoliciesInfo._fields_}
+
+    # ---- the Reparent strategy (PTOPolicyRefiner::refine_solution(Reparent(radius)), pto_policy_refiner.rs:209-322)
+    def reparent_policies_raw(self, radius):
+        """porrt_bg_reparent_policies as arrays: ref_off [n + 1], status [n], expected costs [n], states, original ids, parents, leaf
+        flags.  The call computes and keeps its answers; the node arrays come from porrt_bg_get_reparented_policies."""
+        n = self._n_policies("bg")
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        total = self._chk(int(self._l.porrt_bg_reparent_policies(self._c, float(radius), off, status, cost, None, None, None, None, 0)))
+        xy, oid, par, leaf = np.zeros((total, 2)), np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
+        if total:
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            self._chk(int(self._l.porrt_bg_get_reparented_policies(self._c, None, None, None, p(xy), p(oid), p(par), p(leaf), total)))
+        return off, status[:n], cost[:n], xy, oid, par, leaf
+
+    @staticmethod
+    def _reparented_list(off, status, cost, xy, oid, par, leaf):
+        out = []
+        for q in range(len(status)):
+            a, b = int(off[q]), int(off[q + 1])
+            out.append(None if status[q] else ((xy[a:b], oid[a:b], par[a:b], leaf[a:b]), float(cost[q])))
+        return out, status
+
+    def reparent_policies(self, radius):
+        """every policy of the last extract_policies, refined with the Reparent strategy in one device call: a list with
+        ((states [k, 2], belief node ids, parents, leaf flags), expected cost) per policy -- None where there is none -- and the status
+        array (0 refined, 1 nothing to refine, 2 raster fault, 3 a piece with different beliefs, 4 a tree or a work area beyond
+        option reparent_max_tree_nodes, 5 the pop cap).  Ties between equal priorities pop the lowest tree node id (ours)."""
+        return self._reparented_list(*self.reparent_policies_raw(radius))
+
+    def reparent_policy(self, radius):
+        """the policy of the last extract_policy, refined with the Reparent strategy: (states, belief node ids, parents, leaf flags),
+        expected cost"""
+        return self._refined(lambda xy, oid, par, leaf, cap, cost: self._l.porrt_bg_reparent_policy(self._c, float(radius), xy, oid, par, leaf, cap, cost))
+
+    def reparent_policies_explicit(self, xy, belief_row, beliefs, child_off, child_ids, policies, radius):
+        """the same on a belief graph given as arrays (node g: state xy[g], belief vector beliefs[belief_row[g]], children
+        child_ids[child_off[g]:child_off[g + 1]]) and policies given as a list of (belief-graph node ids, parents within the policy),
+        checked on this context's raster (porrt_reparent_policies)"""
+        xy = _f64(xy).reshape(-1, 2)
+        row = np.ascontiguousarray(belief_row, dtype=np.uint32)
+        bel = _f64(beliefs).reshape(len(beliefs), -1)
+        coff = np.ascontiguousarray(child_off, dtype=np.uint64)
+        cid = np.ascontiguousarray(child_ids, dtype=np.uint32)
+        if len(cid) == 0:
+            cid = np.zeros(1, dtype=np.uint32)
+        n = len(policies)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        for q, pol in enumerate(policies):
+            off[q + 1] = off[q] + np.uint64(len(pol[0]))
+        total = int(off[n])
+        cat = lambda i, dt: (np.ascontiguousarray(np.concatenate([np.asarray(pol[i], dtype=dt).reshape(-1) for pol in policies])) if total else np.zeros(1, dtype=dt))
+        oid, par = cat(0, np.uint64), cat(1, np.int64)
+        cap = 2 * total + 1024
+        while True:
+            roff, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+            oxy, ooid, opar, oleaf = np.zeros((cap, 2)), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            m = self._chk(int(self._l.porrt_reparent_policies(self._c, len(row), xy, row, bel, bel.shape[0], bel.shape[1], coff, cid, n, off, oid, par,
+                                                              float(radius), roff, status, cost, p(oxy), p(ooid), p(opar), p(oleaf), cap)))
+            if m <= cap:
+                break
+            cap = m                                                  # (the answers did not fit: once more with room for them)
+        return self._reparented_list(roff, status[:n], cost[:n], oxy[:m], ooid[:m], opar[:m], oleaf[:m])
+
+    def reparent_policies_info(self):
+        """porrt_reparent_policies_info of the last batched Reparent call: policies, ok, pieces, tree_nodes, max_tree, pairs, pops,
+        reparents, nodes, rounds, ms_tube, ms_neighbours, ms_pop, ms_recompose, ms_wall"""
+        i = ReparentPoliciesInfo()
+        self._chk(self._l.porrt_reparent_policies_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in ReparentPoliciesInfo._fields_}
 
     def refine_info(self):
         a, b = C.c_double(0), C.c_double(0)
