@@ -757,7 +757,8 @@ enum class TampSearch { AStar, BranchAndBound, BranchAndBoundMultipleViewPoints 
 
 // MapShelfDomainTampRRT (map_shelves_tamp_rrt.rs:135-291): plan(.., TampSearch::BranchAndBound) on the device
 // (porrt_tamp_rrt_plan).  AStar and BranchAndBoundMultipleViewPoints throw: their expansion order cannot be
-// pinned.  plan_multiple_viewpoints (:293-430, porrt_tamp_rrt_plan_viewpoints) is the latter with the viewpoints
+// pinned.  plan_astar (:432-563, porrt_tamp_rrt_plan_astar) is the former with equal priorities popped in
+// ascending search node id.  plan_multiple_viewpoints (:293-430, porrt_tamp_rrt_plan_viewpoints) is the latter with the viewpoints
 // of a query walked in ascending node id -- one of the orders the reference may take, which is why it is a method of its own.
 // The stream mode, wave width and pool size are the context's options tamp_streams / tamp_wave / tamp_pool.
 class MapShelfDomainTampRRT {
@@ -773,6 +774,9 @@ public:
         if (search == TampSearch::BranchAndBoundMultipleViewPoints)
             throw std::runtime_error("MapShelfDomainTampRRT: TampSearch::BranchAndBoundMultipleViewPoints walks a HashSet; "
                                      "plan_multiple_viewpoints() offers it with the viewpoints in ascending node id");
+        if (search == TampSearch::AStar)
+            throw std::runtime_error("MapShelfDomainTampRRT: TampSearch::AStar's order among equal priorities cannot be pinned; "
+                                     "plan_astar() offers it with ties popped in ascending search node id");
         if (search != TampSearch::BranchAndBound) throw std::runtime_error("MapShelfDomainTampRRT: only TampSearch::BranchAndBound is supported");
         const int64_t r = porrt_tamp_rrt_plan(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(), max_step,
                                               search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
@@ -786,6 +790,15 @@ public:
                                                          max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K, max_viewpoints);
         return read_policy(r, initial_belief_state.size());
     }
+    // plan_astar (:432-563) with bit-equal priorities popped in ascending search node id and a prior of positive entries only
+    // (ours, not the reference's; porrt_tamp_rrt_plan_astar).  tamp_wave speculates, it never changes the result.
+    Policy plan_astar(State start, const BeliefState &initial_belief_state, double max_step, double search_radius, size_t n_iter_min,
+                      size_t n_iter_max, uint32_t batch_K = 128) {
+        const int64_t r = porrt_tamp_rrt_plan_astar(ctx_.get(), start.data(), initial_belief_state.data(), (uint32_t)initial_belief_state.size(),
+                                                    max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
+        return read_policy(r, initial_belief_state.size());
+    }
+    porrt_tamp_astar_info astar_info() const { porrt_tamp_astar_info i; ctx_.check(porrt_tamp_rrt_get_astar_info(ctx_.get(), &i)); return i; }
     porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
     porrt_tamp_viewpoints_info viewpoints_info() const { porrt_tamp_viewpoints_info i; ctx_.check(porrt_tamp_rrt_get_viewpoints_info(ctx_.get(), &i)); return i; }
     const Context &context() const { return ctx_; }

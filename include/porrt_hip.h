@@ -724,7 +724,9 @@ porrt_tree_device_view porrt_tree_device(const porrt_ctx *ctx);
  * its value at entry on return), 1 (default) = one stream per search edge, seeded from the context's sampler seed and the edge's
  * zone prefix (splitmix64), which makes the result independent of the expansion order; "tamp_wave" (mode 1) search nodes popped at
  * once, their queries grown together; "tamp_pool" worker contexts that grow them (made on first use, freed with this context);
- * "tamp_search" 0 = BranchAndBound, 1 = AStar and 2 = BranchAndBoundMultipleViewPoints are refused (PORRT_ERR_INVALID).
+ * "tamp_search" 0 = BranchAndBound, 1 = AStar and 2 = BranchAndBoundMultipleViewPoints are refused (PORRT_ERR_INVALID): the
+ * reference's order among equal priorities / its HashSet walk cannot be pinned.  Both searches are offered with a stated order
+ * through entry points of their own: porrt_tamp_rrt_plan_astar and porrt_tamp_rrt_plan_viewpoints below.
  * The shuffles draw from the context's discrete sampler, which runs on across plans.  The context's goal is replaced.
  * Returns the policy's node count, PORRT_ERR_INVALID (n_worlds != zones, a prior whose sum is not within 0.001 of 1),
  * PORRT_ERR_NO_PATH, or another error. */
@@ -796,6 +798,45 @@ int64_t  porrt_tamp_rrt_plan_viewpoints(porrt_ctx *ctx, const double start[2], c
                                         double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K,
                                         uint32_t max_viewpoints);
 int      porrt_tamp_rrt_get_viewpoints_info(const porrt_ctx *ctx, porrt_tamp_viewpoints_info *out);
+
+/* ---- MapShelfDomainTampRRT::plan(.., TampSearch::AStar) (plan_astar, map_shelves_tamp_rrt.rs:432-563): a
+ * best-first search over zone orders.  The node of lowest priority is popped and makes one child per remaining zone in zone order
+ * (no shuffle: the discrete sampler is not touched), two RRT* queries per child as in porrt_tamp_rrt_plan;
+ *     ec = u.ec + rp * (obs_cost + belief[t] * pickup_cost),  priority = ec + rp * sum_z belief[z] * norm2(observation_state, zone_pos[z])
+ * over the child's remaining zones in order; the first popped node without remaining zones is the solution.
+ * A separate entry point on purpose: porrt_tamp_rrt_plan with "tamp_search" 1 stays refused, because the reference's Priority never
+ * compares Equal (common.rs:235-239) and its order among equal priorities is its heap's.  OURS, not the reference's:
+ *   - bit-equal priorities pop in ASCENDING SEARCH NODE ID; a node's children get the next ids, in zone order, when the node is
+ *     popped; +0.0 and -0.0 are equal;
+ *   - a prior with an entry that is not > 0 is PORRT_ERR_INVALID (the reference's priorities would all be NaN below the last
+ *     positive zone).
+ * "tamp_streams" 0: the context's own stream across the queries in the sequential order, set back on return, one node per wave.
+ * 1 (default): the per-edge streams of porrt_tamp_rrt_plan.  A node's cost and priority are then functions of its zone prefix, and
+ * "tamp_wave" = W speculates: when the top of the queue has no computed children, it and the next best non-leaf entries without
+ * children (up to W) are expanded in one pair of batches; the children enter the queue only when their parent is popped.  At every
+ * W the policy, zone_order, search_cost, search_nodes and every node's id, ec and priority are those of W = 1; queries, waves and
+ * `speculated` differ.  A query without a path is PORRT_ERR_NO_PATH only when its parent is popped: fail_node = the id the child
+ * would have got, fail_zone / fail_query = the first failing child in zone order (the observation query fails before the pickup).
+ * The paths of all children stay on the device in an arena ("tamp_arena_states": its initial capacity in states, >= 1024; it grows
+ * between gathers, PORRT_ERR_CAPACITY if it cannot); only the winning chain's paths are ever copied out of it.
+ * The policy and the info come through porrt_tamp_rrt_policy / porrt_tamp_rrt_get_info (pruned = 0; waves = rounds of expansion). */
+typedef struct {
+    uint64_t speculated;         /* expansions whose node was never popped */
+    uint64_t arena_states;       /* capacity of the path arena after the plan */
+    uint64_t arena_used;         /* states the plan's paths took in it */
+    uint64_t arena_grown;        /* times it grew during the plan */
+    double   children_s;         /* seconds: uploading, running and fetching k_astar_children */
+    double   chain_s;            /* seconds on the device: k_astar_chain */
+} porrt_tamp_astar_info;         /* describes the last porrt_tamp_rrt_plan_astar */
+int64_t  porrt_tamp_rrt_plan_astar(porrt_ctx *ctx, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                                   double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K);
+int      porrt_tamp_rrt_get_astar_info(const porrt_ctx *ctx, porrt_tamp_astar_info *out);
+/* the search nodes of the last porrt_tamp_rrt_plan_astar in id order (also after PORRT_ERR_NO_PATH: the nodes made so far):
+ * parents (-1 = root), targets (zone; -1 = root), ec, priority.  Returns their count; with cap below it nothing is written. */
+int64_t  porrt_tamp_astar_nodes(const porrt_ctx *ctx, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap);
+/* porrt_tamp_shortcut_paths through the shortcut's device-resident input form: the paths are first put into the A* search's arena
+ * and reach the shortcut's staging planes by k_astar_chain, as the winning chain of a plan does.  Same result, bit for bit. */
+int      porrt_tamp_shortcut_paths_resident(porrt_ctx *ctx, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out);
 
 #ifdef __cplusplus
 }

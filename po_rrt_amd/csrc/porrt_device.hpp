@@ -3323,6 +3323,82 @@ __global__ __launch_bounds__(64) void k_best_path(const RunConst *__restrict__ r
     out[row0 + blockIdx.y] = o;
 }
 
+// ---- the TAMP-RRT A* search (porrt_tamp_astar.hpp)
+// k_astar_children: one lane per child of a wave of expansions.  The child's two best paths stay in the arena; what the search
+// needs of them -- expected cost, priority, where the zone was seen -- is worked out here from their BestPath records, so that one
+// record per child is all the host fetches.  The arithmetic is plan_astar's (map_shelves_tamp_rrt.rs:505-540), in its order:
+//   ec = u.ec + rp * (obs_cost + belief[t] * pickup_cost)
+//   h  = fold from 0.0 over the remaining zones in order: h + belief[z] * norm2(observation_state, zone_pos[z])   (common.rs:203-213)
+//   priority = ec + rp * h
+// The remaining zones of a node are always in ascending order (the root's are 0 .. n, a child's are its parent's without one),
+// so a bit mask walked from bit 0 is that order.
+struct AstarChildIn {
+    double parent_ec, rp;                 // u.expected_cost; the child's reaching probability
+    unsigned long long remaining;         // bit z = zone z is still to visit below the child
+    uint32_t obs_row, pick_row;           // rows of the two BestPath arrays; pick_row = 0xFFFFFFFF: no pickup query ran
+    uint32_t belief_row, target;          // row of the beliefs array (one per parent), the child's zone
+};
+enum : uint32_t { kAstarOk = 0, kAstarNoObs = 1, kAstarNoPick = 2, kAstarSlot = 3, kAstarScratch = 4 };
+struct AstarChildOut {
+    double ec, priority, ox, oy, obs_cost, pick_cost;
+    uint32_t obs_off, obs_len, pick_off, pick_len;
+    uint32_t status, cursor;              // cursor: the arena's, as this launch found it (the same in every record)
+};
+__device__ __forceinline__ uint32_t astar_status(uint32_t best_path_status, uint32_t no_path) {
+    return best_path_status == 0u ? (uint32_t)kAstarOk : best_path_status == 1u ? no_path : best_path_status == 2u ? (uint32_t)kAstarScratch : (uint32_t)kAstarSlot;
+}
+__global__ __launch_bounds__(64) void k_astar_children(const AstarChildIn *__restrict__ in, uint32_t n, const BestPath *__restrict__ obs,
+                                                       const BestPath *__restrict__ pick, const double *__restrict__ beliefs, uint32_t nw,
+                                                       const double2 *__restrict__ zone_pos, const uint32_t *__restrict__ cursor,
+                                                       AstarChildOut *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const AstarChildIn a = in[i];
+    AstarChildOut o;
+    o.ec = o.priority = o.ox = o.oy = o.obs_cost = o.pick_cost = 0.0;
+    o.obs_off = o.obs_len = o.pick_off = o.pick_len = 0;
+    o.cursor = *cursor;
+    const BestPath bo = obs[a.obs_row];
+    o.status = astar_status(bo.status, kAstarNoObs);
+    if (o.status == kAstarOk) {
+        o.ox = bo.end_x; o.oy = bo.end_y; o.obs_cost = bo.cost; o.obs_off = bo.off; o.obs_len = bo.len;
+        if (a.pick_row == 0xFFFFFFFFu) o.status = kAstarNoPick;
+        else {
+            const BestPath bp = pick[a.pick_row];
+            o.status = astar_status(bp.status, kAstarNoPick);
+            if (o.status == kAstarOk) { o.pick_cost = bp.cost; o.pick_off = bp.off; o.pick_len = bp.len; }
+        }
+    }
+    if (o.status == kAstarOk) {
+        const double *b = beliefs + (size_t)a.belief_row * nw;
+        o.ec = a.parent_ec + a.rp * (o.obs_cost + b[a.target] * o.pick_cost);
+        double h = 0.0;
+        for (uint32_t z = 0; z < nw; ++z) {
+            if (!((a.remaining >> z) & 1ull)) continue;
+            const double2 zp = zone_pos[z];
+            double d2 = 0.0, dx = zp.x - o.ox;
+            d2 += dx * dx;
+            dx = zp.y - o.oy;
+            d2 += dx * dx;
+            h = h + b[z] * sqrt(d2);
+        }
+        o.priority = o.ec + a.rp * h;
+    }
+    out[i] = o;
+}
+
+// k_astar_chain: one wave per path of the winning chain, from the arena into the shortcut's staging planes (k_tamp_shortcut then
+// runs on them where they are).  Only these 2 x depth paths of a plan are ever moved.
+struct AstarChainPath { uint32_t src, len, dst, pad; };
+__global__ __launch_bounds__(64) void k_astar_chain(const AstarChainPath *__restrict__ paths, const double2 *__restrict__ arena,
+                                                    double *__restrict__ x, double *__restrict__ y) {
+    const AstarChainPath p = paths[blockIdx.x];
+    for (uint32_t k = threadIdx.x; k < p.len; k += 64u) {
+        const double2 s = arena[(size_t)p.src + k];
+        x[(size_t)p.dst + k] = s.x; y[(size_t)p.dst + k] = s.y;
+    }
+}
+
 // ---- the rows' own step schedules (porrt_grow_batch with per-member n_iter_min / n_iter_max and the reference's loop condition)
 // The plan of a row, a function of (n_iter_min, n_iter_max, K) alone: steps of K iterations up to n_iter_min (the last one
 // shorter), where the condition `i < n_iter_min || (no solution && i < n_iter_max)` (rrt.rs:109, pto.rs:67) is first looked at,

@@ -335,6 +335,7 @@ struct porrt_ctx {
     int opt_tamp_streams = 1;              // "tamp_streams": 0 = one stream across the search (the reference's), 1 = one stream per search edge
     uint32_t opt_tamp_wave = 128;          // "tamp_wave": search nodes popped per wave (tamp_streams = 1; 128: fastest measured)
     uint32_t opt_tamp_pool = 512;          // "tamp_pool": worker contexts (queries of one porrt_grow_batch)
+    uint64_t opt_tamp_arena_states = 1ull << 20;   // "tamp_arena_states": initial capacity of the A* search's path arena (states of 16 B; it grows)
     int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints) are refused
     int mm_upload_roadmaps();
     int mm_build_belief_graph();
@@ -3324,6 +3325,7 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
 
 #include "porrt_tamp.hpp"
 #include "porrt_tamp_viewpoints.hpp"
+#include "porrt_tamp_astar.hpp"
 
 extern "C" {
 
@@ -4672,6 +4674,56 @@ int porrt_tamp_rrt_get_viewpoints_info(const porrt_ctx *cc, porrt_tamp_viewpoint
     return PORRT_OK;
 }
 
+// ---- MapShelfDomainTampRRT::plan(.., AStar) with equal priorities popped in ascending search node id (porrt_tamp_astar.hpp)
+int64_t porrt_tamp_rrt_plan_astar(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
+                                  double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() {
+        const int64_t n = tamp_plan_astar(c, start, initial_belief, n_worlds, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K);
+        out = n;
+        return n < 0 ? (int)n : (int)PORRT_OK;
+    });
+    return r < 0 ? r : out;
+}
+
+int porrt_tamp_rrt_get_astar_info(const porrt_ctx *cc, porrt_tamp_astar_info *out) {
+    if (!cc || !out) return PORRT_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    if (!cc->tamp || !((const TampState *)cc->tamp.get())->astar) return PORRT_OK;
+    *out = ((const AstarState *)((const TampState *)cc->tamp.get())->astar.get())->info;
+    return PORRT_OK;
+}
+
+int64_t porrt_tamp_astar_nodes(const porrt_ctx *cc, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap) {
+    if (!cc) return PORRT_ERR_INVALID;
+    if (!cc->tamp || !((const TampState *)cc->tamp.get())->astar) return 0;
+    const AstarState &A = *(const AstarState *)((const TampState *)cc->tamp.get())->astar.get();
+    const uint64_t n = A.parents.size();
+    if (cap < n) return (int64_t)n;
+    if (parents) memcpy(parents, A.parents.data(), n * sizeof(int64_t));
+    if (targets) memcpy(targets, A.targets.data(), n * sizeof(int32_t));
+    if (ec) memcpy(ec, A.ec.data(), n * sizeof(double));
+    if (priority) memcpy(priority, A.priority.data(), n * sizeof(double));
+    return (int64_t)n;
+}
+
+int porrt_tamp_shortcut_paths_resident(porrt_ctx *c, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out) {
+    if (!c || !offsets || !out || (!xy && offsets[n_paths])) return PORRT_ERR_INVALID;
+    if (!c->has_grid) { c->set_err("tamp_shortcut: the shortcut checks segments on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }
+    if (offsets[0] != 0) { c->set_err("tamp_shortcut: offsets[0] must be 0"); return PORRT_ERR_INVALID; }
+    for (uint64_t i = 0; i < n_paths; ++i) if (offsets[i + 1] < offsets[i]) { c->set_err("tamp_shortcut: offsets must not decrease"); return PORRT_ERR_INVALID; }
+    if (offsets[n_paths] >= (1ull << 31)) { c->set_err("tamp_shortcut: too many states"); return PORRT_ERR_INVALID; }
+    return abi_guard([&]() {
+        std::vector<double> v(xy, xy + 2 * offsets[n_paths]);
+        std::vector<uint64_t> off(offsets, offsets + n_paths + 1);
+        const int r = tamp_shortcut_resident(c, tamp_state(c), v, off);
+        if (r < 0) return r;
+        memcpy(out, v.data(), v.size() * sizeof(double));
+        return (int)PORRT_OK;
+    });
+}
+
 // RRT::get_solutions of every context, on the device (porrt_solutions.hpp)
 int porrt_solutions(porrt_ctx *const *ctxs, uint32_t n_ctx, uint64_t *n_solutions, uint64_t *n_states, uint64_t *ids, uint64_t *lens,
                     double *costs, uint64_t cap_solutions, double *xy, uint64_t cap_states) {
@@ -4813,6 +4865,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "tamp_wave")) *value = c->opt_tamp_wave;
     else if (!strcmp(name, "tamp_pool")) *value = c->opt_tamp_pool;
     else if (!strcmp(name, "tamp_search")) *value = c->opt_tamp_search;
+    else if (!strcmp(name, "tamp_arena_states")) *value = (int64_t)c->opt_tamp_arena_states;
     else if (!strcmp(name, "prm_rows")) *value = c->opt_prm_rows;
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
@@ -4867,6 +4920,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "tamp_streams")) { if (value != 0 && value != 1) { c->set_err("tamp_streams: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_tamp_streams = (int)value; }
     else if (!strcmp(name, "tamp_wave")) { if (value < 1 || value > 65536) { c->set_err("tamp_wave: 1 .. 65536"); return PORRT_ERR_INVALID; } c->opt_tamp_wave = (uint32_t)value; }
     else if (!strcmp(name, "tamp_pool")) { if (value < 1 || value > 4096) { c->set_err("tamp_pool: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_tamp_pool = (uint32_t)value; }
+    else if (!strcmp(name, "tamp_arena_states")) { if (value < 1024 || value > (1ll << 31)) { c->set_err("tamp_arena_states: 1024 (one row's gather) .. 2^31"); return PORRT_ERR_INVALID; } c->opt_tamp_arena_states = (uint64_t)value; }
     else if (!strcmp(name, "tamp_search")) { if (value < 0 || value > 2) { c->set_err("tamp_search: 0 (BranchAndBound), 1 (AStar), 2 (BranchAndBoundMultipleViewPoints)"); return PORRT_ERR_INVALID; } c->opt_tamp_search = (int)value; }
     else if (!strcmp(name, "prm_rows")) { if (value < 1 || value > 4096) { c->set_err("prm_rows: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_prm_rows = (uint32_t)value; }
     else if (!strcmp(name, "prm_xcd_rows")) c->opt_prm_xcd_rows = value != 0;

@@ -53,7 +53,7 @@ struct TampState {
     int device = 0;
     std::vector<porrt_ctx *> pool;
     uint64_t pool_raster_gen = 0;
-    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging, 4 .. 10: porrt_solutions.hpp
+    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging, 4 .. 10: porrt_solutions.hpp, 11 .. 16: porrt_tamp_astar.hpp
     bool valid = false;
     uint32_t nw = 0;
     std::vector<double> xy, beliefs;
@@ -61,6 +61,7 @@ struct TampState {
     std::vector<uint8_t> leaf;
     porrt_tamp_info info;
     porrt_tamp_viewpoints_info vinfo;          // what porrt_tamp_rrt_plan_viewpoints adds (porrt_tamp_viewpoints.hpp); zero after a plan of the other kind
+    std::shared_ptr<void> astar;               // what porrt_tamp_rrt_plan_astar keeps (porrt_tamp_astar.hpp): path arena, search nodes, its info
     TampState() { memset(&info, 0, sizeof info); memset(&vinfo, 0, sizeof vinfo); info.fail_node = -1; info.fail_zone = -1; info.fail_query = -1; }
     ~TampState() {
         for (porrt_ctx *p : pool) porrt_destroy(p);
@@ -183,8 +184,19 @@ static int tamp_gather(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, uint3
     return PORRT_OK;
 }
 
-// shortcut (map_shelves_tamp_rrt.rs:565-617) of every path, in place: one wave per path of >= 3 states, one launch
-static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> &xy, const std::vector<uint64_t> &off, double *dev_s) {
+// the device-resident input form of tamp_shortcut_device: path i is `len` states of `arena` from paths[i].src on (k_astar_chain
+// copies them into the staging planes; paths[i].dst is filled in here)
+struct TampChainSource {
+    const double2 *arena = nullptr;
+    std::vector<AstarChainPath> paths;
+    hipEvent_t ev = nullptr;                   // the caller's: recorded before k_astar_chain
+    double chain_s = 0.0;                      // out: k_astar_chain on the device
+};
+
+// shortcut (map_shelves_tamp_rrt.rs:565-617) of every path, in place: one wave per path of >= 3 states, one launch.  With `src` the
+// states come from the device (xy is only written: every path as it leaves the shortcut, the short ones copied).
+static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> &xy, const std::vector<uint64_t> &off, double *dev_s,
+                                TampChainSource *src = nullptr) {
     const size_t n_paths = off.size() - 1, ns = off.back();
     std::vector<RefinePiece> longs;
     std::vector<std::pair<uint32_t, uint32_t>> len_at;
@@ -201,7 +213,7 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
         longs.push_back({(uint32_t)off[i], (uint32_t)len, at, 0u});
     }
     if (dev_s) *dev_s = 0.0;
-    if (longs.empty()) return PORRT_OK;
+    if (longs.empty() && (!src || ns == 0)) return PORRT_OK;
     if (ns >= (1ull << 31)) { c->set_err("tamp_shortcut: too many states"); return PORRT_ERR_INVALID; }
     HIPCHK_CTX(c, hipSetDevice(c->device));
     RunConst g;
@@ -212,14 +224,19 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
     auto up8 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t nd = len_at.size() * n_iter;
     const size_t o_pc = up8(sizeof(RunConst)), o_dr = o_pc + up8(longs.size() * sizeof(RefinePiece)), o_x = o_dr + up8(nd * sizeof(uint2)),
-                 o_y = o_x + ns * 8, o_err = o_y + ns * 8, bytes = o_err + 16;
+                 o_y = o_x + ns * 8, o_err = o_y + ns * 8, o_cp = o_err + 16, bytes = o_cp + (src ? n_paths * sizeof(AstarChainPath) : 0);
     std::vector<uint8_t> stage(bytes, 0);
     memcpy(stage.data(), &g, sizeof g);
     memcpy(stage.data() + o_pc, longs.data(), longs.size() * sizeof(RefinePiece));
     uint2 *dr = (uint2 *)(stage.data() + o_dr);
     for (const auto &la : len_at) shortcut_draws(la.first, n_iter, dr + la.second);      // DiscreteSampler::new() per path (:576-584)
     double *sx = (double *)(stage.data() + o_x), *sy = (double *)(stage.data() + o_y);
-    for (size_t k = 0; k < ns; ++k) { sx[k] = xy[2 * k]; sy[k] = xy[2 * k + 1]; }
+    if (src) {
+        for (size_t i = 0; i < n_paths; ++i) { src->paths[i].dst = (uint32_t)off[i]; src->paths[i].len = (uint32_t)(off[i + 1] - off[i]); }
+        memcpy(stage.data() + o_cp, src->paths.data(), n_paths * sizeof(AstarChainPath));
+    } else {
+        for (size_t k = 0; k < ns; ++k) { sx[k] = xy[2 * k]; sy[k] = xy[2 * k + 1]; }
+    }
     uint8_t *d = nullptr;
     HIPCHK_CTX(c, T.scratch.get(3, d, bytes));
     HIPCHK_CTX(c, c->refine.events());
@@ -227,16 +244,28 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
     rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = nullptr;
     rc.draws = (const uint2 *)(d + o_dr); rc.x = (double *)(d + o_x); rc.y = (double *)(d + o_y); rc.err = (uint32_t *)(d + o_err);
     rc.n_pieces = (uint32_t)longs.size(); rc.n_iter = n_iter;
-    HIPCHK_CTX(c, hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    if (src) {                                   // the planes are filled on the device: everything but them goes up
+        HIPCHK_CTX(c, hipMemcpyAsync(d, stage.data(), o_x, hipMemcpyHostToDevice, c->stream));
+        HIPCHK_CTX(c, hipMemcpyAsync(d + o_err, stage.data() + o_err, bytes - o_err, hipMemcpyHostToDevice, c->stream));
+        HIPCHK_CTX(c, hipEventRecord(src->ev, c->stream));
+        hipLaunchKernelGGL(k_astar_chain, dim3((uint32_t)n_paths), dim3(64), 0, c->stream, (const AstarChainPath *)(d + o_cp), src->arena, rc.x, rc.y);
+        HIPCHK_CTX(c, hipGetLastError());
+    } else {
+        HIPCHK_CTX(c, hipMemcpyAsync(d, stage.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    }
     HIPCHK_CTX(c, hipEventRecord(c->refine.ev[0], c->stream));
-    hipLaunchKernelGGL(k_tamp_shortcut, dim3(rc.n_pieces), dim3(64), 0, c->stream, rc);
+    if (rc.n_pieces) hipLaunchKernelGGL(k_tamp_shortcut, dim3(rc.n_pieces), dim3(64), 0, c->stream, rc);
     HIPCHK_CTX(c, hipGetLastError());
     HIPCHK_CTX(c, hipEventRecord(c->refine.ev[1], c->stream));
-    HIPCHK_CTX(c, hipMemcpyAsync(stage.data() + o_x, d + o_x, bytes - o_x, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK_CTX(c, hipMemcpyAsync(stage.data() + o_x, d + o_x, o_cp - o_x, hipMemcpyDeviceToHost, c->stream));
     HIPCHK_CTX(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     HIPCHK_CTX(c, hipEventElapsedTime(&ms, c->refine.ev[0], c->refine.ev[1]));
     if (dev_s) *dev_s = 1e-3 * (double)ms;
+    if (src) {
+        HIPCHK_CTX(c, hipEventElapsedTime(&ms, src->ev, c->refine.ev[0]));
+        src->chain_s = 1e-3 * (double)ms;
+    }
     uint32_t err = 0;
     memcpy(&err, stage.data() + o_err, 4);
     if (err) { c->set_err("tamp_shortcut: a segment reads outside the raster (the reference panics)"); return PORRT_ERR_RASTER; }
@@ -305,8 +334,9 @@ static inline double tamp_expected_cost(const std::vector<int64_t> &parent, cons
     }
 }
 
-// build_policy (:619-663) on the chain root .. leaf
-static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id) {
+// build_policy (:619-663) on the chain root .. leaf.  With `src` the nodes' paths give only their lengths: the states are on the
+// device (one entry of src->paths per path, in the order they are laid out here).
+static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id, TampChainSource *src = nullptr) {
     std::vector<int64_t> chain;
     for (int64_t k = leaf_id; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
     std::reverse(chain.begin(), chain.end());
@@ -321,7 +351,7 @@ static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampN
     }
     const double t0 = now_s();
     double dev_s = 0.0;
-    const int r = tamp_shortcut_device(c, T, xy, off, &dev_s);
+    const int r = tamp_shortcut_device(c, T, xy, off, &dev_s, src);
     if (r < 0) return r;
     T.info.shortcut_s = now_s() - t0;
     const uint32_t nw = T.nw;

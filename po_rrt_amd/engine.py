@@ -46,6 +46,7 @@ SYMBOLS = [
     "porrt_graph_file_num_worlds", "porrt_graph_file_get",
     "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
     "porrt_solutions", "porrt_tamp_rrt_plan_viewpoints", "porrt_tamp_rrt_get_viewpoints_info",
+    "porrt_tamp_rrt_plan_astar", "porrt_tamp_rrt_get_astar_info", "porrt_tamp_astar_nodes", "porrt_tamp_shortcut_paths_resident",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
@@ -70,6 +71,12 @@ class TampInfo(C.Structure):
                 ("total_s", C.c_double), ("grow_s", C.c_double), ("path_s", C.c_double), ("shortcut_s", C.c_double),
                 ("search_s", C.c_double), ("pool_s", C.c_double), ("goals_s", C.c_double),
                 ("streams", C.c_uint32), ("wave", C.c_uint32), ("pool", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class TampAstarInfo(C.Structure):
+    """porrt_tamp_astar_info"""
+    _fields_ = [("speculated", C.c_uint64), ("arena_states", C.c_uint64), ("arena_used", C.c_uint64), ("arena_grown", C.c_uint64),
+                ("children_s", C.c_double), ("chain_s", C.c_double)]
 
 
 class TampViewpointsInfo(C.Structure):
@@ -259,6 +266,11 @@ def load_library():
     sig("porrt_tamp_rrt_plan_viewpoints", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_double,
         C.c_uint32, C.c_uint32)
     sig("porrt_tamp_rrt_get_viewpoints_info", C.c_int, vp, C.POINTER(TampViewpointsInfo))
+    sig("porrt_tamp_rrt_plan_astar", C.c_int64, vp, _f64p, _f64p, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_double,
+        C.c_uint32)
+    sig("porrt_tamp_rrt_get_astar_info", C.c_int, vp, C.POINTER(TampAstarInfo))
+    sig("porrt_tamp_astar_nodes", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_tamp_shortcut_paths_resident", C.c_int, vp, C.c_void_p, _u64p, C.c_uint64, C.c_void_p)
     sig("porrt_solutions", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
         C.c_void_p, C.c_uint64)
     sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
@@ -450,6 +462,32 @@ class Engine:
         out.update(self.tamp_viewpoints_info())
         return out
 
+    def plan_tamp_rrt_astar(self, start, belief, max_step=0.1, search_radius=2.0, n_iter_min=2500, n_iter_max=10000, goal_radius=0.05,
+                            batch_K=128):
+        """MapShelfDomainTampRRT::plan(.., AStar) with equal priorities popped in ascending search node id
+        (porrt_tamp_rrt_plan_astar): the dict of plan_tamp_rrt plus tamp_astar_info().  tamp_streams / tamp_wave / tamp_pool as for
+        plan_tamp_rrt (the wave width speculates; it never changes the result), tamp_arena_states = the path arena's first size."""
+        b = _f64(belief)
+        n = self._chk(self._l.porrt_tamp_rrt_plan_astar(self._c, _f64(start), b, b.size, max_step, search_radius, n_iter_min, n_iter_max,
+                                                         goal_radius, batch_K))
+        out = self._tamp_policy(n, b.size)
+        out.update(self.tamp_astar_info())
+        return out
+
+    def tamp_astar_info(self):
+        i = TampAstarInfo()
+        self._chk(self._l.porrt_tamp_rrt_get_astar_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in TampAstarInfo._fields_}
+
+    def tamp_astar_nodes(self):
+        """the search nodes of the last plan_tamp_rrt_astar in id order (after a failed plan: those made so far):
+        dict(parents, targets, ec, priority)"""
+        n = self._chk(self._l.porrt_tamp_astar_nodes(self._c, None, None, None, None, 0))
+        par, tgt = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        ec, pr = np.zeros(n), np.zeros(n)
+        self._chk(self._l.porrt_tamp_astar_nodes(self._c, par.ctypes.data, tgt.ctypes.data, ec.ctypes.data, pr.ctypes.data, n))
+        return dict(parents=par, targets=tgt, ec=ec, priority=pr)
+
     def tamp_viewpoints_info(self):
         i = TampViewpointsInfo()
         self._chk(self._l.porrt_tamp_rrt_get_viewpoints_info(self._c, C.byref(i)))
@@ -505,14 +543,16 @@ class Engine:
             at += n
         return out
 
-    def tamp_shortcut(self, paths):
-        """the planner's shortcut (map_shelves_tamp_rrt.rs:565-617) of each path (a list of n x 2 arrays), on the device"""
+    def tamp_shortcut(self, paths, resident=False):
+        """the planner's shortcut (map_shelves_tamp_rrt.rs:565-617) of each path (a list of n x 2 arrays), on the device.
+        resident: through the device-resident input form the A* planner uses (the paths start in its arena)"""
         arrs = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 2)) for p in paths]
         off = np.zeros(len(arrs) + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(a) for a in arrs]) if arrs else []
         xy = np.concatenate(arrs) if arrs and off[-1] else np.zeros((0, 2))
         out = np.zeros_like(xy)
-        self._chk(self._l.porrt_tamp_shortcut_paths(self._c, xy.ctypes.data, off, len(arrs), out.ctypes.data))
+        call = self._l.porrt_tamp_shortcut_paths_resident if resident else self._l.porrt_tamp_shortcut_paths
+        self._chk(call(self._c, xy.ctypes.data, off, len(arrs), out.ctypes.data))
         return [out[int(off[k]):int(off[k + 1])].copy() for k in range(len(arrs))]
 
     def get_option(self, name):
