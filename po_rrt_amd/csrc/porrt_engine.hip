@@ -336,7 +336,7 @@ struct porrt_ctx {
     uint32_t opt_tamp_wave = 128;          // "tamp_wave": search nodes popped per wave (tamp_streams = 1; 128: fastest measured)
     uint32_t opt_tamp_pool = 512;          // "tamp_pool": worker contexts (queries of one porrt_grow_batch)
     uint64_t opt_tamp_arena_states = 1ull << 20;   // "tamp_arena_states": initial capacity of the A* search's path arena (states of 16 B; it grows)
-    int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints) are refused
+    int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; porrt_tamp_rrt_plan refuses 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints), which have entry points of their own
     int mm_upload_roadmaps();
     int mm_build_belief_graph();
     int mm_compute_expected_costs();
@@ -3323,6 +3323,29 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
     return PORRT_ERR_CAPACITY;
 }
 
+// The run of the argument that starts at q0: its length m when ctxs[q0 .. q0 + m) are exactly the slots 0 .. m of their leader's
+// LAST batch (porrt_grow_batch leaves one such run per sub-batch), with the leader's step count and all with results; 0 when
+// there is none.  Only then does the leader's RunConst array (d_rcarr) hold these members, row r = ctxs[q0 + r]: this is the one
+// place that decides which RunConst array a kernel over several contexts may read.
+static uint32_t porrt_batch_run(porrt_ctx *const *ctxs, uint32_t n, uint32_t q0) {
+    const porrt_ctx *L = ctxs[q0]->batch_leader;
+    const uint32_t m = L ? L->batch_size : 0;
+    if (m == 0 || q0 + m > n) return 0;
+    for (uint32_t r = 0; r < m; ++r) {
+        const porrt_ctx *x = ctxs[q0 + r];
+        if (!x->have_results || x->batch_leader != L || x->batch_slot != r || x->n_steps != L->n_steps || x->batch_gen != L->batch_gen_counter) return 0;
+    }
+    return m;
+}
+
+// the rows a kernel with one workgroup per context (blockIdx.y = row) reads from q0 on: the run there, else ctxs[q0] alone on its own RunConst
+struct BatchRows { const RunConst *rcp; uint32_t rows, steps; };
+static BatchRows porrt_batch_rows(porrt_ctx *const *ctxs, uint32_t n, uint32_t q0) {
+    const uint32_t m = porrt_batch_run(ctxs, n, q0);
+    if (m) return {ctxs[q0]->batch_leader->d_rcarr, m, (uint32_t)ctxs[q0]->batch_leader->n_steps};
+    return {ctxs[q0]->d_rc.p, 1u, (uint32_t)ctxs[q0]->n_steps};
+}
+
 #include "porrt_tamp.hpp"
 #include "porrt_tamp_viewpoints.hpp"
 #include "porrt_tamp_astar.hpp"
@@ -3884,20 +3907,14 @@ int porrt_best_cost_batch(porrt_ctx *const *ctxs, uint32_t n_ctx, double *costs)
     if (!ctxs || !n_ctx || !costs) return PORRT_ERR_INVALID;
     for (uint32_t q = 0; q < n_ctx; ++q) if (!ctxs[q]) return PORRT_ERR_INVALID;
     const double inf = std::numeric_limits<double>::infinity();
-    // runs of the argument that are exactly some leader's last batch, in its order (porrt_grow_batch leaves one such run per
-    // sub-batch): one launch per run, all of them in flight before the first wait
+    // one launch per run of the argument (porrt_batch_run), all of them in flight before the first wait; a context outside a run
+    // is served alone below
     std::vector<char> together(n_ctx, 0);
     std::vector<porrt_ctx *> launched;
     for (uint32_t q0 = 0; q0 < n_ctx;) {
+        const uint32_t m = porrt_batch_run(ctxs, n_ctx, q0);
+        if (!m) { ++q0; continue; }
         porrt_ctx *L = ctxs[q0]->batch_leader;
-        const uint32_t m = L ? L->batch_size : 0;
-        bool run = L != nullptr && m > 0 && q0 + m <= n_ctx;
-        for (uint32_t r = 0; r < m && run; ++r) {
-            const porrt_ctx *c = ctxs[q0 + r];
-            run = c->have_results && c->batch_leader == L && c->batch_slot == r && c->n_steps == L->n_steps &&
-                  c->batch_gen == L->batch_gen_counter;        // the leader's LAST batch: its RunConst array holds these members
-        }
-        if (!run) { ++q0; continue; }
         if (hipSetDevice(L->device) != hipSuccess) return PORRT_ERR_DEVICE;
         for (uint32_t r = 0; r < m; ++r) (void)hipMemsetAsync(ctxs[q0 + r]->d_bccursor.p, 0, sizeof(uint32_t), L->stream);
         hipLaunchKernelGGL(k_best_cost, dim3(1, m), dim3(1024), 0, L->stream, (const RunConst *)L->d_rcarr, (uint32_t)L->n_steps);
@@ -4623,7 +4640,6 @@ int64_t porrt_tamp_rrt_plan(porrt_ctx *c, const double start[2], const double *i
     if (!c) return PORRT_ERR_INVALID;
     int64_t out = 0;
     const int r = abi_guard([&]() {
-        if (c->tamp) memset(&((TampState *)c->tamp.get())->vinfo, 0, sizeof(porrt_tamp_viewpoints_info));
         const int64_t n = tamp_plan(c, start, initial_belief, n_worlds, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K);
         out = n;
         return n < 0 ? (int)n : (int)PORRT_OK;

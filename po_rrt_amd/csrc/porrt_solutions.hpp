@@ -146,8 +146,8 @@ struct SolGather {
     SolRow *d_rows = nullptr;
 };
 
-// Launch 1 on every row of ctxs[0 .. n) and one small download.  Runs of the argument that are exactly some leader's last batch get
-// one launch (as tamp_gather); other contexts go one by one.  Scratch slots 4 .. 10 of the calling context's TampState.
+// Launch 1 on every row of ctxs[0 .. n) and one small download.  A run of the argument (porrt_batch_run) gets one launch; other
+// contexts go one by one.  Scratch: the kSlotSol* slots of the calling context's TampState.
 static int solutions_select(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, uint32_t n, SolGather &G) {
     HIPCHK_CTX(c, hipSetDevice(c->device));
     uint64_t id_cap = 0;
@@ -159,23 +159,16 @@ static int solutions_select(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, 
     }
     if (id_cap >= (1ull << 31)) { c->set_err("solutions: more than 2^31 nodes in one call"); return PORRT_ERR_CAPACITY; }
     uint32_t *d_cur = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(4, G.d_ids, id_cap));
-    HIPCHK_CTX(c, T.scratch.get(5, G.d_lens, id_cap));
-    HIPCHK_CTX(c, T.scratch.get(6, G.d_rows, n));
-    HIPCHK_CTX(c, T.scratch.get(7, d_cur, 1));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolIds, G.d_ids, id_cap));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolLens, G.d_lens, id_cap));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolRows, G.d_rows, n));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolCursor, d_cur, 1));
     hipStream_t st = c->stream;
     HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
     G.runs.clear();
     for (uint32_t q0 = 0; q0 < n;) {
-        porrt_ctx *L = ctxs[q0]->batch_leader;
-        const uint32_t m = L ? L->batch_size : 0;
-        bool run = L != nullptr && m > 0 && q0 + m <= n;
-        for (uint32_t r = 0; r < m && run; ++r) {
-            const porrt_ctx *x = ctxs[q0 + r];
-            run = x->batch_leader == L && x->batch_slot == r && x->n_steps == L->n_steps && x->batch_gen == L->batch_gen_counter;
-        }
-        SolGather::Run R = run ? SolGather::Run{L->d_rcarr, q0, m, (uint32_t)L->n_steps}
-                               : SolGather::Run{ctxs[q0]->d_rc.p, q0, 1u, (uint32_t)ctxs[q0]->n_steps};
+        const BatchRows B = porrt_batch_rows(ctxs, n, q0);
+        const SolGather::Run R{B.rcp, q0, B.rows, B.steps};
         hipLaunchKernelGGL(k_solutions_select, dim3(1, R.rows), dim3(kSolThreads), 0, st, R.rcp, R.steps, R.q0, G.d_ids, G.d_lens, (uint32_t)id_cap, d_cur, G.d_rows);
         HIPCHK_CTX(c, hipGetLastError());
         G.runs.push_back(R);
@@ -203,9 +196,9 @@ static int solutions_write(porrt_ctx *c, TampState &T, const SolGather &G, uint6
     SolBase *d_bases = nullptr;
     unsigned long long *d_oi = nullptr;                  // ids | lens | costs, n_solutions each
     double2 *d_xy = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(8, d_bases, n));
-    HIPCHK_CTX(c, T.scratch.get(9, d_oi, 3 * (size_t)G.n_solutions));
-    HIPCHK_CTX(c, T.scratch.get(10, d_xy, (size_t)G.n_states));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolBases, d_bases, n));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolOut, d_oi, 3 * (size_t)G.n_solutions));
+    HIPCHK_CTX(c, T.scratch.get(kSlotSolXy, d_xy, (size_t)G.n_states));
     unsigned long long *d_ol = d_oi + G.n_solutions;
     double *d_oc = (double *)(d_ol + G.n_solutions);
     hipStream_t st = c->stream;

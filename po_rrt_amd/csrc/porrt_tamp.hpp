@@ -22,7 +22,10 @@
 #pragma once
 
 #include <algorithm>
+#include <functional>
 #include <memory>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -49,11 +52,35 @@ struct TampNode {
     double obs_cost = 0, pick_cost = 0;
 };
 
+// The slots of TampState::scratch and who owns each; a new user takes a new name at the end.
+enum TampSlot : size_t {
+    kSlotBestMeta = 0,        // tamp_gather: BestPath per row
+    kSlotPathArena,           // tamp_gather: the rows' paths
+    kSlotPathCursor,          // tamp_gather: the arena's cursor
+    kSlotShortcut,            // tamp_shortcut_device: its staging area
+    kSlotSolIds,              // solutions_select (porrt_solutions.hpp): id arena
+    kSlotSolLens,             //   lengths beside the ids
+    kSlotSolRows,             //   SolRow per row
+    kSlotSolCursor,           //   the id arena's cursor
+    kSlotSolBases,            // solutions_write: SolBase per row
+    kSlotSolOut,              //   ids | lens | costs
+    kSlotSolXy,               //   states
+    kSlotAstarCursor,         // tamp_plan_astar (porrt_tamp_astar.hpp): the plan arena's cursor
+    kSlotAstarZonePos,        //   zone positions
+    kSlotAstarChildIn,        //   k_astar_children: AstarChildIn per child
+    kSlotAstarBeliefs,        //   belief rows of a wave
+    kSlotAstarChildOut,       //   AstarChildOut per child
+    kSlotAstarPick,           //   BestPath per pickup row
+    // the A* plan's BestPath per observation row shares tamp_gather's buffer: safe because tamp_plan_astar gathers with
+    // tamp_best_paths into its own arena and never calls tamp_gather, and no other call runs on the context during a plan
+    kSlotAstarObs = kSlotBestMeta,
+};
+
 struct TampState {
     int device = 0;
     std::vector<porrt_ctx *> pool;
     uint64_t pool_raster_gen = 0;
-    GrowScratch scratch;                       // 0: BestPath per row, 1: path arena, 2: arena cursor, 3: shortcut staging, 4 .. 10: porrt_solutions.hpp, 11 .. 16: porrt_tamp_astar.hpp
+    GrowScratch scratch;                       // slots: TampSlot
     bool valid = false;
     uint32_t nw = 0;
     std::vector<double> xy, beliefs;
@@ -113,8 +140,25 @@ static int tamp_ensure_pool(porrt_ctx *c, TampState &T, uint32_t want) {
     return PORRT_OK;
 }
 
-// The best path of every row ctxs[0 .. n) after its growth (rrt.rs:183-193, 223-227): k_best_cost + k_best_path per batch of the
-// call, one download of the rows' descriptors, one of the paths.  paths[q] root first; ok[q] = 0 for "No solution found".
+// k_best_cost + k_best_path of the rows ctxs[0 .. n) after their growth, on c's stream: one launch triple per run of the argument
+// (porrt_batch_run), a context outside a run alone.  Row q's path is appended to `arena` through the cursor *d_cur in a slot of
+// kTampPathSlot states, its record goes to d_meta[q]; nothing is downloaded.
+static int tamp_best_paths(porrt_ctx *c, porrt_ctx *const *ctxs, uint32_t n, double2 *arena, uint32_t *d_cur, BestPath *d_meta) {
+    hipStream_t st = c->stream;
+    for (uint32_t q0 = 0; q0 < n;) {
+        const BatchRows B = porrt_batch_rows(ctxs, n, q0);
+        if (B.rows == 1 && !ctxs[q0]->have_results) { c->set_err("tamp: a query has no results"); return PORRT_ERR_INVALID; }
+        hipLaunchKernelGGL(k_best_path_reset, dim3(1, B.rows), dim3(64), 0, st, B.rcp);
+        hipLaunchKernelGGL(k_best_cost, dim3(1, B.rows), dim3(1024), 0, st, B.rcp, B.steps);
+        hipLaunchKernelGGL(k_best_path, dim3(1, B.rows), dim3(64), 0, st, B.rcp, q0, kTampPathSlot, arena, d_cur, d_meta);
+        HIPCHK_CTX(c, hipGetLastError());
+        q0 += B.rows;
+    }
+    return PORRT_OK;
+}
+
+// The best path of every row ctxs[0 .. n) after its growth (rrt.rs:183-193, 223-227): tamp_best_paths into scratch, one download
+// of the rows' descriptors, one of the paths.  paths[q] root first; ok[q] = 0 for "No solution found".
 static int tamp_gather(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, uint32_t n, std::vector<std::vector<double>> &paths,
                        std::vector<double> &costs, std::vector<char> &ok) {
     const double t0 = now_s();
@@ -122,34 +166,13 @@ static int tamp_gather(porrt_ctx *c, TampState &T, porrt_ctx *const *ctxs, uint3
     BestPath *d_meta = nullptr;
     double2 *d_arena = nullptr;
     uint32_t *d_cur = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(0, d_meta, n));
-    HIPCHK_CTX(c, T.scratch.get(1, d_arena, (size_t)n * kTampPathSlot));
-    HIPCHK_CTX(c, T.scratch.get(2, d_cur, 1));
+    HIPCHK_CTX(c, T.scratch.get(kSlotBestMeta, d_meta, n));
+    HIPCHK_CTX(c, T.scratch.get(kSlotPathArena, d_arena, (size_t)n * kTampPathSlot));
+    HIPCHK_CTX(c, T.scratch.get(kSlotPathCursor, d_cur, 1));
     hipStream_t st = c->stream;
     HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
-    for (uint32_t q0 = 0; q0 < n;) {
-        // runs of the argument that are exactly some leader's last batch (as porrt_best_cost_batch): one launch per run
-        porrt_ctx *L = ctxs[q0]->batch_leader;
-        const uint32_t m = L ? L->batch_size : 0;
-        bool run = L != nullptr && m > 0 && q0 + m <= n;
-        for (uint32_t r = 0; r < m && run; ++r) {
-            const porrt_ctx *x = ctxs[q0 + r];
-            run = x->have_results && x->batch_leader == L && x->batch_slot == r && x->n_steps == L->n_steps && x->batch_gen == L->batch_gen_counter;
-        }
-        const RunConst *rcp;
-        uint32_t rows, steps;
-        if (run) { rcp = L->d_rcarr; rows = m; steps = (uint32_t)L->n_steps; }
-        else {
-            porrt_ctx *x = ctxs[q0];
-            if (!x->have_results) { c->set_err("tamp: a query has no results"); return PORRT_ERR_INVALID; }
-            rcp = x->d_rc.p; rows = 1; steps = (uint32_t)x->n_steps;
-        }
-        hipLaunchKernelGGL(k_best_path_reset, dim3(1, rows), dim3(64), 0, st, rcp);
-        hipLaunchKernelGGL(k_best_cost, dim3(1, rows), dim3(1024), 0, st, rcp, steps);
-        hipLaunchKernelGGL(k_best_path, dim3(1, rows), dim3(64), 0, st, rcp, q0, kTampPathSlot, d_arena, d_cur, d_meta);
-        HIPCHK_CTX(c, hipGetLastError());
-        q0 += rows;
-    }
+    const int rb = tamp_best_paths(c, ctxs, n, d_arena, d_cur, d_meta);
+    if (rb < 0) return rb;
     std::vector<BestPath> meta(n);
     HIPCHK_CTX(c, hipMemcpyAsync(meta.data(), d_meta, n * sizeof(BestPath), hipMemcpyDeviceToHost, st));
     HIPCHK_CTX(c, hipStreamSynchronize(st));
@@ -238,7 +261,7 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
         for (size_t k = 0; k < ns; ++k) { sx[k] = xy[2 * k]; sy[k] = xy[2 * k + 1]; }
     }
     uint8_t *d = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(3, d, bytes));
+    HIPCHK_CTX(c, T.scratch.get(kSlotShortcut, d, bytes));
     HIPCHK_CTX(c, c->refine.events());
     RefineConst rc{};
     rc.rc = (const RunConst *)d; rc.pieces = (const RefinePiece *)(d + o_pc); rc.compat = nullptr;
@@ -398,52 +421,195 @@ static int tamp_fail(porrt_ctx *c, TampState &T, int64_t node, int32_t zone, int
     return PORRT_ERR_NO_PATH;
 }
 
-static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
-                         uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
+// ---- what the three searches (this file, porrt_tamp_viewpoints.hpp, porrt_tamp_astar.hpp) share: DESIGN.md section 17
+
+// stream seed of the edge into the child of zone t of a node whose own seed is h
+static inline uint64_t tamp_edge_seed(uint64_t h, uint32_t t) { return tamp_splitmix64(h ^ ((uint64_t)t + 1)); }
+
+// a child's belief and reaching probability: the parent's belief with the parent's target zeroed, normalised
+static std::pair<std::vector<double>, double> tamp_child_belief(const double *belief, int32_t target, double rp, uint32_t nw) {
+    std::vector<double> b(belief, belief + nw);
+    if (target >= 0) b[(size_t)target] = 0.0;
+    tamp_normalize(b);
+    const double q = tamp_transition_probability(belief, b.data(), nw);
+    return {std::move(b), rp * q};
+}
+
+// a fresh shuffle of `remaining` without zone t: one per child, from the discrete sampler (the branch-and-bound searches only)
+static std::vector<uint32_t> tamp_remaining_without(const std::vector<uint32_t> &remaining, uint32_t t, Pcg64 &rng) {
+    std::vector<uint32_t> out;
+    for (uint32_t z : tamp_shuffled(remaining, rng)) if (z != t) out.push_back(z);
+    return out;
+}
+
+static std::vector<int64_t> tamp_chain(const std::vector<TampNode> &nodes, int64_t leaf) {     // root .. leaf
+    std::vector<int64_t> chain;
+    for (int64_t k = leaf; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
+    std::reverse(chain.begin(), chain.end());
+    return chain;
+}
+
+// One plan's frame: the entry checks and the reset of the state (begin), the growth parameters and the two ways to grow queries
+// with their accounting (grow_lead, grow_rows), the guard of the lead's continuous stream, and the end of a plan (finish).
+struct TampFrame {
+    porrt_ctx *c = nullptr;
+    TampState *T = nullptr;
+    double max_step = 0, search_radius = 0, goal_radius = 0;
+    uint64_t n_iter_min = 0, n_iter_max = 0;
+    uint32_t K = 0, nw = 0, streams = 0, wave = 1, pool_cap = 1;
     const double t_start = now_s();
-    if (c->opt_tamp_search != 0) {
-        c->set_err(c->opt_tamp_search == 1 ? "tamp: TampSearch::AStar is not supported (its expansion order cannot be pinned)"
-                                           : "tamp: TampSearch::BranchAndBoundMultipleViewPoints is not supported (it walks a HashSet)");
-        return PORRT_ERR_INVALID;
+    Pcg64 crng0{};
+    bool restore = false;                      // tamp_streams = 0: the lead's stream is set back however the plan ends
+    TampFrame() = default;
+    TampFrame(const TampFrame &) = delete;
+    ~TampFrame() { if (restore) c->crng = crng0; }
+
+    // The checks every search makes, in their order, then the state of a plan that has begun.  own(stage) holds the checks of one
+    // search alone at their places among the common ones: stage 0 after the zone count, stage 1 after the prior's sum.
+    int begin(porrt_ctx *ctx, const double start[2], const double *belief, uint32_t n_worlds, double max_step_, double search_radius_,
+              uint64_t n_iter_min_, uint64_t n_iter_max_, double goal_radius_, uint32_t K_, const std::function<int(int)> &own = nullptr) {
+        c = ctx;
+        if (!c->has_grid || c->zones.empty() || c->domain != PORRT_DOMAIN_SHELF) { c->set_err("tamp: needs a shelf map with zones (porrt_set_grid, porrt_set_zones)"); return PORRT_ERR_INVALID; }
+        if (!start || !belief || n_worlds != (uint32_t)c->n_zones) { c->set_err("tamp: n_worlds must equal the number of zones"); return PORRT_ERR_INVALID; }
+        int r = own ? own(0) : PORRT_OK;
+        if (r < 0) return r;
+        double sum = 0.0;
+        for (uint32_t w = 0; w < n_worlds; ++w) sum = sum + belief[w];
+        if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp: the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
+        if ((r = own ? own(1) : PORRT_OK) < 0) return r;
+        if (K_ == 0 || K_ > 4096) { c->set_err("batch_K must be in 1..4096"); return PORRT_ERR_INVALID; }
+        if (!(goal_radius_ >= 0.0)) { c->set_err("tamp: goal_radius"); return PORRT_ERR_INVALID; }
+        max_step = max_step_; search_radius = search_radius_; goal_radius = goal_radius_;
+        n_iter_min = n_iter_min_; n_iter_max = n_iter_max_; K = K_; nw = n_worlds;
+        T = &tamp_state(c);
+        T->valid = false;
+        memset(&T->info, 0, sizeof T->info);
+        memset(&T->vinfo, 0, sizeof T->vinfo);
+        T->info.fail_node = -1; T->info.fail_zone = -1; T->info.fail_query = -1;
+        T->nw = nw;
+        streams = c->opt_tamp_streams ? 1u : 0u;
+        wave = streams ? std::max<uint32_t>(1u, c->opt_tamp_wave) : 1u;
+        pool_cap = std::max<uint32_t>(1u, c->opt_tamp_pool);
+        T->info.streams = streams; T->info.wave = wave;
+        crng0 = c->crng;
+        restore = streams == 0;
+        return PORRT_OK;
     }
-    if (!c->has_grid || c->zones.empty() || c->domain != PORRT_DOMAIN_SHELF) { c->set_err("tamp: needs a shelf map with zones (porrt_set_grid, porrt_set_zones)"); return PORRT_ERR_INVALID; }
-    if (!start || !belief || nw != (uint32_t)c->n_zones) { c->set_err("tamp: n_worlds must equal the number of zones"); return PORRT_ERR_INVALID; }
-    double sum = 0.0;
-    for (uint32_t w = 0; w < nw; ++w) sum = sum + belief[w];
-    if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp: the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
-    if (K == 0 || K > 4096) { c->set_err("batch_K must be in 1..4096"); return PORRT_ERR_INVALID; }
-    if (!(goal_radius >= 0.0)) { c->set_err("tamp: goal_radius"); return PORRT_ERR_INVALID; }
-    TampState &T = tamp_state(c);
-    T.valid = false;
-    memset(&T.info, 0, sizeof T.info);
-    T.info.fail_node = -1; T.info.fail_zone = -1; T.info.fail_query = -1;
-    T.nw = nw;
-    const uint32_t streams = c->opt_tamp_streams ? 1u : 0u;
-    const uint32_t wave = streams ? std::max<uint32_t>(1u, c->opt_tamp_wave) : 1u;
-    const uint32_t pool_cap = std::max<uint32_t>(1u, c->opt_tamp_pool);
-    T.info.streams = streams; T.info.wave = wave;
-    const uint32_t nz = (uint32_t)c->n_zones;
-    std::vector<TampNode> nodes(1);
-    {
-        TampNode &root = nodes[0];
-        std::vector<uint32_t> all(nz);
-        for (uint32_t z = 0; z < nz; ++z) all[z] = z;
-        root.remaining = tamp_shuffled(all, c->drng);
-        root.ox = start[0]; root.oy = start[1];
-        root.belief.assign(belief, belief + nw);
-        root.h = c->s_seed;
+
+    // the goal of a query on context x: which = 0 to see the zone, 1 to pick the object up at it
+    int set_goal(porrt_ctx *x, uint32_t zone, int which) const {
+        const uint64_t m1 = 1;
+        return which == 0 ? porrt_set_observation_goal(x, zone) : porrt_set_square_goal(x, c->zone_pos[zone], &m1, 1, goal_radius);
     }
+    // the same on a stream of its own: a worker context seeded for one search edge
+    int seed_and_goal(porrt_ctx *x, uint64_t seed, uint32_t zone, int which) const {
+        const int r = porrt_set_sampler(x, c->s_low, c->s_up, seed);
+        return r < 0 ? r : set_goal(x, zone, which);
+    }
+
+    // one query on the lead, its stream running on
+    int grow_lead(const double start[2], uint32_t zone, int which) {
+        double t0 = now_s();
+        int r = set_goal(c, zone, which);
+        T->info.goals_s += now_s() - t0;
+        if (r < 0) return r;
+        t0 = now_s();
+        r = c->grow(start, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
+        T->info.grow_s += now_s() - t0;
+        ++T->info.queries;
+        return r;
+    }
+    // m queries in one porrt_grow_batch on ctxs[0 .. m) from starts; set_row(i) gives row i its goal (and its seed, where the
+    // search wants a fresh stream: that differs between the searches on purpose)
+    template <class SetRow>
+    int grow_rows(porrt_ctx *const *ctxs, uint32_t m, const double *starts, SetRow set_row) {
+        double t0 = now_s();
+        int r = PORRT_OK;
+        for (uint32_t i = 0; i < m; ++i) if ((r = set_row(i)) < 0) return r;
+        T->info.goals_s += now_s() - t0;
+        t0 = now_s();
+        r = porrt_grow_batch(ctxs, m, starts, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
+        T->info.grow_s += now_s() - t0;
+        T->info.queries += m;
+        if (r < 0) c->set_err(ctxs[0]->err);
+        return r;
+    }
+
+    // The end of a plan that found `leaf`: search cost and zone order of the chain root .. leaf, the lead's stream set back, the
+    // policy (with src the paths are on the device), the times.  extra_s: time the search accounts for outside search_s.
+    int64_t finish(const std::vector<TampNode> &nodes, int64_t leaf, TampChainSource *src = nullptr, double extra_s = 0.0) {
+        porrt_tamp_info &I = T->info;
+        I.search_cost = nodes[(size_t)leaf].ec;
+        I.n_order = 0;
+        for (int64_t k : tamp_chain(nodes, leaf)) if (nodes[(size_t)k].parent >= 0) I.zone_order[I.n_order++] = (uint32_t)nodes[(size_t)k].target;
+        if (restore) { c->crng = crng0; restore = false; }
+        const int r = tamp_build_policy(c, *T, nodes, leaf, src);
+        if (r < 0) return r;
+        T->valid = true;
+        I.pool = (uint32_t)T->pool.size();
+        I.total_s = now_s() - t_start;
+        I.search_s = I.total_s - I.grow_s - I.path_s - I.shortcut_s - I.pool_s - I.goals_s - extra_s;
+        return (int64_t)T->parents.size();
+    }
+};
+
+// the root of the branch-and-bound searches: every zone remaining, in a first shuffle
+static TampNode tamp_root(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw) {
+    TampNode root;
+    std::vector<uint32_t> all((size_t)c->n_zones);
+    for (uint32_t z = 0; z < all.size(); ++z) all[z] = z;
+    root.remaining = tamp_shuffled(all, c->drng);
+    root.ox = start[0]; root.oy = start[1];
+    root.belief.assign(belief, belief + nw);
+    root.h = c->s_seed;
+    return root;
+}
+
+// The branch and bound itself: the stack, the best leaf's cost so far and the leaf that holds it.
+struct TampBound {
     std::vector<int64_t> stack{0};
     double best = std::numeric_limits<double>::infinity();
     int64_t best_leaf = -1;
-    const Pcg64 crng0 = c->crng;
-    struct Restore { porrt_ctx *c; Pcg64 s; bool on; ~Restore() { if (on) c->crng = s; } } restore{c, crng0, streams == 0};
+    std::vector<int64_t> pop(uint32_t wave) {
+        std::vector<int64_t> popped;
+        while (!stack.empty() && popped.size() < wave) { popped.push_back(stack.back()); stack.pop_back(); }
+        return popped;
+    }
+    // node uid has been expanded; kids are its children in the sequential order, their queries done.  A child is pushed iff its
+    // expected cost is below the best leaf's so far; among leaves of the lowest cost the last one wins.
+    void close(TampState &T, std::vector<TampNode> &nodes, int64_t uid, const std::vector<int64_t> &kids) {
+        const TampNode &u = nodes[(size_t)uid];
+        for (int64_t vid : kids) {
+            TampNode &v = nodes[(size_t)vid];
+            v.ec = u.ec + v.rp * (v.obs_cost + v.belief[(size_t)v.target] * v.pick_cost);
+            if (v.ec < best) stack.push_back(vid);
+            else ++T.info.pruned;
+        }
+        if (u.remaining.empty()) {
+            if (u.ec < best) best = u.ec;
+            if (best_leaf < 0 || u.ec <= nodes[(size_t)best_leaf].ec) best_leaf = uid;
+        }
+    }
+};
+
+static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
+                         uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
+    TampFrame F;
+    if (c->opt_tamp_search != 0) {
+        c->set_err(c->opt_tamp_search == 1 ? "tamp: TampSearch::AStar has an entry point of its own: porrt_tamp_rrt_plan_astar"
+                                           : "tamp: TampSearch::BranchAndBoundMultipleViewPoints has an entry point of its own: porrt_tamp_rrt_plan_viewpoints");
+        return PORRT_ERR_INVALID;
+    }
+    int r = F.begin(c, start, belief, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K);
+    if (r < 0) return r;
+    TampState &T = *F.T;
+    std::vector<TampNode> nodes{tamp_root(c, start, belief, nw)};
+    TampBound B;
     std::vector<std::vector<double>> paths;
     std::vector<double> costs;
     std::vector<char> ok;
-    while (!stack.empty()) {
-        std::vector<int64_t> popped;
-        while (!stack.empty() && popped.size() < wave) { popped.push_back(stack.back()); stack.pop_back(); }
+    while (!B.stack.empty()) {
+        const std::vector<int64_t> popped = B.pop(F.wave);
         ++T.info.waves;
         // children in the sequential order, with their shuffles
         std::vector<std::pair<int64_t, std::vector<int64_t>>> made;
@@ -452,17 +618,13 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
             std::vector<int64_t> kids;
             const std::vector<uint32_t> rem_u = nodes[(size_t)uid].remaining;
             for (uint32_t t : rem_u) {
-                std::vector<uint32_t> sh = tamp_shuffled(rem_u, c->drng);
                 TampNode v;
+                v.remaining = tamp_remaining_without(rem_u, t, c->drng);
                 const TampNode &u = nodes[(size_t)uid];
-                for (uint32_t z : sh) if (z != t) v.remaining.push_back(z);
-                v.belief = u.belief;
-                if (u.target >= 0) v.belief[(size_t)u.target] = 0.0;
-                tamp_normalize(v.belief);
-                v.rp = u.rp * tamp_transition_probability(u.belief.data(), v.belief.data(), nw);
+                std::tie(v.belief, v.rp) = tamp_child_belief(u.belief.data(), u.target, u.rp, nw);
                 v.target = (int32_t)t;
                 v.parent = uid;
-                v.h = tamp_splitmix64(u.h ^ ((uint64_t)t + 1));
+                v.h = tamp_edge_seed(u.h, t);
                 kids.push_back((int64_t)nodes.size());
                 edges.push_back((int64_t)nodes.size());
                 nodes.push_back(std::move(v));
@@ -471,27 +633,15 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
         }
         T.info.search_nodes = nodes.size();
         // the queries
-        if (streams == 0) {
+        if (F.streams == 0) {
             for (int64_t vid : edges) {
                 TampNode &v = nodes[(size_t)vid];
                 const TampNode &u = nodes[(size_t)v.parent];
                 for (int which = 0; which < 2; ++which) {
-                    double t0 = now_s();
-                    int r = which == 0 ? porrt_set_observation_goal(c, (uint32_t)v.target) : [&]() {
-                        const uint64_t m1 = 1;
-                        return porrt_set_square_goal(c, c->zone_pos[v.target], &m1, 1, goal_radius);
-                    }();
-                    T.info.goals_s += now_s() - t0;
-                    if (r < 0) return r;
                     const double st[2] = {which == 0 ? u.ox : v.ox, which == 0 ? u.oy : v.oy};
-                    t0 = now_s();
-                    r = c->grow(st, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                    T.info.grow_s += now_s() - t0;
-                    ++T.info.queries;
-                    if (r < 0) return r;
+                    if ((r = F.grow_lead(st, (uint32_t)v.target, which)) < 0) return r;
                     porrt_ctx *one = c;
-                    r = tamp_gather(c, T, &one, 1, paths, costs, ok);
-                    if (r < 0) return r;
+                    if ((r = tamp_gather(c, T, &one, 1, paths, costs, ok)) < 0) return r;
                     if (!ok[0]) return tamp_fail(c, T, vid, v.target, which);
                     if (which == 0) {
                         v.path_obs = std::move(paths[0]); v.obs_cost = costs[0];
@@ -502,25 +652,19 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
                 }
             }
         } else {
-            for (size_t e0 = 0; e0 < edges.size(); e0 += pool_cap) {
-                const uint32_t m = (uint32_t)std::min<size_t>(pool_cap, edges.size() - e0);
-                int r = tamp_ensure_pool(c, T, m);
-                if (r < 0) return r;
+            for (size_t e0 = 0; e0 < edges.size(); e0 += F.pool_cap) {
+                const uint32_t m = (uint32_t)std::min<size_t>(F.pool_cap, edges.size() - e0);
+                if ((r = tamp_ensure_pool(c, T, m)) < 0) return r;
                 std::vector<double> starts(2 * (size_t)m);
-                double t0 = now_s();
                 for (uint32_t i = 0; i < m; ++i) {
-                    const TampNode &v = nodes[(size_t)edges[e0 + i]];
-                    const TampNode &u = nodes[(size_t)v.parent];
-                    if ((r = porrt_set_sampler(T.pool[i], c->s_low, c->s_up, v.h)) < 0) return r;
-                    if ((r = porrt_set_observation_goal(T.pool[i], (uint32_t)v.target)) < 0) return r;
+                    const TampNode &u = nodes[(size_t)nodes[(size_t)edges[e0 + i]].parent];
                     starts[2 * i] = u.ox; starts[2 * i + 1] = u.oy;
                 }
-                T.info.goals_s += now_s() - t0;
-                t0 = now_s();
-                r = porrt_grow_batch(T.pool.data(), m, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                T.info.queries += m;
-                if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                r = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) {
+                    const TampNode &v = nodes[(size_t)edges[e0 + i]];
+                    return F.seed_and_goal(T.pool[i], v.h, (uint32_t)v.target, 0);
+                });
+                if (r < 0) return r;
                 if ((r = tamp_gather(c, T, T.pool.data(), m, paths, costs, ok)) < 0) return r;
                 uint32_t first_bad = m;
                 for (uint32_t i = 0; i < m && first_bad == m; ++i) if (!ok[i]) first_bad = i;
@@ -533,18 +677,8 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
                 // the pickup queries of the rows before the first failure, on the same contexts: their streams run on
                 const uint32_t mp = first_bad;
                 if (mp) {
-                    t0 = now_s();
-                    for (uint32_t i = 0; i < mp; ++i) {
-                        const TampNode &v = nodes[(size_t)edges[e0 + i]];
-                        const uint64_t m1 = 1;
-                        if ((r = porrt_set_square_goal(T.pool[i], c->zone_pos[v.target], &m1, 1, goal_radius)) < 0) return r;
-                    }
-                    T.info.goals_s += now_s() - t0;
-                    t0 = now_s();
-                    r = porrt_grow_batch(T.pool.data(), mp, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                    T.info.grow_s += now_s() - t0;
-                    T.info.queries += mp;
-                    if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                    r = F.grow_rows(T.pool.data(), mp, starts.data(), [&](uint32_t i) { return F.set_goal(T.pool[i], (uint32_t)nodes[(size_t)edges[e0 + i]].target, 1); });
+                    if (r < 0) return r;
                     if ((r = tamp_gather(c, T, T.pool.data(), mp, paths, costs, ok)) < 0) return r;
                     for (uint32_t i = 0; i < mp; ++i) {
                         TampNode &v = nodes[(size_t)edges[e0 + i]];
@@ -556,38 +690,10 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
             }
         }
         // push the children, record the leaves: the sequential order
-        for (const auto &mk : made) {
-            const TampNode &u = nodes[(size_t)mk.first];
-            for (int64_t vid : mk.second) {
-                TampNode &v = nodes[(size_t)vid];
-                v.ec = u.ec + v.rp * (v.obs_cost + v.belief[(size_t)v.target] * v.pick_cost);
-                if (v.ec < best) stack.push_back(vid);
-                else ++T.info.pruned;
-            }
-            if (u.remaining.empty()) {
-                if (u.ec < best) best = u.ec;
-                if (best_leaf < 0 || u.ec <= nodes[(size_t)best_leaf].ec) best_leaf = mk.first;
-            }
-        }
+        for (const auto &mk : made) B.close(T, nodes, mk.first, mk.second);
     }
     T.info.search_nodes = nodes.size();
-    T.info.search_cost = nodes[(size_t)best_leaf].ec;
-    T.info.n_order = 0;
-    {
-        std::vector<uint32_t> order;
-        for (int64_t k = best_leaf; k > 0; k = nodes[(size_t)k].parent) order.push_back((uint32_t)nodes[(size_t)k].target);
-        std::reverse(order.begin(), order.end());
-        for (uint32_t z : order) T.info.zone_order[T.info.n_order++] = z;
-    }
-    restore.on = false;
-    if (streams == 0) c->crng = crng0;
-    const int r = tamp_build_policy(c, T, nodes, best_leaf);
-    if (r < 0) return r;
-    T.valid = true;
-    T.info.pool = (uint32_t)T.pool.size();
-    T.info.total_s = now_s() - t_start;
-    T.info.search_s = T.info.total_s - T.info.grow_s - T.info.path_s - T.info.shortcut_s - T.info.pool_s - T.info.goals_s;
-    return (int64_t)T.parents.size();
+    return F.finish(nodes, B.best_leaf);
 }
 
 } // namespace

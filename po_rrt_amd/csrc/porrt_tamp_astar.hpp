@@ -102,35 +102,14 @@ static int astar_arena_reserve(porrt_ctx *c, AstarState &A, size_t states) {
     return PORRT_OK;
 }
 
-// k_best_cost + k_best_path of the rows ctxs[0 .. n) after their growth, as tamp_gather, but into the plan's arena through its
-// running cursor, the records to meta[0 .. n) on the device: nothing is downloaded here
-static int astar_gather(porrt_ctx *c, AstarState &A, porrt_ctx *const *ctxs, uint32_t n, uint32_t *d_cur, BestPath *d_meta) {
+// tamp_best_paths of the rows ctxs[0 .. n) into the plan's arena through its running cursor, the records to d_meta[0 .. n) on the
+// device: nothing is downloaded here
+static int astar_gather(porrt_ctx *c, TampState &T, AstarState &A, porrt_ctx *const *ctxs, uint32_t n, uint32_t *d_cur, BestPath *d_meta) {
+    const double t0 = now_s();
     int r = astar_arena_reserve(c, A, A.cursor_ub + (size_t)n * kTampPathSlot);
-    if (r < 0) return r;
-    hipStream_t st = c->stream;
-    for (uint32_t q0 = 0; q0 < n;) {
-        porrt_ctx *L = ctxs[q0]->batch_leader;
-        const uint32_t m = L ? L->batch_size : 0;
-        bool run = L != nullptr && m > 0 && q0 + m <= n;
-        for (uint32_t k = 0; k < m && run; ++k) {
-            const porrt_ctx *x = ctxs[q0 + k];
-            run = x->have_results && x->batch_leader == L && x->batch_slot == k && x->n_steps == L->n_steps && x->batch_gen == L->batch_gen_counter;
-        }
-        const RunConst *rcp;
-        uint32_t rows, steps;
-        if (run) { rcp = L->d_rcarr; rows = m; steps = (uint32_t)L->n_steps; }
-        else {
-            porrt_ctx *x = ctxs[q0];
-            if (!x->have_results) { c->set_err("tamp astar: a query has no results"); return PORRT_ERR_INVALID; }
-            rcp = x->d_rc.p; rows = 1; steps = (uint32_t)x->n_steps;
-        }
-        hipLaunchKernelGGL(k_best_path_reset, dim3(1, rows), dim3(64), 0, st, rcp);
-        hipLaunchKernelGGL(k_best_cost, dim3(1, rows), dim3(1024), 0, st, rcp, steps);
-        hipLaunchKernelGGL(k_best_path, dim3(1, rows), dim3(64), 0, st, rcp, q0, kTampPathSlot, A.arena, d_cur, d_meta);
-        HIPCHK_CTX(c, hipGetLastError());
-        q0 += rows;
-    }
+    if (r < 0 || (r = tamp_best_paths(c, ctxs, n, A.arena, d_cur, d_meta)) < 0) return r;
     A.cursor_ub += (size_t)n * kTampPathSlot;
+    T.info.path_s += now_s() - t0;
     return PORRT_OK;
 }
 
@@ -142,43 +121,32 @@ static int astar_bad_record(porrt_ctx *c, uint32_t status) {
 
 static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
                                uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
-    const double t_start = now_s();
-    if (!c->has_grid || c->zones.empty() || c->domain != PORRT_DOMAIN_SHELF) { c->set_err("tamp: needs a shelf map with zones (porrt_set_grid, porrt_set_zones)"); return PORRT_ERR_INVALID; }
-    if (!start || !belief || nw != (uint32_t)c->n_zones) { c->set_err("tamp: n_worlds must equal the number of zones"); return PORRT_ERR_INVALID; }
-    if (nw > 64) { c->set_err("tamp astar: at most 64 zones"); return PORRT_ERR_INVALID; }
-    double sum = 0.0;
-    for (uint32_t w = 0; w < nw; ++w) sum = sum + belief[w];
-    if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp: the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
-    for (uint32_t w = 0; w < nw; ++w)
-        if (!(belief[w] > 0.0)) { c->set_err("tamp astar: every entry of the prior must be > 0 (below the last positive zone every priority would be NaN)"); return PORRT_ERR_INVALID; }
-    if (K == 0 || K > 4096) { c->set_err("batch_K must be in 1..4096"); return PORRT_ERR_INVALID; }
-    if (!(goal_radius >= 0.0)) { c->set_err("tamp: goal_radius"); return PORRT_ERR_INVALID; }
-    TampState &T = tamp_state(c);
+    TampFrame F;
+    int r = F.begin(c, start, belief, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K, [&](int stage) -> int {
+        if (stage == 0) {
+            if (nw > 64) { c->set_err("tamp astar: at most 64 zones"); return PORRT_ERR_INVALID; }
+            return PORRT_OK;
+        }
+        for (uint32_t w = 0; w < nw; ++w)
+            if (!(belief[w] > 0.0)) { c->set_err("tamp astar: every entry of the prior must be > 0 (below the last positive zone every priority would be NaN)"); return PORRT_ERR_INVALID; }
+        return PORRT_OK;
+    });
+    if (r < 0) return r;
+    TampState &T = *F.T;
     AstarState &A = astar_state(T);
-    T.valid = false;
-    memset(&T.info, 0, sizeof T.info);
-    memset(&T.vinfo, 0, sizeof T.vinfo);
     memset(&A.info, 0, sizeof A.info);
     A.parents.clear(); A.targets.clear(); A.ec.clear(); A.priority.clear();
-    T.info.fail_node = -1; T.info.fail_zone = -1; T.info.fail_query = -1;
-    T.nw = nw;
-    const uint32_t streams = c->opt_tamp_streams ? 1u : 0u;
-    const uint32_t wave = streams ? std::max<uint32_t>(1u, c->opt_tamp_wave) : 1u;
-    const uint32_t pool_cap = std::max<uint32_t>(1u, c->opt_tamp_pool);
-    T.info.streams = streams; T.info.wave = wave;
     const uint32_t nz = nw;
 
     HIPCHK_CTX(c, hipSetDevice(c->device));
     if (!A.ev) HIPCHK_CTX(c, hipEventCreate(&A.ev));
     hipStream_t st = c->stream;
     A.cursor_ub = 0;
-    int r = astar_arena_reserve(c, A, std::max<size_t>(kTampPathSlot, c->opt_tamp_arena_states));
-    if (r < 0) return r;
-    // device scratch of the plan (slots 11 .. 16 of the TAMP state are this file's)
+    if ((r = astar_arena_reserve(c, A, std::max<size_t>(kTampPathSlot, c->opt_tamp_arena_states))) < 0) return r;
     uint32_t *d_cur = nullptr;
     double2 *d_zpos = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(11, d_cur, 1));
-    HIPCHK_CTX(c, T.scratch.get(12, d_zpos, nz));
+    HIPCHK_CTX(c, T.scratch.get(kSlotAstarCursor, d_cur, 1));
+    HIPCHK_CTX(c, T.scratch.get(kSlotAstarZonePos, d_zpos, nz));
     HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
     {
         std::vector<double2> zp(nz);
@@ -196,8 +164,6 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
         root.ox = start[0]; root.oy = start[1];
         root.h = c->s_seed;
     }
-    const Pcg64 crng0 = c->crng;
-    struct Restore { porrt_ctx *c; Pcg64 s; bool on; ~Restore() { if (on) c->crng = s; } } restore{c, crng0, streams == 0};
     // the nodes as they stand go to the state whichever way the plan ends (porrt_tamp_astar_nodes)
     struct Keep {
         AstarState &A; TampState &T; const std::vector<AstarNode> &nodes;
@@ -207,16 +173,13 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
             A.info.arena_states = A.arena_cap;
         }
     } keep{A, T, nodes};
-    const uint64_t m1 = 1;
 
     // the expansion of node uid gets its belief row and reaching probability; returns its index
     auto open_expansion = [&](int64_t uid) {
         const AstarNode &u = nodes[(size_t)uid];
         AstarExpansion E;
-        std::vector<double> vb(beliefs.begin() + (size_t)u.belief * nw, beliefs.begin() + (size_t)(u.belief + 1) * nw);
-        if (u.target >= 0) vb[(size_t)u.target] = 0.0;
-        tamp_normalize(vb);
-        E.rp = u.rp * tamp_transition_probability(beliefs.data() + (size_t)u.belief * nw, vb.data(), nw);
+        std::vector<double> vb;
+        std::tie(vb, E.rp) = tamp_child_belief(beliefs.data() + (size_t)u.belief * nw, u.target, u.rp, nw);
         E.belief = (uint32_t)(beliefs.size() / nw);
         beliefs.insert(beliefs.end(), vb.begin(), vb.end());
         for (uint32_t z = 0; z < nz; ++z) if ((u.remaining >> z) & 1ull) E.zone.push_back(z);
@@ -250,9 +213,9 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
         AstarChildIn *d_in = nullptr;
         double *d_bl = nullptr;
         AstarChildOut *d_out = nullptr;
-        HIPCHK_CTX(c, T.scratch.get(13, d_in, m));
-        HIPCHK_CTX(c, T.scratch.get(14, d_bl, bl.size()));
-        HIPCHK_CTX(c, T.scratch.get(15, d_out, m));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarChildIn, d_in, m));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarBeliefs, d_bl, bl.size()));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarChildOut, d_out, m));
         HIPCHK_CTX(c, hipMemcpyAsync(d_in, in.data(), m * sizeof(AstarChildIn), hipMemcpyHostToDevice, st));
         HIPCHK_CTX(c, hipMemcpyAsync(d_bl, bl.data(), bl.size() * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_astar_children, dim3((m + 63u) / 64u), dim3(64), 0, st, d_in, m, d_obs, d_pick, d_bl, nw, d_zpos, d_cur, d_out);
@@ -292,8 +255,8 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
         nodes[(size_t)uid].kids = ei;
         const uint32_t m = (uint32_t)exps[(size_t)ei].zone.size();
         BestPath *d_obs = nullptr, *d_pick = nullptr;
-        HIPCHK_CTX(c, T.scratch.get(0, d_obs, m));
-        HIPCHK_CTX(c, T.scratch.get(16, d_pick, m));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
         std::vector<Edge> edges;
         std::vector<uint32_t> pick_row(m);
         std::vector<BestPath> meta;
@@ -304,19 +267,9 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
             pick_row[i] = i;
             double st2[2] = {nodes[(size_t)uid].ox, nodes[(size_t)uid].oy};
             for (int which = 0; which < 2; ++which) {
-                double t0 = now_s();
-                int rr = which == 0 ? porrt_set_observation_goal(c, t) : porrt_set_square_goal(c, c->zone_pos[t], &m1, 1, goal_radius);
-                T.info.goals_s += now_s() - t0;
+                int rr = F.grow_lead(st2, t, which);
                 if (rr < 0) return rr;
-                t0 = now_s();
-                rr = c->grow(st2, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                ++T.info.queries;
-                if (rr < 0) return rr;
-                t0 = now_s();
-                rr = astar_gather(c, A, &one, 1, d_cur, (which == 0 ? d_obs : d_pick) + i);
-                T.info.path_s += now_s() - t0;
-                if (rr < 0) return rr;
+                if ((rr = astar_gather(c, T, A, &one, 1, d_cur, (which == 0 ? d_obs : d_pick) + i)) < 0) return rr;
                 if ((rr = fetch_obs((which == 0 ? d_obs : d_pick) + i, 1, meta)) < 0) return rr;
                 if (meta[0].status == 1u) return tamp_fail(c, T, (int64_t)nodes.size() + i, (int32_t)t, which);
                 st2[0] = meta[0].end_x; st2[1] = meta[0].end_y;
@@ -334,59 +287,37 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
             for (uint32_t i = 0; i < exps[(size_t)ei].zone.size(); ++i) edges.push_back({uid, ei, i});
         }
         std::vector<BestPath> meta;
-        for (size_t e0 = 0; e0 < edges.size(); e0 += pool_cap) {
-            const uint32_t m = (uint32_t)std::min<size_t>(pool_cap, edges.size() - e0);
+        auto zone_of = [&](size_t e) { return exps[(size_t)edges[e].e].zone[edges[e].i]; };
+        for (size_t e0 = 0; e0 < edges.size(); e0 += F.pool_cap) {
+            const uint32_t m = (uint32_t)std::min<size_t>(F.pool_cap, edges.size() - e0);
             int rr = tamp_ensure_pool(c, T, m);
             if (rr < 0) return rr;
             BestPath *d_obs = nullptr, *d_pick = nullptr;
-            HIPCHK_CTX(c, T.scratch.get(0, d_obs, m));
-            HIPCHK_CTX(c, T.scratch.get(16, d_pick, m));
+            HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
+            HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
             std::vector<double> starts(2 * (size_t)m);
-            double t0 = now_s();
-            for (uint32_t i = 0; i < m; ++i) {
-                const Edge &ed = edges[e0 + i];
-                const AstarNode &u = nodes[(size_t)ed.u];
-                const uint32_t t = exps[(size_t)ed.e].zone[ed.i];
-                if ((rr = porrt_set_sampler(T.pool[i], c->s_low, c->s_up, tamp_splitmix64(u.h ^ ((uint64_t)t + 1)))) < 0) return rr;
-                if ((rr = porrt_set_observation_goal(T.pool[i], t)) < 0) return rr;
-                starts[2 * i] = u.ox; starts[2 * i + 1] = u.oy;
-            }
-            T.info.goals_s += now_s() - t0;
-            t0 = now_s();
-            rr = porrt_grow_batch(T.pool.data(), m, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-            T.info.grow_s += now_s() - t0;
-            T.info.queries += m;
-            if (rr < 0) { c->set_err(T.pool[0]->err); return rr; }
-            t0 = now_s();
-            rr = astar_gather(c, A, T.pool.data(), m, d_cur, d_obs);
-            T.info.path_s += now_s() - t0;
+            for (uint32_t i = 0; i < m; ++i) { starts[2 * i] = nodes[(size_t)edges[e0 + i].u].ox; starts[2 * i + 1] = nodes[(size_t)edges[e0 + i].u].oy; }
+            rr = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) {
+                return F.seed_and_goal(T.pool[i], tamp_edge_seed(nodes[(size_t)edges[e0 + i].u].h, zone_of(e0 + i)), zone_of(e0 + i), 0);
+            });
             if (rr < 0) return rr;
+            if ((rr = astar_gather(c, T, A, T.pool.data(), m, d_cur, d_obs)) < 0) return rr;
             if ((rr = fetch_obs(d_obs, m, meta)) < 0) return rr;
             // the pickup queries of the rows that saw their zone, on the same contexts: their streams run on
             std::vector<porrt_ctx *> sub;
-            std::vector<uint32_t> pick_row(m, 0xFFFFFFFFu);
+            std::vector<uint32_t> pick_row(m, 0xFFFFFFFFu), sub_zone;
             std::vector<double> pstarts;
-            t0 = now_s();
             for (uint32_t i = 0; i < m; ++i) {
                 if (meta[i].status != 0u) continue;
-                const uint32_t t = exps[(size_t)edges[e0 + i].e].zone[edges[e0 + i].i];
-                if ((rr = porrt_set_square_goal(T.pool[i], c->zone_pos[t], &m1, 1, goal_radius)) < 0) return rr;
                 pick_row[i] = (uint32_t)sub.size();
                 sub.push_back(T.pool[i]);
+                sub_zone.push_back(zone_of(e0 + i));
                 pstarts.push_back(meta[i].end_x); pstarts.push_back(meta[i].end_y);
             }
-            T.info.goals_s += now_s() - t0;
             if (!sub.empty()) {
                 const uint32_t mp = (uint32_t)sub.size();
-                t0 = now_s();
-                rr = porrt_grow_batch(sub.data(), mp, pstarts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                T.info.queries += mp;
-                if (rr < 0) { c->set_err(sub[0]->err); return rr; }
-                t0 = now_s();
-                rr = astar_gather(c, A, sub.data(), mp, d_cur, d_pick);
-                T.info.path_s += now_s() - t0;
-                if (rr < 0) return rr;
+                if ((rr = F.grow_rows(sub.data(), mp, pstarts.data(), [&](uint32_t j) { return F.set_goal(sub[j], sub_zone[j], 1); })) < 0) return rr;
+                if ((rr = astar_gather(c, T, A, sub.data(), mp, d_cur, d_pick)) < 0) return rr;
             }
             if ((rr = children(edges, e0, m, pick_row, d_obs, d_pick)) < 0) return rr;
         }
@@ -414,7 +345,7 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
                     v.remaining = u.remaining & ~(1ull << E.zone[i]);
                     v.ox = o.ox; v.oy = o.oy; v.rp = E.rp; v.ec = o.ec; v.priority = o.priority;
                     v.belief = E.belief;
-                    v.h = tamp_splitmix64(u.h ^ ((uint64_t)E.zone[i] + 1));
+                    v.h = tamp_edge_seed(u.h, E.zone[i]);
                     v.obs_off = o.obs_off; v.obs_len = o.obs_len; v.pick_off = o.pick_off; v.pick_len = o.pick_len;
                     queue.push(v.priority, (uint64_t)nodes.size());
                     nodes.push_back(v);
@@ -426,47 +357,37 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
         // the top has no children yet: it and the next best entries like it
         std::vector<porrt_astar::QueueEntry> held;
         std::vector<int64_t> batch;
-        while (!queue.empty() && batch.size() < wave) {
+        while (!queue.empty() && batch.size() < F.wave) {
             const porrt_astar::QueueEntry e = queue.pop();
             held.push_back(e);
             if (nodes[(size_t)e.id].remaining && nodes[(size_t)e.id].kids < 0) batch.push_back((int64_t)e.id);
         }
         for (const porrt_astar::QueueEntry &e : held) queue.push(e.priority, e.id);
         ++T.info.waves;
-        const int64_t rr = streams == 0 ? expand_sequential(batch[0]) : expand_wave(batch);
+        const int64_t rr = F.streams == 0 ? expand_sequential(batch[0]) : expand_wave(batch);
         if (rr < 0) return rr;
     }
     if (solution < 0) { c->set_err("No solution found!"); return PORRT_ERR_NO_PATH; }
     for (const AstarNode &n : nodes) if (n.kids >= 0 && !n.popped) ++A.info.speculated;
-    T.info.search_cost = nodes[(size_t)solution].ec;
-    T.info.n_order = 0;
     std::vector<int64_t> chain;
     for (int64_t k = solution; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
     std::reverse(chain.begin(), chain.end());
-    for (size_t i = 1; i < chain.size(); ++i) T.info.zone_order[T.info.n_order++] = (uint32_t)nodes[(size_t)chain[i]].target;
-    restore.on = false;
-    if (streams == 0) c->crng = crng0;
-    // build_policy on the chain: the paths stay on the device, tamp_build_policy sees their lengths
+    // the chain as TampNodes for the frame's finish: the paths stay on the device, tamp_build_policy sees their lengths
     std::vector<TampNode> cn(chain.size());
     TampChainSource src;
     src.arena = A.arena; src.ev = A.ev;
     for (size_t i = 0; i < chain.size(); ++i) {
         const AstarNode &n = nodes[(size_t)chain[i]];
-        cn[i].target = n.target; cn[i].parent = (int64_t)i - 1;
+        cn[i].target = n.target; cn[i].parent = (int64_t)i - 1; cn[i].ec = n.ec;
         cn[i].belief.assign(beliefs.begin() + (size_t)n.belief * nw, beliefs.begin() + (size_t)(n.belief + 1) * nw);
         cn[i].path_obs.assign(2 * (size_t)n.obs_len, 0.0);
         cn[i].path_pick.assign(2 * (size_t)n.pick_len, 0.0);
         src.paths.push_back({n.obs_off, n.obs_len, 0u, 0u});
         src.paths.push_back({n.pick_off, n.pick_len, 0u, 0u});
     }
-    r = tamp_build_policy(c, T, cn, (int64_t)cn.size() - 1, &src);
-    if (r < 0) return r;
-    A.info.chain_s = src.chain_s;
-    T.valid = true;
-    T.info.pool = (uint32_t)T.pool.size();
-    T.info.total_s = now_s() - t_start;
-    T.info.search_s = T.info.total_s - T.info.grow_s - T.info.path_s - T.info.shortcut_s - T.info.pool_s - T.info.goals_s - A.info.children_s;
-    return (int64_t)T.parents.size();
+    const int64_t n = F.finish(cn, (int64_t)cn.size() - 1, &src, A.info.children_s);
+    if (n >= 0) A.info.chain_s = src.chain_s;
+    return n;
 }
 
 // the shortcut's device-resident input form on explicit paths: they are put into the arena as a plan's gathers would leave them

@@ -69,46 +69,17 @@ struct VpEdge {                                   // one (node, zone) pair of a 
 
 static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
                                     uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K, uint32_t max_viewpoints) {
-    const double t_start = now_s();
-    if (!c->has_grid || c->zones.empty() || c->domain != PORRT_DOMAIN_SHELF) { c->set_err("tamp: needs a shelf map with zones (porrt_set_grid, porrt_set_zones)"); return PORRT_ERR_INVALID; }
-    if (!start || !belief || nw != (uint32_t)c->n_zones) { c->set_err("tamp: n_worlds must equal the number of zones"); return PORRT_ERR_INVALID; }
-    double sum = 0.0;
-    for (uint32_t w = 0; w < nw; ++w) sum = sum + belief[w];
-    if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp: the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
-    if (K == 0 || K > 4096) { c->set_err("batch_K must be in 1..4096"); return PORRT_ERR_INVALID; }
-    if (!(goal_radius >= 0.0)) { c->set_err("tamp: goal_radius"); return PORRT_ERR_INVALID; }
-    TampState &T = tamp_state(c);
-    T.valid = false;
-    memset(&T.info, 0, sizeof T.info);
-    memset(&T.vinfo, 0, sizeof T.vinfo);
-    T.info.fail_node = -1; T.info.fail_zone = -1; T.info.fail_query = -1;
+    TampFrame F;
+    int r = F.begin(c, start, belief, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K);
+    if (r < 0) return r;
+    TampState &T = *F.T;
     T.vinfo.max_viewpoints = max_viewpoints;
-    T.nw = nw;
-    const uint32_t streams = c->opt_tamp_streams ? 1u : 0u;
-    const uint32_t wave = streams ? std::max<uint32_t>(1u, c->opt_tamp_wave) : 1u;
-    const uint32_t pool_cap = std::max<uint32_t>(1u, c->opt_tamp_pool);
-    T.info.streams = streams; T.info.wave = wave;
-    const uint32_t nz = (uint32_t)c->n_zones;
-    std::vector<TampNode> nodes(1);
+    std::vector<TampNode> nodes{tamp_root(c, start, belief, nw)};
     std::vector<uint32_t> rank_of(1, 0);
-    {
-        TampNode &root = nodes[0];
-        std::vector<uint32_t> all(nz);
-        for (uint32_t z = 0; z < nz; ++z) all[z] = z;
-        root.remaining = tamp_shuffled(all, c->drng);
-        root.ox = start[0]; root.oy = start[1];
-        root.belief.assign(belief, belief + nw);
-        root.h = c->s_seed;
-    }
-    std::vector<int64_t> stack{0};
-    double best = std::numeric_limits<double>::infinity();
-    int64_t best_leaf = -1;
-    const Pcg64 crng0 = c->crng;
-    struct Restore { porrt_ctx *c; Pcg64 s; bool on; ~Restore() { if (on) c->crng = s; } } restore{c, crng0, streams == 0};
+    TampBound B;
     std::vector<std::vector<double>> paths;
     std::vector<double> costs;
     std::vector<char> ok;
-    const uint64_t m1 = 1;
     // a child of edge e from the solution s of S, with its pickup path still to come
     auto add_child = [&](VpEdge &e, const VpSolutions &S, uint64_t s, uint32_t rank) {
         TampNode v;
@@ -126,9 +97,8 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
         T.vinfo.viewpoints_found += found; T.vinfo.viewpoints_kept += kept;
         T.vinfo.largest_set = std::max<uint64_t>(T.vinfo.largest_set, found);
     };
-    while (!stack.empty()) {
-        std::vector<int64_t> popped;
-        while (!stack.empty() && popped.size() < wave) { popped.push_back(stack.back()); stack.pop_back(); }
+    while (!B.stack.empty()) {
+        const std::vector<int64_t> popped = B.pop(F.wave);
         ++T.info.waves;
         // the (node, zone) pairs in the sequential order, with their shuffles
         std::vector<VpEdge> edges;
@@ -137,30 +107,20 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
             const size_t e0 = edges.size();
             const TampNode &u = nodes[(size_t)uid];
             for (uint32_t t : u.remaining) {
-                std::vector<uint32_t> sh = tamp_shuffled(u.remaining, c->drng);
                 VpEdge e;
                 e.u = uid; e.t = t;
-                for (uint32_t z : sh) if (z != t) e.remaining.push_back(z);
-                e.belief = u.belief;
-                if (u.target >= 0) e.belief[(size_t)u.target] = 0.0;
-                tamp_normalize(e.belief);
-                e.rp = u.rp * tamp_transition_probability(u.belief.data(), e.belief.data(), nw);
-                e.ho = tamp_splitmix64(u.h ^ ((uint64_t)t + 1));
+                e.remaining = tamp_remaining_without(u.remaining, t, c->drng);
+                std::tie(e.belief, e.rp) = tamp_child_belief(u.belief.data(), u.target, u.rp, nw);
+                e.ho = tamp_edge_seed(u.h, t);
                 edges.push_back(std::move(e));
             }
             made.push_back({uid, {e0, edges.size()}});
         }
-        if (streams == 0) {
+        if (F.streams == 0) {
             for (VpEdge &e : edges) {
-                double t0 = now_s();
-                int r = porrt_set_observation_goal(c, e.t);
-                T.info.goals_s += now_s() - t0;
-                if (r < 0) return r;
                 const double st[2] = {nodes[(size_t)e.u].ox, nodes[(size_t)e.u].oy};
-                t0 = now_s();
-                r = c->grow(st, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                ++T.info.queries; ++T.vinfo.observation_queries;
+                r = F.grow_lead(st, e.t, 0);
+                ++T.vinfo.observation_queries;
                 if (r < 0) return r;
                 porrt_ctx *one = c;
                 VpSolutions S;
@@ -170,15 +130,9 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
                 for (uint32_t j = 0; j < kept.size(); ++j) {
                     const int64_t vid = (int64_t)nodes.size();
                     add_child(e, S, kept[j], j);
-                    t0 = now_s();
-                    r = porrt_set_square_goal(c, c->zone_pos[e.t], &m1, 1, goal_radius);
-                    T.info.goals_s += now_s() - t0;
-                    if (r < 0) return r;
                     const double ps[2] = {nodes[(size_t)vid].ox, nodes[(size_t)vid].oy};
-                    t0 = now_s();
-                    r = c->grow(ps, max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                    T.info.grow_s += now_s() - t0;
-                    ++T.info.queries; ++T.vinfo.pickup_queries;
+                    r = F.grow_lead(ps, e.t, 1);
+                    ++T.vinfo.pickup_queries;
                     if (r < 0) return r;
                     if ((r = tamp_gather(c, T, &one, 1, paths, costs, ok)) < 0) return r;
                     if (!ok[0]) return tamp_fail(c, T, vid, (int32_t)e.t, 1);
@@ -187,24 +141,14 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
             }
         } else {
             // the observation queries, all solutions of all rows gathered on the device
-            for (size_t e0 = 0; e0 < edges.size(); e0 += pool_cap) {
-                const uint32_t m = (uint32_t)std::min<size_t>(pool_cap, edges.size() - e0);
-                int r = tamp_ensure_pool(c, T, m);
-                if (r < 0) return r;
+            for (size_t e0 = 0; e0 < edges.size(); e0 += F.pool_cap) {
+                const uint32_t m = (uint32_t)std::min<size_t>(F.pool_cap, edges.size() - e0);
+                if ((r = tamp_ensure_pool(c, T, m)) < 0) return r;
                 std::vector<double> starts(2 * (size_t)m);
-                double t0 = now_s();
-                for (uint32_t i = 0; i < m; ++i) {
-                    const VpEdge &e = edges[e0 + i];
-                    if ((r = porrt_set_sampler(T.pool[i], c->s_low, c->s_up, e.ho)) < 0) return r;
-                    if ((r = porrt_set_observation_goal(T.pool[i], e.t)) < 0) return r;
-                    starts[2 * i] = nodes[(size_t)e.u].ox; starts[2 * i + 1] = nodes[(size_t)e.u].oy;
-                }
-                T.info.goals_s += now_s() - t0;
-                t0 = now_s();
-                r = porrt_grow_batch(T.pool.data(), m, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                T.info.queries += m; T.vinfo.observation_queries += m;
-                if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                for (uint32_t i = 0; i < m; ++i) { starts[2 * i] = nodes[(size_t)edges[e0 + i].u].ox; starts[2 * i + 1] = nodes[(size_t)edges[e0 + i].u].oy; }
+                r = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) { return F.seed_and_goal(T.pool[i], edges[e0 + i].ho, edges[e0 + i].t, 0); });
+                T.vinfo.observation_queries += m;
+                if (r < 0) return r;
                 VpSolutions S;
                 if ((r = vp_gather_solutions(c, T, T.pool.data(), m, S)) < 0) return r;
                 for (uint32_t i = 0; i < m; ++i) {              // ids in the sequential order: (node, zone, rank)
@@ -213,27 +157,20 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
                     for (uint32_t j = 0; j < kept.size(); ++j) add_child(edges[e0 + i], S, kept[j], j);
                 }
             }
-            // the pickup queries of every kept viewpoint
+            // the pickup queries of every kept viewpoint, each on a stream of its own: one observation tree feeds many pickups
             std::vector<int64_t> kids;
             for (const VpEdge &e : edges) kids.insert(kids.end(), e.kids.begin(), e.kids.end());
-            for (size_t k0 = 0; k0 < kids.size(); k0 += pool_cap) {
-                const uint32_t m = (uint32_t)std::min<size_t>(pool_cap, kids.size() - k0);
-                int r = tamp_ensure_pool(c, T, m);
-                if (r < 0) return r;
+            for (size_t k0 = 0; k0 < kids.size(); k0 += F.pool_cap) {
+                const uint32_t m = (uint32_t)std::min<size_t>(F.pool_cap, kids.size() - k0);
+                if ((r = tamp_ensure_pool(c, T, m)) < 0) return r;
                 std::vector<double> starts(2 * (size_t)m);
-                double t0 = now_s();
-                for (uint32_t i = 0; i < m; ++i) {
+                for (uint32_t i = 0; i < m; ++i) { starts[2 * i] = nodes[(size_t)kids[k0 + i]].ox; starts[2 * i + 1] = nodes[(size_t)kids[k0 + i]].oy; }
+                r = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) {
                     const TampNode &v = nodes[(size_t)kids[k0 + i]];
-                    if ((r = porrt_set_sampler(T.pool[i], c->s_low, c->s_up, v.h)) < 0) return r;
-                    if ((r = porrt_set_square_goal(T.pool[i], c->zone_pos[v.target], &m1, 1, goal_radius)) < 0) return r;
-                    starts[2 * i] = v.ox; starts[2 * i + 1] = v.oy;
-                }
-                T.info.goals_s += now_s() - t0;
-                t0 = now_s();
-                r = porrt_grow_batch(T.pool.data(), m, starts.data(), max_step, search_radius, n_iter_min, n_iter_max, K, PORRT_MODE_RRT);
-                T.info.grow_s += now_s() - t0;
-                T.info.queries += m; T.vinfo.pickup_queries += m;
-                if (r < 0) { c->set_err(T.pool[0]->err); return r; }
+                    return F.seed_and_goal(T.pool[i], v.h, (uint32_t)v.target, 1);
+                });
+                T.vinfo.pickup_queries += m;
+                if (r < 0) return r;
                 if ((r = tamp_gather(c, T, T.pool.data(), m, paths, costs, ok)) < 0) return r;
                 for (uint32_t i = 0; i < m; ++i) {
                     TampNode &v = nodes[(size_t)kids[k0 + i]];
@@ -245,45 +182,19 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
         T.info.search_nodes = nodes.size();
         // push the children, record the leaves: the sequential order
         for (const auto &mk : made) {
-            const TampNode &u = nodes[(size_t)mk.first];
-            for (size_t ei = mk.second.first; ei < mk.second.second; ++ei)
-                for (int64_t vid : edges[ei].kids) {
-                    TampNode &v = nodes[(size_t)vid];
-                    v.ec = u.ec + v.rp * (v.obs_cost + v.belief[(size_t)v.target] * v.pick_cost);
-                    if (v.ec < best) stack.push_back(vid);
-                    else ++T.info.pruned;
-                }
-            if (u.remaining.empty()) {
-                if (u.ec < best) best = u.ec;
-                if (best_leaf < 0 || u.ec <= nodes[(size_t)best_leaf].ec) best_leaf = mk.first;
-            }
+            std::vector<int64_t> kids;
+            for (size_t ei = mk.second.first; ei < mk.second.second; ++ei) kids.insert(kids.end(), edges[ei].kids.begin(), edges[ei].kids.end());
+            B.close(T, nodes, mk.first, kids);
         }
     }
     T.info.search_nodes = nodes.size();
-    if (best_leaf < 0) {                                   // expect("No solution found!") (:423)
+    if (B.best_leaf < 0) {                                 // expect("No solution found!") (:423)
         c->set_err("No solution found! (no search node reached a leaf: an observation query without solutions makes no children)");
         return PORRT_ERR_NO_PATH;
     }
-    T.info.search_cost = nodes[(size_t)best_leaf].ec;
-    T.info.n_order = 0; T.vinfo.n_ranks = 0;
-    {
-        std::vector<int64_t> chain;
-        for (int64_t k = best_leaf; k > 0; k = nodes[(size_t)k].parent) chain.push_back(k);
-        std::reverse(chain.begin(), chain.end());
-        for (int64_t k : chain) {
-            T.info.zone_order[T.info.n_order++] = (uint32_t)nodes[(size_t)k].target;
-            T.vinfo.ranks[T.vinfo.n_ranks++] = rank_of[(size_t)k];
-        }
-    }
-    restore.on = false;
-    if (streams == 0) c->crng = crng0;
-    const int r = tamp_build_policy(c, T, nodes, best_leaf);
-    if (r < 0) return r;
-    T.valid = true;
-    T.info.pool = (uint32_t)T.pool.size();
-    T.info.total_s = now_s() - t_start;
-    T.info.search_s = T.info.total_s - T.info.grow_s - T.info.path_s - T.info.shortcut_s - T.info.pool_s - T.info.goals_s - T.vinfo.solutions_s;
-    return (int64_t)T.parents.size();
+    T.vinfo.n_ranks = 0;
+    for (int64_t k : tamp_chain(nodes, B.best_leaf)) if (k > 0) T.vinfo.ranks[T.vinfo.n_ranks++] = rank_of[(size_t)k];
+    return F.finish(nodes, B.best_leaf, nullptr, T.vinfo.solutions_s);
 }
 
 } // namespace

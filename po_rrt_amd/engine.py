@@ -427,7 +427,8 @@ class Engine:
                       batch_K=128, search="branch_and_bound"):
         """MapShelfDomainTampRRT::plan(.., TampSearch) (porrt_tamp_rrt_plan): dict of the policy (xy, parents, is_leaf, beliefs,
         expected_cost) and the search's info.  Stream mode, wave width and pool size are the options tamp_streams / tamp_wave /
-        tamp_pool.  Only branch_and_bound is supported; the other two search kinds raise PorrtError (PORRT_ERR_INVALID)."""
+        tamp_pool.  This entry point runs branch_and_bound only and raises PorrtError (PORRT_ERR_INVALID) for the other two search
+        kinds, which have methods of their own: plan_tamp_rrt_astar and plan_tamp_rrt_viewpoints."""
         if search not in self.TAMP_SEARCH:
             raise ValueError("search: one of %s" % sorted(self.TAMP_SEARCH))
         keep = self.get_option("tamp_search")
