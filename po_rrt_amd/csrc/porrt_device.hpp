@@ -345,6 +345,41 @@ template <class T>
 __device__ __forceinline__ T g_atomic_min(GPTR(T) p, T v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ------------------------------------------------------------------ small helpers
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// a wave-uniform double, kept in scalar registers
+__device__ __forceinline__ double uni_d(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned long long lo = uni((uint32_t)b), hi = uni((uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(lo | (hi << 32)));
+}
+
+// A row of run constants as the compiler may read it through the scalar cache.  The fields of a row are wave-uniform, but after a
+// kernel's first store the compiler can no longer prove that the row is unchanged, and a function that is not inlined receives the
+// reference as a generic pointer in vector registers: every later field then costs a vector (or flat_*) load, an address register
+// and a wait that drains all loads in flight, in the middle of a dependent chain.  Here the address is made wave-uniform (uni()) and
+// viewed as constant memory (address space 4) by way of an integer -- a plain address-space cast is folded away --, which the
+// compiler carries through the inlined helpers: the fields become s_load_* wherever they are read.
+// CONTRACT: nothing writes the row while the kernel runs (DESIGN.md section 6 lists every writer: host uploads, k_batch_prep's copy
+// to rc.self, k_rows_gather -- all kernels or copies EARLIER on the stream).  What a row points TO (rc.cnt, the arrays) may change.
+// A function that is not inlined takes the helper again at its entry: an argument is not uniform to the callee.
+// Who takes it: the kernels of the batch growth path and their out-of-line functions, and of the single query k_step1_rrt with
+// file_step_fast and g_track_step (measured).  Not k_row_sched (a row per LANE is not uniform) and not
+// insert_step_pages<0> (k_connect_rrt gained scratch with it).
+// -DPORRT_RC_SCALAR=0: the plain reference everywhere (the A/B of profiles/rc_scalar_experiments.txt).
+#ifndef PORRT_RC_SCALAR
+#define PORRT_RC_SCALAR 1
+#endif
+__device__ __forceinline__ const RunConst &rc_const(const RunConst *p) {
+#if PORRT_RC_SCALAR
+    const uintptr_t a = (uintptr_t)p;
+    const uintptr_t u = (uintptr_t)uni((uint32_t)a) | ((uintptr_t)uni((uint32_t)(a >> 32)) << 32);
+    return *(const RunConst *)(const RunConst __attribute__((address_space(4))) *)u;
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ const RunConst &rc_const(const RunConst &rc) { return rc_const(&rc); }
+
 // what a kernel launched for step b with (i0, nb) does for THIS row
 __device__ __forceinline__ uint32_t row_nb(const RunConst &rc, uint32_t b, uint32_t nb_arg) {
     return rc.sched_nb ? ((GPTR(const uint32_t))(uintptr_t)rc.sched_nb)[b] : nb_arg;
@@ -614,7 +649,7 @@ __device__ __forceinline__ double gen_range_once(unsigned long long r, double lo
 __global__ void k_gen_samples(const RunConst *__restrict__ rcp, const PcgJump *__restrict__ jt, unsigned long long it0,
                               unsigned long long n, unsigned long long st_lo, unsigned long long st_hi,
                               unsigned long long inc_lo, unsigned long long inc_hi, unsigned long long draws_before) {
-    const RunConst &rc = rcp[blockIdx.y];      // one context per grid row; jt == nullptr: table and sampler state from the run constants
+    const RunConst &rc = rc_const(rcp + blockIdx.y);      // one context per grid row; jt == nullptr: table and sampler state from the run constants
     if (!jt) { jt = rc.jump; st_lo = rc.rng_st_lo; st_hi = rc.rng_st_hi; inc_lo = rc.rng_inc_lo; inc_hi = rc.rng_inc_hi; }
     unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -758,14 +793,6 @@ __device__ __forceinline__ uint32_t region_of(const RunConst &rc, double x, doub
 // roundings of d2 and of q -+ rho)
 __device__ __forceinline__ double disc_radius(double bound_d2, double qx, double qy) {
     return sqrt(bound_d2) * (1.0 + 1e-9) + 1e-12 * (1.0 + fabs(qx) + fabs(qy));
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-// a wave-uniform double, kept in scalar registers
-__device__ __forceinline__ double uni_d(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const unsigned long long lo = uni((uint32_t)b), hi = uni((uint32_t)(b >> 32));
-    return __longlong_as_double((long long)(lo | (hi << 32)));
 }
 
 // visit(x, y, id, ok): called by all 64 lanes together; ok = this lane holds a node.  Every node whose region
@@ -1007,7 +1034,11 @@ __global__ __launch_bounds__(256) void k_near(const RunConst *__restrict__ rcp, 
 // positions and validity are final since k_near, ids follow from the valid mask).  Nothing reads the pages
 // between k_near of this step and k_near of the next.
 constexpr uint32_t kInsertLds = kRegions * 4u + 4096u * 2u + 16u;       // bytes of LDS scratch insert_step_pages needs
-__device__ void insert_step_pages(const RunConst &rc, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *scratch) {
+// (TAG: 1 = the group kernels; 0 = k_connect_rrt / k_connect_pto, which keep the plain reference -- with the helper k_connect_rrt, 64 VGPRs by
+// request, went from no scratch to 96 B and 40 spilled VGPRs)
+template <int TAG = 0>
+__device__ void insert_step_pages(const RunConst &rc_arg, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *scratch) {
+    const RunConst &rc = TAG == 1 ? rc_const(rc_arg) : rc_arg;          // (the compiler keeps this function out of line)
     uint32_t *s_add = reinterpret_cast<uint32_t *>(scratch);                            // [kRegions]
     uint16_t *s_off = reinterpret_cast<uint16_t *>(scratch + kRegions * 4u);            // [4096]
     uint32_t &s_np = *reinterpret_cast<uint32_t *>(scratch + kRegions * 4u + 4096u * 2u);
@@ -1083,7 +1114,8 @@ __device__ void insert_step_pages(const RunConst &rc, uint32_t b, uint32_t nb, u
 // pages, which nothing depends on.
 constexpr uint32_t kFileLds = 2u * kRegions * 4u + 4096u * 2u + 64u * 8u + 66u * 4u + 32u;
 template <uint32_t T = 1024u>
-__device__ void file_step_fast(const RunConst &rc, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *scratch) {
+__device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *scratch) {
+    const RunConst &rc = rc_const(rc_arg);          // (out of line in k_step1_rrt and k_coop_rrt)
     uint32_t *s_add = reinterpret_cast<uint32_t *>(scratch);                               // [kRegions] new nodes per region
     uint32_t *s_old = s_add + kRegions;                                                    // [kRegions] counts before the step
     uint16_t *s_off = reinterpret_cast<uint16_t *>(s_old + kRegions);                      // [4096] a sample's place among its region's new nodes
@@ -2110,7 +2142,7 @@ __global__ __launch_bounds__(kConnectWaves * 64) __attribute__((amdgpu_waves_per
     __shared__ int s_i[kConnectWaves];
     __shared__ uint32_t s_heavy[kConnectWaves];
     __shared__ __attribute__((aligned(16))) uint8_t s_ins[kFileLds];
-    const RunConst &rc = rcp[blockIdx.y];
+    const RunConst &rc = rc_const(rcp + blockIdx.y);
     // in launch order: the filing (one workgroup's chain of phases: it must start first), the connect pass (the longest waves),
     // the searches, the rewire commit (short)
     const uint32_t cblocks = (nb + kConnectWaves - 1u) / kConnectWaves, sblocks = (nb_next + 3u) / 4u;
@@ -2313,7 +2345,8 @@ __global__ __launch_bounds__(256) void k_commit_rrt(const RunConst *__restrict__
 // then builds the whole structure after the steps, as with option kd_after, and k_tie_fix settles those records.  Equal costs
 // through different parents off G take coordinates made to collide; the copies of the goal point, the ties of every run that
 // reaches its goal, are all on G.
-template <int TAG> __device__ void g_track_step(const RunConst &rc, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *lds) {
+template <int TAG> __device__ void g_track_step(const RunConst &rc_arg, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *lds) {
+    const RunConst &rc = rc_const(rc_arg);          // (out of line in every caller)
 #ifdef PORRT_GTRACK_TIMING
     const unsigned long long gt0 = wall_clock64();
 #define GT_MARK(slot) do { if (threadIdx.x == 0) { atomicAdd(&rc.cnt->tim[slot], wall_clock64() - gt0); atomicAdd(&rc.cnt->tim[(slot) + 8], 1ull); } } while (0)
@@ -3514,7 +3547,7 @@ __global__ __launch_bounds__(256) void k_trees_out(const TreeOut *__restrict__ t
 struct BatchOut { Counters cnt; uint32_t nodes, pad; };
 __global__ __launch_bounds__(64) void k_batch_gather(const RunConst *__restrict__ rcp, uint32_t steps, BatchOut *__restrict__ out) {
     if (threadIdx.x) return;
-    const RunConst &rc = rcp[blockIdx.x];
+    const RunConst &rc = rc_const(rcp + blockIdx.x);
     BatchOut o;
     o.cnt = *rc.cnt;
     o.nodes = rc.n_at[steps];

@@ -145,7 +145,7 @@ __device__ __forceinline__ uint32_t xcd_swizzle_roles(uint32_t &bx, uint32_t &by
 // tiles, row-major inside).  Samples served by one workgroup -- and by workgroups that run at the same time -- then
 // read the same few region pages.  Any order is a correct order: results are indexed by the sample.
 __global__ __launch_bounds__(256) void k_sort_samples(const RunConst *__restrict__ rcp, uint32_t b0, unsigned long long it0, unsigned long long n, uint32_t K) {
-    const RunConst &rc = rcp[blockIdx.y];      // one context per grid row
+    const RunConst &rc = rc_const(rcp + blockIdx.y);      // one context per grid row
     __shared__ uint32_t s_bin[kRegions];
     __shared__ uint32_t s_tot[256];
     const uint32_t s = blockIdx.x, b = b0 + s;
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_N
     constexpr uint32_t SPB = (uint32_t)WV * 64u / GL;      // (WV waves per workgroup; the search synchronises nothing beyond the wave)
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     xcd_swizzle(bx, by);
-    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
+    const RunConst &rc = rc_const(rcp + by);    // one context per grid row (porrt_grow_batch)
     GTeam<GL> tm;
     tm.gl = threadIdx.x % GL;
     tm.base = (threadIdx.x & 63u) - tm.gl;
@@ -675,7 +675,8 @@ __host__ __device__ inline size_t conn2_wg4_lds_bytes(uint32_t GL) {
 
 // (the connect pass needs these rarely: functions of their own, so that their registers are not the step kernel's)
 template <int GL>
-__device__ __attribute__((noinline)) int group_nn_call(const RunConst &rc, uint32_t b, uint32_t gl, uint32_t base, uint32_t N, double px, double py) {
+__device__ __attribute__((noinline)) int group_nn_call(const RunConst &rc_arg, uint32_t b, uint32_t gl, uint32_t base, uint32_t N, double px, double py) {
+    const RunConst &rc = rc_const(rc_arg);
     GTeam<GL> tm;
     tm.gl = gl; tm.base = base;
     int nn;
@@ -684,7 +685,8 @@ __device__ __attribute__((noinline)) int group_nn_call(const RunConst &rc, uint3
     return nn;
 }
 // nearest node of (px, py) by all 64 lanes of the calling wave (px, py wave-uniform)
-__device__ __attribute__((noinline)) int wave_nn(const RunConst &rc, uint32_t b, uint32_t N, double px, double py) {
+__device__ __attribute__((noinline)) int wave_nn(const RunConst &rc_arg, uint32_t b, uint32_t N, double px, double py) {
+    const RunConst &rc = rc_const(rc_arg);
     GTeam<64> t64;
     t64.gl = threadIdx.x & 63u;
     t64.base = 0;
@@ -724,7 +726,8 @@ __device__ __forceinline__ void list_scan_wave(const RunConst &rc, uint32_t b, u
 
 // The clone workgroup of k_conn2: the step's copies of the goal point, one search for all of them by the 4-wave team.
 // A function of its own (not inlined): its registers are not the step kernel's.
-__device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc, uint32_t b, uint32_t vwords, uint32_t N, double T2) {
+__device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc_arg, uint32_t b, uint32_t vwords, uint32_t N, double T2) {
+    const RunConst &rc = rc_const(rc_arg);
     __shared__ double s_d[kConnectWaves];
     __shared__ int s_i[kConnectWaves];
     __shared__ uint32_t s_cid[64], s_ck[64];
@@ -781,8 +784,9 @@ __device__ __forceinline__ MemHits mem_hits(const RunConst &rc, uint32_t b, uint
 // step kernel's).  Its hits are in its slice of the lists in memory; when the wave's four LDS lists together hold them (4 x kLdsHits:
 // most such samples) they are read back into those lists in one coalesced pass and the three passes of the connect run on LDS.
 template <int GL>
-__device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc, uint32_t b, uint32_t N, uint32_t kh, uint32_t idh, uint32_t toth, int clrh,
+__device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc_arg, uint32_t b, uint32_t N, uint32_t kh, uint32_t idh, uint32_t toth, int clrh,
                                                             double pxh, double pyh, uint8_t *wb, uint32_t &err) {
+    const RunConst &rc = rc_const(rc_arg);
     const uint32_t lane = threadIdx.x & 63u;
     constexpr uint32_t kWaveHits = (64u / (uint32_t)GL) * (kLdsHits * (uint32_t)(GL / 16));
     Team<1> tw;
@@ -926,7 +930,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     xcd_swizzle(bx, by);
-    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
+    const RunConst &rc = rc_const(rcp + by);    // one context per grid row (porrt_grow_batch)
     nb = row_nb(rc, b, nb);
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
     if (bx * SPB >= nb) return;                 // (a row that has stopped, does not run this step, or runs a shorter one)
@@ -946,11 +950,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_
 // (The register request of k_conn2_wg4: clone_workgroup is a function of both kernels and is compiled to the larger of their budgets.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_riders(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
-    const RunConst &rc = rcp[blockIdx.y];
+    const RunConst &rc = rc_const(rcp + blockIdx.y);
     const uint32_t role = blockIdx.x;
     nb = row_nb(rc, b, nb);
     if (nb == 0) return;
-    if (role == 0) { insert_step_pages(rc, b, nb, vwords, lds_dyn); return; }
+    if (role == 0) { insert_step_pages<1>(rc, b, nb, vwords, lds_dyn); return; }
     if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
     clone_workgroup(rc, b, vwords, as_global(rc.n_at)[b], as_global(rc.t2_at)[b]);
 }
@@ -965,10 +969,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     const uint32_t ns = lazy ? 3u : 2u;         // the rows' special workgroups: page filing, goal-point copies, (lazy) the goal path of the kd order
     const uint32_t role = xcd_swizzle_roles(bx, by, ns);
-    const RunConst &rc = rcp[by];               // one context per grid row (porrt_grow_batch)
+    const RunConst &rc = rc_const(rcp + by);    // one context per grid row (porrt_grow_batch)
     nb = row_nb(rc, b, nb);
     if (nb == 0) return;                        // (a row that has stopped, or does not run this step)
-    if (role == 0) { insert_step_pages(rc, b, nb, vwords, lds_dyn); return; }    // the page-filing workgroup
+    if (role == 0) { insert_step_pages<1>(rc, b, nb, vwords, lds_dyn); return; }    // the page-filing workgroup
     if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
     // first round trip: everything that depends on nothing
@@ -984,12 +988,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
 // stand-alone rewire phase 2 for the last step of a launch sequence, GL lanes per sample
 template <int GL>
 __global__ __launch_bounds__(256) void k_commit2(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords) {
+    const RunConst &rc = rc_const(rcp + blockIdx.y);
     const uint32_t k = (blockIdx.x * 256u + threadIdx.x) / GL;
-    if (k < nb && k < row_nb(rcp[blockIdx.y], b, nb)) commit_rrt_sample(rcp[blockIdx.y], b, vwords, k, threadIdx.x % GL, GL);
+    if (k < nb && k < row_nb(rc, b, nb)) commit_rrt_sample(rc, b, vwords, k, threadIdx.x % GL, GL);
 }
 // the same from a flat index (commit_flat_span): grid = (ceil(nb / kSpan), Q).  It needs few registers and asks for eight waves per SIMD.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_commit_flat(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords) {
-    commit_flat_span<256u>(rcp[blockIdx.y], b, vwords, nb, blockIdx.x);
+    commit_flat_span<256u>(rc_const(rcp + blockIdx.y), b, vwords, nb, blockIdx.x);
 }
 
 } // namespace porrt
