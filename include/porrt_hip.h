@@ -388,6 +388,55 @@ int64_t  porrt_refine_policies(porrt_ctx *ctx, uint64_t n_policies, const uint64
 struct porrt_refine_policies_info { uint64_t policies, ok, pieces, shortcut_pieces, nodes, distinct_lengths; double ms_device, ms_wall; };
 int      porrt_refine_policies_info(const porrt_ctx *ctx, struct porrt_refine_policies_info *out);
 
+/* ---- PTO::plan_belief_space (src/pto.rs:152-182) for many grown contexts of one device in one call: the second half of the loops
+ * the reference's experiments run (main.rs:40-68: one map, one prior, a new sample stream per run), after porrt_grow_batch has
+ * served the first.  Member q's answer is, bit for bit, what the same context gives alone through
+ *     porrt_build_belief_graph(ctx, start_belief, n_worlds); porrt_bg_compute_expected_costs;
+ *     porrt_bg_extract_policies with the one start 0; porrt_bg_refine_policies(refine_iterations) when refine_iterations > 0.
+ * A helper context owned by ctxs[0] (the leader) adopts the disjoint union of the members' PTO graphs, gathered on the device, and
+ * runs those stages once on it; no edge joins two members, so every member's costs and policy on the union are its own.
+ * status[q]: the extraction's status (0 .. 4, as porrt_bg_extract_policies documents them; 1 covers a root without finite cost: no
+ * final node, an incomplete final set after a PORRT_INCOMPLETE growth); expected_costs[q]: the root's cost; refine_status[q] and
+ * refined_costs[q] (either may be NULL): those of porrt_bg_refine_policies, 1 and +0.0 when refine_iterations is 0.  Policy q is rows
+ * pol_off[q] .. pol_off[q + 1] of xy (2 per node: the states) / original_ids (the member's OWN belief node ids, graph node *
+ * n_beliefs + belief) / parents / is_leaf: the refined policy when refine_iterations > 0, the extracted one otherwise.  A member with
+ * nonzero status contributes no rows and does not void the others; porrt_last_error(ctxs[0]) names the first.  pol_off (n_ctx + 1),
+ * status and expected_costs are always written, the node arrays only if the total fits cap (cap = 0 sizes).  Returns the total number
+ * of policy nodes, or a negative error.  n_ctx = 0 returns 0 and writes pol_off[0] = 0.
+ * PORRT_ERR_INVALID before any launch (porrt_last_error(ctxs[0]) names the member): a NULL array or member, the same context twice,
+ * members on different devices, a member without PTO results, n_worlds not the members' own, a prior that does not sum to 1,
+ * members whose domain data differ from the leader's (W, H, low, up, the domain kind, the occupancy and zone bytes, the visibility:
+ * compared on the host).  Goals, starts, seeds, batch_K and node counts may differ; the graphs may come from porrt_grow_batch or from
+ * single porrt_grow calls.  An error of a stage (a raster fault of the visibility raycast, say) is the call's error.
+ * The members stay as they are: their trees and any belief graph, costs, policies or refinements they hold are neither read as
+ * results nor changed (the host copies of their trees may be fetched).  The answers are snapshots kept on the leader:
+ * porrt_plan_batch_get_policies and porrt_plan_batch_info hand them out again, a later regrowth of a member does not invalidate them.
+ * Members are taken in order into a pass -- one union -- while the sum of their nodes x n_beliefs stays at or below option
+ * "plan_batch_max_belief_nodes" (default 2^22, at most 2^32 - 2); a member that alone exceeds it runs alone.  The answers do not
+ * depend on the cut, the time does: a level of a pass's cost sweeps goes on until its slowest member's costs stand, and small passes
+ * pay a pass's fixed costs more often (BASELINE.md has the measurement behind the default).  PORRT_ERR_CAPACITY when a pass's device buffers cannot be allocated (never a truncated answer).
+ * porrt_plan_batch_get_expected_costs copies member `member`'s cost vector (its nodes x n_beliefs doubles, what
+ * porrt_bg_get_expected_costs gives for the context alone) from the device: members of the LAST pass only, PORRT_ERR_INVALID
+ * otherwise.  All three getters are an error before the first successful call.  The dynamic programming's schedule and
+ * "policy_max_nodes" are read from the leader's options; "plan_batch_host_ranks" (default 1) takes the adjacency order's kd ranks
+ * from the members' host kd-trees, 0 makes them on the device, a workgroup per member.
+ * Info: counts summed over the passes (graph nodes and edges, belief nodes and edges, final belief nodes, members with status 0,
+ * policy nodes returned) and milliseconds: the whole call, gathering the union (with its download), the adjacency order (ranks
+ * included), the belief graph, the costs, the policy walk, the refinement -- host clock around stages that end in a synchronise --
+ * and the HIP-event times those stages report themselves, summed. */
+int64_t  porrt_plan_belief_space_batch(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *start_belief, uint32_t n_worlds,
+                                       uint64_t refine_iterations, uint64_t *pol_off, uint8_t *status, double *expected_costs,
+                                       uint8_t *refine_status, double *refined_costs, double *xy, uint64_t *original_ids, int64_t *parents,
+                                       uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_plan_batch_get_policies(const porrt_ctx *leader, uint64_t *pol_off, double *xy, uint64_t *original_ids, int64_t *parents,
+                                       uint8_t *is_leaf, uint64_t cap);
+int      porrt_plan_batch_get_expected_costs(const porrt_ctx *leader, uint32_t member, double *out);
+struct porrt_plan_batch_info {
+    uint64_t members, passes, graph_nodes, graph_edges, beliefs, belief_nodes, belief_edges, final_belief_nodes, policies_ok, policy_nodes;
+    double ms_wall, ms_join, ms_edge_order, ms_belief_graph, ms_costs, ms_policies, ms_refine, ms_device;
+};
+int      porrt_plan_batch_info(const porrt_ctx *leader, struct porrt_plan_batch_info *out);
+
 /* ---- the other strategy: PTOPolicyRefiner::refine_solution(RefinmentStrategy::Reparent(radius)) (pto_policy_refiner.rs:209-322), of
  * one policy or many in one call, on the device.  Per piece of the policy (the decomposition above): build_tree makes the piece's path
  * a tree and adds belief-graph offsprings within `radius` of a path node; reparent pops the tree's nodes by distance from the root and

@@ -744,6 +744,28 @@ static int bg_scan(const uint32_t *deg, size_t n, unsigned long long *tot, unsig
 
 static double bg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// The belief states reachable from start_belief and their compatibilities into bc, unless it holds them already (a build's first
+// host step; porrt_plan_belief_space_batch asks for the number of beliefs before it cuts its passes).
+static int belief_cache_fill(BeliefCache &bc, int domain, int n_zones, int n_validities, int n_worlds, const uint64_t *validities, const double *start_belief,
+                             std::string &err) {
+    if (bc.matches(domain, n_zones, n_validities, (uint32_t)n_worlds, validities, start_belief)) return PORRT_OK;
+    bc = BeliefCache();
+    bc.domain = domain; bc.nz = n_zones; bc.nv = n_validities; bc.nw = (uint32_t)n_worlds;
+    bc.validities.assign(validities, validities + n_validities);
+    bc.start.assign(start_belief, start_belief + n_worlds);
+    bc.space.domain = domain; bc.space.nz = n_zones; bc.space.nw = bc.nw; bc.space.validities = bc.validities.data();
+    const int r = bc.space.reach_from(start_belief, err);
+    if (r) { bc = BeliefCache(); return r; }
+    bc.compat.assign(bc.space.size(), 0);                       // compute_compatibility (common.rs:266-276)
+    for (size_t b = 0; b < bc.space.size(); ++b)
+        for (int v = 0; v < n_validities; ++v) {
+            bool ok = true;
+            for (uint32_t w = 0; w < bc.nw && ok; ++w) ok = !(bc.space.at(b)[w] > 0.0) || ((validities[v] >> w) & 1ull);
+            if (ok) bc.compat[b] |= 1ull << v;
+        }
+    return PORRT_OK;
+}
+
 // PTO::build_belief_graph.  The PTO graph is the one of the context's last grow (mode PTO).
 static int belief_graph_build(BeliefGraphState &g, const BeliefInputs &in, const double *start_belief, std::string &err) {
     g.release();
@@ -787,21 +809,9 @@ static int belief_graph_build(BeliefGraphState &g, const BeliefInputs &in, const
     // ... while the raycasts run: the belief states and the adjacency lists, which do not depend on them
     const double tr0 = bg_now();
     BeliefCache &bc = g.cache;
-    if (!bc.matches(in.domain, in.n_zones, in.n_validities, (uint32_t)in.n_worlds, in.validities, start_belief)) {
-        bc = BeliefCache();
-        bc.domain = in.domain; bc.nz = in.n_zones; bc.nv = in.n_validities; bc.nw = (uint32_t)in.n_worlds;
-        bc.validities.assign(in.validities, in.validities + in.n_validities);
-        bc.start.assign(start_belief, start_belief + in.n_worlds);
-        bc.space.domain = in.domain; bc.space.nz = in.n_zones; bc.space.nw = bc.nw; bc.space.validities = bc.validities.data();
-        r = bc.space.reach_from(start_belief, err);
-        if (r) { bc = BeliefCache(); (void)hipStreamSynchronize(s); return r; }          // the copies above target this frame
-        bc.compat.assign(bc.space.size(), 0);                       // compute_compatibility (common.rs:266-276)
-        for (size_t b = 0; b < bc.space.size(); ++b)
-            for (int v = 0; v < in.n_validities; ++v) {
-                bool ok = true;
-                for (uint32_t w = 0; w < bc.nw && ok; ++w) ok = !(bc.space.at(b)[w] > 0.0) || ((in.validities[v] >> w) & 1ull);
-                if (ok) bc.compat[b] |= 1ull << v;
-            }
+    if ((r = belief_cache_fill(bc, in.domain, in.n_zones, in.n_validities, in.n_worlds, in.validities, start_belief, err))) {
+        (void)hipStreamSynchronize(s);                               // the copies above target this frame
+        return r;
     }
     const BeliefSpace &bs = bc.space;
     const std::vector<unsigned long long> &compat = bc.compat;

@@ -239,9 +239,11 @@ static int kd_ranks_device(EdgeOrderState &st, size_t N, const double *d_x, cons
 }
 
 // Orders the E edges (d_from, d_to, d_val: the growth kernels' arrays) of a graph of N nodes; the nodes' pre-order ranks come from
-// h_rank (host) or, when that is null, are made on the device from the coordinates (d_x, d_y).
+// h_rank (host), from d_rank (device: made by the caller, e.g. per segment of a union of graphs -- a rank is only ever compared inside
+// one node's bucket) or, when both are null, are made on the device from the coordinates (d_x, d_y).
 static int edge_order_build(EdgeOrderState &st, uint64_t tag, size_t N, size_t E, const uint32_t *d_from, const uint32_t *d_to, const uint32_t *d_val,
-                            const std::vector<uint32_t> *h_rank, const double *d_x, const double *d_y, hipStream_t s, std::string &err) {
+                            const std::vector<uint32_t> *h_rank, const double *d_x, const double *d_y, hipStream_t s, std::string &err,
+                            const uint32_t *d_rank = nullptr) {
     const double t0 = bg_now();
     st.next_slot = 0;
     st.tag = ~0ull;
@@ -260,6 +262,7 @@ static int edge_order_build(EdgeOrderState &st, uint64_t tag, size_t N, size_t E
         (r = eo_alloc(st, off_to, N + 2, err)) || (r = eo_alloc(st, off_from, N + 2, err)) || (r = eo_alloc(st, tot, nblk + 2, err)))
         return r;
     if (h_rank) EO_HIP(hipMemcpyAsync(rank, h_rank->data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    else if (d_rank) EO_HIP(hipMemcpyAsync(rank, d_rank, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     else if ((r = kd_ranks_device(st, N, d_x, d_y, rank, s, err))) return r;
     EO_HIP(hipMemsetAsync(deg_to, 0, (N + 1) * sizeof(uint32_t), s));
     EO_HIP(hipMemsetAsync(deg_from, 0, (N + 1) * sizeof(uint32_t), s));

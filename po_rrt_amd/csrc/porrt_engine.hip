@@ -21,6 +21,7 @@
 #include "porrt_refine_batch.hpp"
 #include "porrt_reparent.hpp"
 #include "porrt_qmdp.hpp"
+#include "porrt_join.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -80,7 +81,7 @@ struct porrt_ctx {
     // ---- domain (host copies)
     std::vector<uint8_t> occ, zones, cls;
     uint32_t W = 0, H = 0;
-    double low[2] = {0, 0}, ppm = 0;
+    double low[2] = {0, 0}, up[2] = {0, 0}, ppm = 0;
     int domain = 0;
     bool has_grid = false, cls_dirty = true;
     double visibility = 0;
@@ -336,6 +337,10 @@ struct porrt_ctx {
     uint32_t opt_tamp_wave = 128;          // "tamp_wave": search nodes popped per wave (tamp_streams = 1; 128: fastest measured)
     uint32_t opt_tamp_pool = 512;          // "tamp_pool": worker contexts (queries of one porrt_grow_batch)
     uint64_t opt_tamp_arena_states = 1ull << 20;   // "tamp_arena_states": initial capacity of the A* search's path arena (states of 16 B; it grows)
+    std::shared_ptr<void> plan_batch;      // porrt_plan_belief_space_batch (porrt_plan_batch.hpp): PlanBatchState -- the helper context that adopts a pass's union, the last call's answers
+    uint64_t opt_plan_batch_max_belief_nodes = kJoinBeliefNodesDefault;    // "plan_batch_max_belief_nodes": members share a pass while their belief nodes stay at or below this
+    int opt_plan_batch_host_ranks = 1;     // "plan_batch_host_ranks": 1 = the union's kd pre-order ranks from the members' host kd-trees, 0 = made on the device (k_seg_kd_ranks, a workgroup per member)
+    uint64_t n_final_belief_nodes = 0;     // final belief nodes of the last expected-cost run
     int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; porrt_tamp_rrt_plan refuses 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints), which have entry points of their own
     int mm_upload_roadmaps();
     int mm_build_belief_graph();
@@ -1716,6 +1721,7 @@ int porrt_ctx::compute_expected_costs() {
             if (!(possible[b] & ~finality)) finals.push_back((unsigned long long)(id * B + b));     // is_compatible(belief_state, validity)
         }
     }
+    n_final_belief_nodes = finals.size();
     DpConst c{};
     c.n = (unsigned long long)(bg.N * bg.B); c.B = (uint32_t)bg.B; c.nw = bg.nw;
     c.nx = d_nx.p; c.ny = d_ny.p; c.bvec = nullptr; c.beliefs = bg.d_beliefs; c.types = bg.d_types;
@@ -3349,6 +3355,7 @@ static BatchRows porrt_batch_rows(porrt_ctx *const *ctxs, uint32_t n, uint32_t q
 #include "porrt_tamp.hpp"
 #include "porrt_tamp_viewpoints.hpp"
 #include "porrt_tamp_astar.hpp"
+#include "porrt_plan_batch.hpp"
 
 extern "C" {
 
@@ -3378,6 +3385,7 @@ porrt_ctx *porrt_create(int device) {
 void porrt_destroy(porrt_ctx *c) {
     if (!c) return;
     c->tamp.reset();                          // the TAMP planner's worker contexts and buffers
+    c->plan_batch.reset();                    // porrt_plan_belief_space_batch's helper context and answers
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (hipStream_t st : c->sub_streams) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -3424,6 +3432,7 @@ int porrt_set_grid(porrt_ctx *c, const uint8_t *occ, uint32_t W, uint32_t H, con
     c->zones.clear();
     c->W = W; c->H = H;
     c->low[0] = low[0]; c->low[1] = low[1];
+    c->up[0] = up[0]; c->up[1] = up[1];
     c->ppm = (double)W / (up[0] - low[0]);      // map_shelves_io.rs:89
     c->domain = domain;
     c->has_grid = true;
@@ -4306,6 +4315,56 @@ int porrt_refine_policies_info(const porrt_ctx *c, struct porrt_refine_policies_
 
 // ---- refine_solution(Reparent(radius)) (porrt_reparent.hpp)
 // the context's belief graph as the Reparent strategy reads it: the graph the expected costs were computed on
+// ---- PTO::plan_belief_space for many grown contexts in one call (porrt_plan_batch.hpp)
+int64_t porrt_plan_belief_space_batch(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *start_belief, uint32_t n_worlds, uint64_t refine_iterations,
+                                      uint64_t *pol_off, uint8_t *status, double *expected_costs, uint8_t *refine_status, double *refined_costs, double *xy,
+                                      uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (n_ctx == 0) {
+        if (!pol_off) return PORRT_ERR_INVALID;
+        pol_off[0] = 0;
+        return 0;
+    }
+    if (!ctxs || !ctxs[0]) return PORRT_ERR_INVALID;
+    for (uint32_t q = 1; q < n_ctx; ++q)
+        if (!ctxs[q]) { ctxs[0]->set_err("plan_belief_space_batch: member " + std::to_string(q) + " is NULL"); return PORRT_ERR_INVALID; }
+    return abi_guard([&]() -> int64_t {
+        return plan_belief_space_batch(ctxs, n_ctx, start_belief, n_worlds, refine_iterations, pol_off, status, expected_costs, refine_status, refined_costs, xy,
+                                       original_ids, parents, is_leaf, cap);
+    });
+}
+static const PlanBatchState *plan_batch_answers(const porrt_ctx *c, const char *who) {
+    if (!c) return nullptr;
+    const PlanBatchState *S = (const PlanBatchState *)c->plan_batch.get();
+    if (!S || !S->valid) { const_cast<porrt_ctx *>(c)->set_err(std::string(who) + ": no answers: call porrt_plan_belief_space_batch first"); return nullptr; }
+    return S;
+}
+int64_t porrt_plan_batch_get_policies(const porrt_ctx *c, uint64_t *pol_off, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    const PlanBatchState *S = plan_batch_answers(c, "plan_batch_get_policies");
+    if (!S) return PORRT_ERR_INVALID;
+    return plan_batch_copy_out(*S, pol_off, nullptr, nullptr, nullptr, nullptr, xy, original_ids, parents, is_leaf, cap);
+}
+int porrt_plan_batch_get_expected_costs(const porrt_ctx *c, uint32_t member, double *out) {
+    const PlanBatchState *S = plan_batch_answers(c, "plan_batch_get_expected_costs");
+    if (!S || !out) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);
+    const size_t n_last = S->last_noff.size() ? S->last_noff.size() - 1 : 0;
+    if (member < S->last_first || member - S->last_first >= n_last || !S->helper->dp.valid) {
+        m->set_err("plan_batch_get_expected_costs: member " + std::to_string(member) + " is not of the last pass (its costs are gone)");
+        return PORRT_ERR_INVALID;
+    }
+    const uint32_t q = member - S->last_first;
+    HIPCHK_CTX(m, hipSetDevice(c->device));
+    HIPCHK_CTX(m, hipMemcpy(out, S->helper->dp.d_dist + S->last_noff[q] * S->last_B, (S->last_noff[q + 1] - S->last_noff[q]) * S->last_B * sizeof(double),
+                            hipMemcpyDeviceToHost));
+    return PORRT_OK;
+}
+int porrt_plan_batch_info(const porrt_ctx *c, struct porrt_plan_batch_info *out) {
+    const PlanBatchState *S = plan_batch_answers(c, "plan_batch_info");
+    if (!S || !out) return PORRT_ERR_INVALID;
+    *out = S->info;
+    return PORRT_OK;
+}
+
 static ReparentGraph reparent_bg_graph(const porrt_ctx *c) {
     const DpConst &d = c->dp.last;
     return ReparentGraph{d.nx, d.ny, nullptr, d.child_off, d.child_id, d.B, d.n};
@@ -4886,6 +4945,8 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
     else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
+    else if (!strcmp(name, "plan_batch_max_belief_nodes")) *value = (int64_t)c->opt_plan_batch_max_belief_nodes;
+    else if (!strcmp(name, "plan_batch_host_ranks")) *value = c->opt_plan_batch_host_ranks;
     else if (!strcmp(name, "refine_short_lds")) *value = c->opt_refine_short_lds ? 1 : 0;
     else if (!strcmp(name, "reparent_max_tree_nodes")) *value = c->opt_reparent_max_tree_nodes;
     else if (!strcmp(name, "reparent_max_pops_per_node")) *value = c->opt_reparent_max_pops_per_node;
@@ -4941,6 +5002,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "prm_rows")) { if (value < 1 || value > 4096) { c->set_err("prm_rows: 1 .. 4096"); return PORRT_ERR_INVALID; } c->opt_prm_rows = (uint32_t)value; }
     else if (!strcmp(name, "prm_xcd_rows")) c->opt_prm_xcd_rows = value != 0;
     else if (!strcmp(name, "policy_max_nodes")) { if (value < 1 || value > (int64_t)kPolMaxNodesLimit) { c->set_err("policy_max_nodes: 1 .. 2^24"); return PORRT_ERR_INVALID; } c->opt_policy_max_nodes = (uint32_t)value; }
+    else if (!strcmp(name, "plan_batch_max_belief_nodes")) { if (value < 1 || value > (int64_t)kJoinBeliefNodesLimit) { c->set_err("plan_batch_max_belief_nodes: 1 .. 2^32 - 2"); return PORRT_ERR_INVALID; } c->opt_plan_batch_max_belief_nodes = (uint64_t)value; }
+    else if (!strcmp(name, "plan_batch_host_ranks")) c->opt_plan_batch_host_ranks = value != 0;
     else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again

@@ -110,7 +110,7 @@ static TampState &tamp_state(porrt_ctx *c) {
 static void tamp_copy_domain(porrt_ctx *d, const porrt_ctx *s) {
     d->occ = s->occ; d->zones = s->zones;
     d->W = s->W; d->H = s->H;
-    d->low[0] = s->low[0]; d->low[1] = s->low[1]; d->ppm = s->ppm;
+    d->low[0] = s->low[0]; d->low[1] = s->low[1]; d->up[0] = s->up[0]; d->up[1] = s->up[1]; d->ppm = s->ppm;
     d->domain = s->domain; d->has_grid = s->has_grid;
     d->visibility = s->visibility;
     d->n_zones = s->n_zones; d->n_worlds = s->n_worlds; d->n_validities = s->n_validities;

@@ -53,6 +53,7 @@ SYMBOLS = [
     "porrt_bg_refine_policies", "porrt_mm_refine_policies", "porrt_refine_policies", "porrt_refine_policies_info",
     "porrt_bg_reparent_policies", "porrt_bg_get_reparented_policies", "porrt_bg_reparent_policy", "porrt_reparent_policies",
     "porrt_reparent_policies_info",
+    "porrt_plan_belief_space_batch", "porrt_plan_batch_get_policies", "porrt_plan_batch_get_expected_costs", "porrt_plan_batch_info",
 ]
 
 
@@ -115,6 +116,13 @@ class ReparentPoliciesInfo(C.Structure):
     """struct porrt_reparent_policies_info"""
     _fields_ = [(k, C.c_uint64) for k in ("policies", "ok", "pieces", "tree_nodes", "max_tree", "pairs", "pops", "reparents", "nodes", "rounds")] + \
                [(k, C.c_double) for k in ("ms_tube", "ms_neighbours", "ms_pop", "ms_recompose", "ms_wall")]
+
+
+class PlanBatchInfo(C.Structure):
+    """struct porrt_plan_batch_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("members", "passes", "graph_nodes", "graph_edges", "beliefs", "belief_nodes", "belief_edges",
+                                          "final_belief_nodes", "policies_ok", "policy_nodes")] + \
+               [(k, C.c_double) for k in ("ms_wall", "ms_join", "ms_edge_order", "ms_belief_graph", "ms_costs", "ms_policies", "ms_refine", "ms_device")]
 
 
 class TreeDeviceView(C.Structure):
@@ -298,6 +306,10 @@ def load_library():
     sig("porrt_reparent_policies", C.c_int64, vp, C.c_uint64, _f64p, _u32p, _f64p, C.c_uint32, C.c_uint32, _u64p, _u32p, C.c_uint64, _u64p, _u64p, _i64p,
         C.c_double, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_reparent_policies_info", C.c_int, vp, C.POINTER(ReparentPoliciesInfo))
+    sig("porrt_plan_belief_space_batch", C.c_int64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64)
+    sig("porrt_plan_batch_get_policies", C.c_int64, vp, vp, vp, vp, vp, vp, C.c_uint64)
+    sig("porrt_plan_batch_get_expected_costs", C.c_int, vp, C.c_uint32, vp)
+    sig("porrt_plan_batch_info", C.c_int, vp, C.POINTER(PlanBatchInfo))
     _LIB = L
     return L
 
@@ -934,6 +946,59 @@ class Engine:
         i = RefinePoliciesInfo()
         self._chk(self._l.porrt_refine_policies_info(self._c, C.byref(i)))
         return {k: getattr(i, k) for k, _ in RefinePoliciesInfo._fields_}
+
+    # ---- PTO::plan_belief_space for many grown engines in one device call (porrt_plan_belief_space_batch)
+    @staticmethod
+    def plan_belief_space_batch_raw(engines, start_belief, refine_iterations=0):
+        """porrt_plan_belief_space_batch as arrays: pol_off [n + 1], status [n], expected costs [n], refine status [n], refined costs [n],
+        states [total, 2], original ids (the member's own belief node ids), parents, leaf flags.  The call sizes (cap 0), the nodes come
+        from porrt_plan_batch_get_policies."""
+        engines = list(engines)
+        n = len(engines)
+        lead = engines[0]
+        arr = (C.c_void_p * n)(*[e._c for e in engines])
+        b = np.ascontiguousarray(start_belief, dtype=np.float64)
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint8), np.zeros(n)
+        rstatus, rcost = np.zeros(n, dtype=np.uint8), np.zeros(n)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        total = lead._chk(int(lead._l.porrt_plan_belief_space_batch(arr, n, p(b), len(b), int(refine_iterations), p(off), p(status), p(cost), p(rstatus),
+                                                                    p(rcost), None, None, None, None, 0)))
+        B = lead.plan_batch_info()["beliefs"]
+        lead._plan_batch_sizes = [e.num_nodes() * B for e in engines]        # what plan_batch_expected_costs sizes its answer by
+        xy, oid, par, leaf = np.zeros((total, 2)), np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
+        if total:
+            lead._chk(int(lead._l.porrt_plan_batch_get_policies(lead._c, None, p(xy), p(oid), p(par), p(leaf), total)))
+        return off, status, cost, rstatus, rcost, xy, oid, par, leaf
+
+    @staticmethod
+    def plan_belief_space_batch(engines, start_belief, refine_iterations=0):
+        """PTO::plan_belief_space (pto.rs:152-182) for every engine of the list (grown in MODE_PTO on one map) in one device call: per
+        member (status, expected cost of the root, refine status, refined cost, policy) with policy = (states [k, 2], the member's own
+        belief node ids, parents, leaf flags) -- the refined policy when refine_iterations > 0, the extracted one otherwise -- or None
+        where the member has none.  The answers live on engines[0] (plan_batch_info, plan_batch_expected_costs)."""
+        off, status, cost, rstatus, rcost, xy, oid, par, leaf = Engine.plan_belief_space_batch_raw(engines, start_belief, refine_iterations)
+        out = []
+        for q in range(len(status)):
+            a, b = int(off[q]), int(off[q + 1])
+            gone = status[q] != 0 or (refine_iterations > 0 and rstatus[q] != 0)
+            out.append((int(status[q]), float(cost[q]), int(rstatus[q]), float(rcost[q]), None if gone else (xy[a:b], oid[a:b], par[a:b], leaf[a:b])))
+        return out
+
+    def plan_batch_info(self):
+        """porrt_plan_batch_info of the last plan_belief_space_batch this engine led: counts and milliseconds per stage"""
+        i = PlanBatchInfo()
+        self._chk(self._l.porrt_plan_batch_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in PlanBatchInfo._fields_}
+
+    def plan_batch_expected_costs(self, member):
+        """the expected costs of one member of the last pass of the last plan_belief_space_batch this engine led (the member's
+        nodes x beliefs values, as expected_costs gives them for the engine alone), copied from the device"""
+        sizes = getattr(self, "_plan_batch_sizes", [])
+        if not 0 <= int(member) < len(sizes):
+            raise PorrtError(-1, "plan_batch_expected_costs: no member %d in the last plan_belief_space_batch of this engine" % member)
+        d = np.zeros(int(sizes[int(member)]))
+        self._chk(self._l.porrt_plan_batch_get_expected_costs(self._c, int(member), d.ctypes.data_as(C.c_void_p)))
+        return d
 
     # ---- the Reparent strategy (PTOPolicyRefiner::refine_solution(Reparent(radius)), pto_policy_refiner.rs:209-322)
     def reparent_policies_raw(self, radius):
