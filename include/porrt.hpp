@@ -798,19 +798,62 @@ public:
                                                     max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
         return read_policy(r, initial_belief_state.size());
     }
+    // plan_astar for many (start, prior, seed) on this planner's map in one device call (porrt_tamp_rrt_plan_astar_batch, DESIGN.md
+    // section 25): plan p is, bit for bit, plan_astar alone with the continuous sampler seeded seeds[p] (seeds empty: this planner's
+    // seed for every plan).  A plan without a path has status PORRT_ERR_NO_PATH in its record and an empty policy; it does not throw.
+    struct AstarBatch {
+        std::vector<Policy> policies;
+        std::vector<porrt_tamp_batch_plan> plans;
+        size_t n_ok = 0;
+    };
+    AstarBatch plan_astar_batch(const std::vector<State> &starts, const std::vector<BeliefState> &priors, const std::vector<uint64_t> &seeds,
+                                double max_step, double search_radius, size_t n_iter_min, size_t n_iter_max, uint32_t batch_K = 128) {
+        if (starts.size() != priors.size() || (!seeds.empty() && seeds.size() != starts.size()))
+            throw std::runtime_error("MapShelfDomainTampRRT::plan_astar_batch: one start, one prior and (if any) one seed per plan");
+        const size_t n = starts.size(), nw = n ? priors[0].size() : 0;
+        std::vector<double> st, pr;
+        for (size_t p = 0; p < n; ++p) {
+            if (priors[p].size() != nw) throw std::runtime_error("MapShelfDomainTampRRT::plan_astar_batch: priors of different sizes");
+            st.insert(st.end(), starts[p].begin(), starts[p].end());
+            pr.insert(pr.end(), priors[p].begin(), priors[p].end());
+        }
+        const int64_t r = porrt_tamp_rrt_plan_astar_batch(ctx_.get(), (uint32_t)n, st.data(), pr.data(), seeds.empty() ? nullptr : seeds.data(),
+                                                          (uint32_t)nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
+        if (r < 0) ctx_.check((int)r);
+        AstarBatch out;
+        out.n_ok = (size_t)r;
+        out.policies.resize(n);
+        out.plans.resize(n);
+        for (size_t p = 0; p < n; ++p) {
+            ctx_.check(porrt_tamp_batch_get_plan(ctx_.get(), (uint32_t)p, &out.plans[p]));
+            if (out.plans[p].status != PORRT_OK) continue;
+            const uint32_t plan = (uint32_t)p;
+            out.policies[p] = read_policy((int64_t)out.plans[p].policy_nodes, nw, [&](double *xy, int64_t *par, uint8_t *leaf, double *bel, uint64_t cap, double *cost) {
+                return porrt_tamp_batch_policy(ctx_.get(), plan, xy, par, leaf, bel, cap, cost);
+            });
+        }
+        return out;
+    }
     porrt_tamp_astar_info astar_info() const { porrt_tamp_astar_info i; ctx_.check(porrt_tamp_rrt_get_astar_info(ctx_.get(), &i)); return i; }
     porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
     porrt_tamp_viewpoints_info viewpoints_info() const { porrt_tamp_viewpoints_info i; ctx_.check(porrt_tamp_rrt_get_viewpoints_info(ctx_.get(), &i)); return i; }
     const Context &context() const { return ctx_; }
 private:
     Policy read_policy(int64_t r, size_t nw) {
+        return read_policy(r, nw, [&](double *xy, int64_t *par, uint8_t *leaf, double *bel, uint64_t cap, double *cost) {
+            return porrt_tamp_rrt_policy(ctx_.get(), xy, par, leaf, bel, cap, cost);
+        });
+    }
+    // fetch(xy, parents, is_leaf, beliefs, cap, expected_cost): porrt_tamp_rrt_policy, or a batch plan's porrt_tamp_batch_policy
+    template <class Fetch>
+    Policy read_policy(int64_t r, size_t nw, Fetch fetch) {
         if (r < 0) ctx_.check((int)r);
         const size_t n = (size_t)r;
         std::vector<double> xy(2 * n), bel(n * nw);
         std::vector<int64_t> par(n);
         std::vector<uint8_t> leaf(n);
         Policy policy;
-        const int64_t m = porrt_tamp_rrt_policy(ctx_.get(), xy.data(), par.data(), leaf.data(), bel.data(), n, &policy.expected_costs);
+        const int64_t m = fetch(xy.data(), par.data(), leaf.data(), bel.data(), (uint64_t)n, &policy.expected_costs);
         if (m < 0) ctx_.check((int)m);
         for (size_t k = 0; k < n; ++k) {
             PolicyNode pn;

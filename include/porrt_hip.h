@@ -883,6 +883,46 @@ int      porrt_tamp_rrt_get_astar_info(const porrt_ctx *ctx, porrt_tamp_astar_in
 /* the search nodes of the last porrt_tamp_rrt_plan_astar in id order (also after PORRT_ERR_NO_PATH: the nodes made so far):
  * parents (-1 = root), targets (zone; -1 = root), ec, priority.  Returns their count; with cap below it nothing is written. */
 int64_t  porrt_tamp_astar_nodes(const porrt_ctx *ctx, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap);
+/* ---- many A* plans on one map in one call.  Plan p is the search of porrt_tamp_rrt_plan_astar from
+ * starts[p] with prior priors[p] and root stream seed seeds[p] (NULL: the context's sampler seed for every plan); its worker streams
+ * are splitmix64 of that seed and the zone prefix, the sampler box is the context's.  Map, zones and every numeric parameter are
+ * shared.  Needs "tamp_streams" 1: every plan of a batch is then, bit for bit, the plan porrt_tamp_rrt_plan_astar gives alone on a
+ * context whose sampler seed is seeds[p] -- policy, costs, zone order, every search node, and queries / waves / speculated at the
+ * same "tamp_wave".  The plans' searches run in rounds: every live search replays and selects its wave ("tamp_wave" per plan), and
+ * the selected edges of all plans, in plan then node then zone order, go through porrt_grow_batch in chunks of "tamp_pool" rows;
+ * their paths share one arena ("tamp_arena_states": its first capacity), and the chains of all plans that found a leaf are shortcut
+ * in one launch.
+ * Returns the number of plans that found a policy (0 is no error), or a negative code.  PORRT_ERR_NO_PATH is per plan (status,
+ * fail_* by the rule above; the nodes made so far stay readable; the other plans go on).  Everything else fails the call and names
+ * the plan in porrt_last_error where one is to blame: PORRT_ERR_INVALID before anything runs (a prior whose sum is off or with an
+ * entry not > 0, n_worlds != zones, n_plans outside 1..65536, NULL starts or priors, "tamp_streams" 0), PORRT_ERR_CAPACITY from the
+ * arena or a path slot, device errors, and whatever porrt_grow_batch answers.
+ * The call leaves the context's continuous stream, its discrete sampler and its goal-independent state alone.  It replaces the
+ * context's last single plan: porrt_tamp_rrt_policy then answers as after a failed plan and porrt_tamp_astar_nodes gives 0 nodes;
+ * porrt_tamp_rrt_get_info holds the call's totals (queries, waves = rounds of the driver, search_nodes, the seconds, pool) and
+ * porrt_tamp_rrt_get_astar_info the call's arena figures, children_s, chain_s and the sum of `speculated`.  The results live on
+ * the context until the next batch call or porrt_destroy. */
+typedef struct {
+    int32_t  status;                 /* PORRT_OK or PORRT_ERR_NO_PATH */
+    int32_t  fail_zone, fail_query;  /* as porrt_tamp_info; -1 when status is PORRT_OK */
+    int64_t  fail_node;
+    double   search_cost, expected_cost;
+    uint64_t search_nodes, queries, waves, speculated;   /* this plan's own: those of the single plan at the same tamp_wave */
+    uint64_t policy_nodes;           /* 0 for a failed plan */
+    uint32_t n_order, pad;
+    uint32_t zone_order[64];
+} porrt_tamp_batch_plan;
+int64_t  porrt_tamp_rrt_plan_astar_batch(porrt_ctx *ctx, uint32_t n_plans, const double *starts /* n x 2 */,
+                                         const double *priors /* n x n_worlds */, const uint64_t *seeds /* n, or NULL */, uint32_t n_worlds,
+                                         double max_step, double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius,
+                                         uint32_t batch_K);
+int      porrt_tamp_batch_get_plan(const porrt_ctx *ctx, uint32_t plan, porrt_tamp_batch_plan *out);
+/* plan `plan` of the last batch: its policy as porrt_tamp_rrt_policy gives it (PORRT_ERR_INVALID for a failed plan), its search
+ * nodes as porrt_tamp_astar_nodes gives them (also of a failed plan) */
+int64_t  porrt_tamp_batch_policy(const porrt_ctx *ctx, uint32_t plan, double *xy, int64_t *parents, uint8_t *is_leaf, double *beliefs,
+                                 uint64_t cap, double *expected_cost);
+int64_t  porrt_tamp_batch_astar_nodes(const porrt_ctx *ctx, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, double *priority,
+                                      uint64_t cap);
 /* porrt_tamp_shortcut_paths through the shortcut's device-resident input form: the paths are first put into the A* search's arena
  * and reach the shortcut's staging planes by k_astar_chain, as the winning chain of a plan does.  Same result, bit for bit. */
 int      porrt_tamp_shortcut_paths_resident(porrt_ctx *ctx, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out);

@@ -4683,6 +4683,64 @@ int64_t porrt_tamp_astar_nodes(const porrt_ctx *cc, int64_t *parents, int32_t *t
     return (int64_t)n;
 }
 
+// ---- many A* plans on one map in one call (tamp_plan_astar_batch, porrt_tamp_astar.hpp)
+int64_t porrt_tamp_rrt_plan_astar_batch(porrt_ctx *c, uint32_t n_plans, const double *starts, const double *priors, const uint64_t *seeds,
+                                        uint32_t n_worlds, double max_step, double search_radius, uint64_t n_iter_min, uint64_t n_iter_max,
+                                        double goal_radius, uint32_t batch_K) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() {
+        const int64_t n = tamp_plan_astar_batch(c, n_plans, starts, priors, seeds, n_worlds, max_step, search_radius, n_iter_min, n_iter_max,
+                                                goal_radius, batch_K);
+        out = n;
+        return n < 0 ? (int)n : (int)PORRT_OK;
+    });
+    return r < 0 ? r : out;
+}
+
+static const AstarBatchPlan *astar_batch_plan(const porrt_ctx *cc, uint32_t plan, uint32_t *nw = nullptr) {
+    if (!cc || !cc->tamp || !((const TampState *)cc->tamp.get())->astar) return nullptr;
+    const AstarState &A = *(const AstarState *)((const TampState *)cc->tamp.get())->astar.get();
+    if (plan >= A.batch.size()) return nullptr;
+    if (nw) *nw = A.batch_nw;
+    return &A.batch[plan];
+}
+
+int porrt_tamp_batch_get_plan(const porrt_ctx *cc, uint32_t plan, porrt_tamp_batch_plan *out) {
+    const AstarBatchPlan *B = astar_batch_plan(cc, plan);
+    if (!B || !out) return PORRT_ERR_INVALID;
+    *out = B->rec;
+    return PORRT_OK;
+}
+
+int64_t porrt_tamp_batch_policy(const porrt_ctx *cc, uint32_t plan, double *xy, int64_t *parents, uint8_t *is_leaf, double *beliefs, uint64_t cap,
+                                double *expected_cost) {
+    uint32_t nw = 0;
+    const AstarBatchPlan *B = astar_batch_plan(cc, plan, &nw);
+    if (!B) return PORRT_ERR_INVALID;
+    if (B->rec.status != PORRT_OK) { const_cast<porrt_ctx *>(cc)->set_err("tamp astar batch: plan " + std::to_string(plan) + " found no policy"); return PORRT_ERR_INVALID; }
+    const uint64_t n = B->parents.size();
+    if (expected_cost) *expected_cost = B->rec.expected_cost;
+    if (cap < n) return (int64_t)n;
+    if (xy) memcpy(xy, B->xy.data(), 2 * n * sizeof(double));
+    if (parents) memcpy(parents, B->parents.data(), n * sizeof(int64_t));
+    if (is_leaf) memcpy(is_leaf, B->leaf.data(), n);
+    if (beliefs) memcpy(beliefs, B->beliefs.data(), n * nw * sizeof(double));
+    return (int64_t)n;
+}
+
+int64_t porrt_tamp_batch_astar_nodes(const porrt_ctx *cc, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap) {
+    const AstarBatchPlan *B = astar_batch_plan(cc, plan);
+    if (!B) return PORRT_ERR_INVALID;
+    const uint64_t n = B->node_parents.size();
+    if (cap < n) return (int64_t)n;
+    if (parents) memcpy(parents, B->node_parents.data(), n * sizeof(int64_t));
+    if (targets) memcpy(targets, B->node_targets.data(), n * sizeof(int32_t));
+    if (ec) memcpy(ec, B->node_ec.data(), n * sizeof(double));
+    if (priority) memcpy(priority, B->node_priority.data(), n * sizeof(double));
+    return (int64_t)n;
+}
+
 int porrt_tamp_shortcut_paths_resident(porrt_ctx *c, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out) {
     if (!c || !offsets || !out || (!xy && offsets[n_paths])) return PORRT_ERR_INVALID;
     if (!c->has_grid) { c->set_err("tamp_shortcut: the shortcut checks segments on the context's grid (porrt_set_grid)"); return PORRT_ERR_INVALID; }

@@ -28,17 +28,15 @@
 #include <utility>
 #include <vector>
 
+#include "porrt_astar_search.hpp"
+
 namespace {
 
 constexpr uint32_t kTampPathSlot = 1024;      // states of one query's best path (a longer one is PORRT_ERR_CAPACITY, never cut short)
 constexpr uint32_t kTampShortcutIterations = 100;   // map_shelves_tamp_rrt.rs:581
 
-static inline uint64_t tamp_splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// the stream and belief arithmetic of a search edge (splitmix64, edge_seed, normalize, transition_probability, child_belief) is that
+// of the host-only porrt_astar_search.hpp: one statement of each for the three searches
 
 struct TampNode {
     int32_t target = -1;
@@ -308,18 +306,6 @@ static std::vector<uint32_t> tamp_shuffled(const std::vector<uint32_t> &v, Pcg64
     return out;
 }
 
-static void tamp_normalize(std::vector<double> &b) {
-    double s = 0.0;
-    for (double p : b) s = s + p;
-    for (double &p : b) p = p / s;
-}
-
-static double tamp_transition_probability(const double *parent, const double *child, uint32_t nw) {     // common.rs:188-190
-    double s = 0.0;
-    for (uint32_t w = 0; w < nw; ++w) s = s + (child[w] > 0.0 ? parent[w] : 0.0);
-    return s;
-}
-
 // Policy::compute_expected_costs_to_goals (common.rs:131-154) from node 0: sum over the children in order of
 // p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
 // Children in ascending id order.  Evaluated with an explicit stack (a piece can be long).
@@ -357,60 +343,76 @@ static inline double tamp_expected_cost(const std::vector<int64_t> &parent, cons
     }
 }
 
-// build_policy (:619-663) on the chain root .. leaf.  With `src` the nodes' paths give only their lengths: the states are on the
-// device (one entry of src->paths per path, in the order they are laid out here).
-static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id, TampChainSource *src = nullptr) {
+// The policy arrays of one plan, wherever they are kept: the single plans keep them in TampState, a batch per plan.
+struct TampPolicyArrays {
+    std::vector<double> &xy, &beliefs;
+    std::vector<int64_t> &parents;
+    std::vector<uint8_t> &leaf;
+};
+
+// the assembly half of build_policy (:619-663) for one chain of `depth` search nodes after the shortcut: node i's observation path
+// is the states [off[2i], off[2i + 1]) of xy, its pickup path [off[2i + 1], off[2i + 2]); target[i] and belief[i] are the node's.
+// Returns the policy's expected cost.
+static double tamp_assemble_policy(uint32_t nw, size_t depth, const int32_t *target, const double *const *belief, const std::vector<double> &xy,
+                                   const uint64_t *off, TampPolicyArrays P) {
+    P.xy.clear(); P.parents.clear(); P.leaf.clear(); P.beliefs.clear();
+    auto add = [&](double x, double y, const double *b, bool is_leaf) {
+        P.xy.push_back(x); P.xy.push_back(y);
+        P.parents.push_back(-1);
+        P.leaf.push_back(is_leaf ? 1 : 0);
+        P.beliefs.insert(P.beliefs.end(), b, b + nw);
+        return (int64_t)P.parents.size() - 1;
+    };
+    int64_t last_obs = 0;
+    for (size_t i = 0; i < depth; ++i) {
+        int64_t prev = last_obs;
+        for (uint64_t k = off[2 * i]; k < off[2 * i + 1]; ++k) {
+            const int64_t id = add(xy[2 * k], xy[2 * k + 1], belief[i], false);
+            if (id != prev) P.parents[(size_t)id] = prev;
+            prev = id;
+        }
+        last_obs = prev;
+        const uint64_t p0 = off[2 * i + 1], p1 = off[2 * i + 2];
+        std::vector<double> b(belief[i], belief[i] + nw);
+        if (p1 > p0) {
+            for (uint32_t w = 0; w < nw; ++w) if ((int32_t)w != target[i]) b[w] = 0.0;
+            porrt_astar::normalize(b);
+        }
+        for (uint64_t k = p0; k < p1; ++k) {
+            const int64_t id = add(xy[2 * k], xy[2 * k + 1], b.data(), k + 1 == p1);
+            if (id != prev) P.parents[(size_t)id] = prev;
+            prev = id;
+        }
+    }
+    return tamp_expected_cost(P.parents, P.xy, [&](uint32_t a, uint32_t b2) {
+        return porrt_astar::transition_probability(P.beliefs.data() + (size_t)a * nw, P.beliefs.data() + (size_t)b2 * nw, nw);
+    });
+}
+
+// build_policy (:619-663) on the chain root .. leaf: the shortcut of its paths on the device, then the assembly.
+static int tamp_build_policy(porrt_ctx *c, TampState &T, const std::vector<TampNode> &nodes, int64_t leaf_id) {
     std::vector<int64_t> chain;
     for (int64_t k = leaf_id; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
     std::reverse(chain.begin(), chain.end());
     std::vector<double> xy;
     std::vector<uint64_t> off{0};
+    std::vector<int32_t> target;
+    std::vector<const double *> belief;
     for (int64_t k : chain) {
         const TampNode &sn = nodes[(size_t)k];
         xy.insert(xy.end(), sn.path_obs.begin(), sn.path_obs.end());
         off.push_back(xy.size() / 2);
         xy.insert(xy.end(), sn.path_pick.begin(), sn.path_pick.end());
         off.push_back(xy.size() / 2);
+        target.push_back(sn.target);
+        belief.push_back(sn.belief.data());
     }
     const double t0 = now_s();
     double dev_s = 0.0;
-    const int r = tamp_shortcut_device(c, T, xy, off, &dev_s, src);
+    const int r = tamp_shortcut_device(c, T, xy, off, &dev_s);
     if (r < 0) return r;
     T.info.shortcut_s = now_s() - t0;
-    const uint32_t nw = T.nw;
-    T.xy.clear(); T.parents.clear(); T.leaf.clear(); T.beliefs.clear();
-    auto add = [&](double x, double y, const std::vector<double> &b, bool is_leaf) {
-        T.xy.push_back(x); T.xy.push_back(y);
-        T.parents.push_back(-1);
-        T.leaf.push_back(is_leaf ? 1 : 0);
-        T.beliefs.insert(T.beliefs.end(), b.begin(), b.end());
-        return (int64_t)T.parents.size() - 1;
-    };
-    int64_t last_obs = 0;
-    for (size_t i = 0; i < chain.size(); ++i) {
-        const TampNode &sn = nodes[(size_t)chain[i]];
-        int64_t prev = last_obs;
-        for (uint64_t k = off[2 * i]; k < off[2 * i + 1]; ++k) {
-            const int64_t id = add(xy[2 * k], xy[2 * k + 1], sn.belief, false);
-            if (id != prev) T.parents[(size_t)id] = prev;
-            prev = id;
-        }
-        last_obs = prev;
-        const uint64_t p0 = off[2 * i + 1], p1 = off[2 * i + 2];
-        std::vector<double> b(sn.belief);
-        if (p1 > p0) {
-            for (uint32_t w = 0; w < nw; ++w) if ((int32_t)w != sn.target) b[w] = 0.0;
-            tamp_normalize(b);
-        }
-        for (uint64_t k = p0; k < p1; ++k) {
-            const int64_t id = add(xy[2 * k], xy[2 * k + 1], b, k + 1 == p1);
-            if (id != prev) T.parents[(size_t)id] = prev;
-            prev = id;
-        }
-    }
-    T.info.expected_cost = tamp_expected_cost(T.parents, T.xy, [&](uint32_t a, uint32_t b2) {
-        return tamp_transition_probability(T.beliefs.data() + (size_t)a * nw, T.beliefs.data() + (size_t)b2 * nw, nw);
-    });
+    T.info.expected_cost = tamp_assemble_policy(T.nw, chain.size(), target.data(), belief.data(), xy, off.data(), {T.xy, T.beliefs, T.parents, T.leaf});
     return PORRT_OK;
 }
 
@@ -422,18 +424,6 @@ static int tamp_fail(porrt_ctx *c, TampState &T, int64_t node, int32_t zone, int
 }
 
 // ---- what the three searches (this file, porrt_tamp_viewpoints.hpp, porrt_tamp_astar.hpp) share: DESIGN.md section 17
-
-// stream seed of the edge into the child of zone t of a node whose own seed is h
-static inline uint64_t tamp_edge_seed(uint64_t h, uint32_t t) { return tamp_splitmix64(h ^ ((uint64_t)t + 1)); }
-
-// a child's belief and reaching probability: the parent's belief with the parent's target zeroed, normalised
-static std::pair<std::vector<double>, double> tamp_child_belief(const double *belief, int32_t target, double rp, uint32_t nw) {
-    std::vector<double> b(belief, belief + nw);
-    if (target >= 0) b[(size_t)target] = 0.0;
-    tamp_normalize(b);
-    const double q = tamp_transition_probability(belief, b.data(), nw);
-    return {std::move(b), rp * q};
-}
 
 // a fresh shuffle of `remaining` without zone t: one per child, from the discrete sampler (the branch-and-bound searches only)
 static std::vector<uint32_t> tamp_remaining_without(const std::vector<uint32_t> &remaining, uint32_t t, Pcg64 &rng) {
@@ -536,20 +526,25 @@ struct TampFrame {
     }
 
     // The end of a plan that found `leaf`: search cost and zone order of the chain root .. leaf, the lead's stream set back, the
-    // policy (with src the paths are on the device), the times.  extra_s: time the search accounts for outside search_s.
-    int64_t finish(const std::vector<TampNode> &nodes, int64_t leaf, TampChainSource *src = nullptr, double extra_s = 0.0) {
+    // policy, the times.  extra_s: time the search accounts for outside search_s.
+    int64_t finish(const std::vector<TampNode> &nodes, int64_t leaf, double extra_s = 0.0) {
         porrt_tamp_info &I = T->info;
         I.search_cost = nodes[(size_t)leaf].ec;
         I.n_order = 0;
         for (int64_t k : tamp_chain(nodes, leaf)) if (nodes[(size_t)k].parent >= 0) I.zone_order[I.n_order++] = (uint32_t)nodes[(size_t)k].target;
         if (restore) { c->crng = crng0; restore = false; }
-        const int r = tamp_build_policy(c, *T, nodes, leaf, src);
+        const int r = tamp_build_policy(c, *T, nodes, leaf);
         if (r < 0) return r;
         T->valid = true;
+        close(extra_s);
+        return (int64_t)T->parents.size();
+    }
+    // the pool and the seconds of a call that ends
+    void close(double extra_s = 0.0) {
+        porrt_tamp_info &I = T->info;
         I.pool = (uint32_t)T->pool.size();
         I.total_s = now_s() - t_start;
         I.search_s = I.total_s - I.grow_s - I.path_s - I.shortcut_s - I.pool_s - I.goals_s - extra_s;
-        return (int64_t)T->parents.size();
     }
 };
 
@@ -621,10 +616,10 @@ static int64_t tamp_plan(porrt_ctx *c, const double start[2], const double *beli
                 TampNode v;
                 v.remaining = tamp_remaining_without(rem_u, t, c->drng);
                 const TampNode &u = nodes[(size_t)uid];
-                std::tie(v.belief, v.rp) = tamp_child_belief(u.belief.data(), u.target, u.rp, nw);
+                std::tie(v.belief, v.rp) = porrt_astar::child_belief(u.belief.data(), u.target, u.rp, nw);
                 v.target = (int32_t)t;
                 v.parent = uid;
-                v.h = tamp_edge_seed(u.h, t);
+                v.h = porrt_astar::edge_seed(u.h, t);
                 kids.push_back((int64_t)nodes.size());
                 edges.push_back((int64_t)nodes.size());
                 nodes.push_back(std::move(v));

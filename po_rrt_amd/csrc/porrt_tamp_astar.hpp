@@ -33,41 +33,43 @@
 // observation state, costs, arena offsets), the only thing the search fetches besides the observation queries' own records (the
 // pickup batch starts from the observation end states, which porrt_grow_batch takes from the host); k_astar_chain copies the
 // 2 x depth paths of the winning chain into the shortcut's staging planes, where k_tamp_shortcut runs on them unchanged.
+//
+// What is one plan's own -- tables, queue, replay, selection, the failure rule -- is porrt_astar::Search, and the rounds are
+// porrt_astar::run (porrt_astar_search.hpp, host only).  This file is the device side of those rounds (AstarRun) and the two
+// callers: tamp_plan_astar, the driver with one plan, and tamp_plan_astar_batch, the same driver over many
+// plans on one map whose rows share the batches, the arena, one k_astar_children per chunk and one k_astar_chain /
+// k_tamp_shortcut at the end.  With per-edge streams a plan of a batch is, bit for bit, the plan it is alone.
 #pragma once
 
-#include "porrt_astar_queue.hpp"
+#include "porrt_astar_search.hpp"
 
 namespace {
 
-struct AstarNode {
-    int32_t target = -1;
-    int64_t parent = -1;
-    unsigned long long remaining = 0;          // bit z: zone z still to visit (always walked in ascending order)
-    double ox = 0, oy = 0;                     // observation_state
-    double rp = 1.0, ec = 0.0, priority = 0.0;
-    uint32_t belief = 0;                       // row of the plan's belief table
-    uint64_t h = 0;                            // stream seed of the edge into this node (tamp_streams = 1)
-    uint32_t obs_off = 0, obs_len = 0, pick_off = 0, pick_len = 0;   // its two paths in the arena
-    int64_t kids = -1;                         // its expansion, once computed
-    bool popped = false;
-};
+using AstarSearch = porrt_astar::Search;
+using AstarEdge = porrt_astar::Edge;
+using AstarChildRecord = porrt_astar::ChildRecord;
 
-struct AstarExpansion {                        // the children of one node, before they have ids
-    uint32_t belief = 0;
-    double rp = 0.0;
-    std::vector<uint32_t> zone;
-    std::vector<AstarChildOut> rec;
+struct AstarBatchPlan {                        // one plan of the last porrt_tamp_rrt_plan_astar_batch
+    porrt_tamp_batch_plan rec;
+    std::vector<double> xy, beliefs;           // its policy (empty for a failed plan)
+    std::vector<int64_t> parents;
+    std::vector<uint8_t> leaf;
+    std::vector<int64_t> node_parents;         // its search nodes, in id order
+    std::vector<int32_t> node_targets;
+    std::vector<double> node_ec, node_priority;
 };
 
 struct AstarState {
-    double2 *arena = nullptr;                  // path arena of the running plan; kept across plans, its cursor is not
+    double2 *arena = nullptr;                  // path arena of the running call; kept across calls, its cursor is not
     size_t arena_cap = 0;                      // states
     size_t cursor_ub = 0;                      // no gather has written at or beyond this state
     hipEvent_t ev = nullptr;
     porrt_tamp_astar_info info;
-    std::vector<int64_t> parents;              // the last plan's search nodes, in id order
+    std::vector<int64_t> parents;              // the last single plan's search nodes, in id order
     std::vector<int32_t> targets;
     std::vector<double> ec, priority;
+    std::vector<AstarBatchPlan> batch;         // the last batch call's plans
+    uint32_t batch_nw = 0;
     AstarState() { memset(&info, 0, sizeof info); }
     ~AstarState() {
         if (arena) (void)hipFree(arena);
@@ -102,7 +104,7 @@ static int astar_arena_reserve(porrt_ctx *c, AstarState &A, size_t states) {
     return PORRT_OK;
 }
 
-// tamp_best_paths of the rows ctxs[0 .. n) into the plan's arena through its running cursor, the records to d_meta[0 .. n) on the
+// tamp_best_paths of the rows ctxs[0 .. n) into the call's arena through its running cursor, the records to d_meta[0 .. n) on the
 // device: nothing is downloaded here
 static int astar_gather(porrt_ctx *c, TampState &T, AstarState &A, porrt_ctx *const *ctxs, uint32_t n, uint32_t *d_cur, BestPath *d_meta) {
     const double t0 = now_s();
@@ -113,102 +115,68 @@ static int astar_gather(porrt_ctx *c, TampState &T, AstarState &A, porrt_ctx *co
     return PORRT_OK;
 }
 
-static int astar_bad_record(porrt_ctx *c, uint32_t status) {
-    c->set_err(status == kAstarSlot ? "tamp astar: a best path longer than its slot of " + std::to_string(kTampPathSlot) + " states"
-                                    : std::string("tamp astar: the best-cost scratch of a query overflowed"));
-    return PORRT_ERR_CAPACITY;
-}
-
-static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
-                               uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
-    TampFrame F;
-    int r = F.begin(c, start, belief, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K, [&](int stage) -> int {
-        if (stage == 0) {
-            if (nw > 64) { c->set_err("tamp astar: at most 64 zones"); return PORRT_ERR_INVALID; }
-            return PORRT_OK;
-        }
-        for (uint32_t w = 0; w < nw; ++w)
-            if (!(belief[w] > 0.0)) { c->set_err("tamp astar: every entry of the prior must be > 0 (below the last positive zone every priority would be NaN)"); return PORRT_ERR_INVALID; }
-        return PORRT_OK;
-    });
-    if (r < 0) return r;
-    TampState &T = *F.T;
-    AstarState &A = astar_state(T);
-    memset(&A.info, 0, sizeof A.info);
-    A.parents.clear(); A.targets.clear(); A.ec.clear(); A.priority.clear();
-    const uint32_t nz = nw;
-
-    HIPCHK_CTX(c, hipSetDevice(c->device));
-    if (!A.ev) HIPCHK_CTX(c, hipEventCreate(&A.ev));
-    hipStream_t st = c->stream;
-    A.cursor_ub = 0;
-    if ((r = astar_arena_reserve(c, A, std::max<size_t>(kTampPathSlot, c->opt_tamp_arena_states))) < 0) return r;
+// The device side of one call over the searches S: the arena and what the kernels read call-wide (begin), the records of a chunk
+// of edges of any of the searches (expand_chunk, and expand_sequential for the one plan on the lead's own stream), and the end of
+// every search that found its leaf (policies).  `named`: errors name the plan they came from (a batch).
+struct AstarRun {
+    porrt_ctx *c;
+    TampFrame &F;
+    TampState &T;
+    AstarState &A;
+    std::vector<AstarSearch> &S;
+    bool named;
+    uint32_t nw = 0;
+    hipStream_t st = nullptr;
     uint32_t *d_cur = nullptr;
     double2 *d_zpos = nullptr;
-    HIPCHK_CTX(c, T.scratch.get(kSlotAstarCursor, d_cur, 1));
-    HIPCHK_CTX(c, T.scratch.get(kSlotAstarZonePos, d_zpos, nz));
-    HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
-    {
-        std::vector<double2> zp(nz);
-        for (uint32_t z = 0; z < nz; ++z) zp[z] = make_double2(c->zone_pos[z][0], c->zone_pos[z][1]);
-        HIPCHK_CTX(c, hipMemcpyAsync(d_zpos, zp.data(), nz * sizeof(double2), hipMemcpyHostToDevice, st));
+
+    std::string of_plan(uint32_t p) const { return named ? " (plan " + std::to_string(p) + ")" : std::string(); }
+
+    int begin() {
+        nw = F.nw;
+        HIPCHK_CTX(c, hipSetDevice(c->device));
+        if (!A.ev) HIPCHK_CTX(c, hipEventCreate(&A.ev));
+        st = c->stream;
+        A.cursor_ub = 0;
+        const int r = astar_arena_reserve(c, A, std::max<size_t>(kTampPathSlot, c->opt_tamp_arena_states));
+        if (r < 0) return r;
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarCursor, d_cur, 1));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarZonePos, d_zpos, nw));
+        HIPCHK_CTX(c, hipMemsetAsync(d_cur, 0, sizeof(uint32_t), st));
+        std::vector<double2> zp(nw);
+        for (uint32_t z = 0; z < nw; ++z) zp[z] = make_double2(c->zone_pos[z][0], c->zone_pos[z][1]);
+        HIPCHK_CTX(c, hipMemcpyAsync(d_zpos, zp.data(), nw * sizeof(double2), hipMemcpyHostToDevice, st));
         HIPCHK_CTX(c, hipStreamSynchronize(st));
+        return PORRT_OK;
     }
 
-    std::vector<AstarNode> nodes(1);
-    std::vector<AstarExpansion> exps;
-    std::vector<double> beliefs(belief, belief + nw);         // row 0: the prior
-    {
-        AstarNode &root = nodes[0];
-        root.remaining = nz == 64 ? ~0ull : ((1ull << nz) - 1ull);
-        root.ox = start[0]; root.oy = start[1];
-        root.h = c->s_seed;
+    int bad_record(uint32_t status, uint32_t plan) {
+        c->set_err((status == kAstarSlot ? "tamp astar: a best path longer than its slot of " + std::to_string(kTampPathSlot) + " states"
+                                         : std::string("tamp astar: the best-cost scratch of a query overflowed")) + of_plan(plan));
+        return PORRT_ERR_CAPACITY;
     }
-    // the nodes as they stand go to the state whichever way the plan ends (porrt_tamp_astar_nodes)
-    struct Keep {
-        AstarState &A; TampState &T; const std::vector<AstarNode> &nodes;
-        ~Keep() {
-            for (const AstarNode &n : nodes) { A.parents.push_back(n.parent); A.targets.push_back(n.target); A.ec.push_back(n.ec); A.priority.push_back(n.priority); }
-            T.info.search_nodes = nodes.size();
-            A.info.arena_states = A.arena_cap;
-        }
-    } keep{A, T, nodes};
 
-    // the expansion of node uid gets its belief row and reaching probability; returns its index
-    auto open_expansion = [&](int64_t uid) {
-        const AstarNode &u = nodes[(size_t)uid];
-        AstarExpansion E;
-        std::vector<double> vb;
-        std::tie(vb, E.rp) = tamp_child_belief(beliefs.data() + (size_t)u.belief * nw, u.target, u.rp, nw);
-        E.belief = (uint32_t)(beliefs.size() / nw);
-        beliefs.insert(beliefs.end(), vb.begin(), vb.end());
-        for (uint32_t z = 0; z < nz; ++z) if ((u.remaining >> z) & 1ull) E.zone.push_back(z);
-        E.rec.resize(E.zone.size());
-        exps.push_back(std::move(E));
-        return (int64_t)exps.size() - 1;
-    };
-
-    struct Edge { int64_t u; int64_t e; uint32_t i; };        // child i of expansion e of node u
-    // the records of edges[e0 .. e0 + m): rows of the two BestPath arrays -> k_astar_children -> the expansions
-    auto children = [&](const std::vector<Edge> &edges, size_t e0, uint32_t m, const std::vector<uint32_t> &pick_row, const BestPath *d_obs,
-                        const BestPath *d_pick) -> int {
+    // the records of edges[e0 .. e0 + m): rows of the two BestPath arrays -> one k_astar_children launch -> out[0 .. m)
+    int children(const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, const std::vector<uint32_t> &pick_row, const BestPath *d_obs,
+                 const BestPath *d_pick, AstarChildRecord *out) {
         const double t0 = now_s();
         std::vector<AstarChildIn> in(m);
         std::vector<double> bl;
-        std::vector<int64_t> row_of;                           // expansion of each uploaded belief row
+        uint32_t rows = 0;                                     // belief rows uploaded: one per run of edges of one expansion
         for (uint32_t i = 0; i < m; ++i) {
-            const Edge &ed = edges[e0 + i];
-            const AstarNode &u = nodes[(size_t)ed.u];
-            const AstarExpansion &E = exps[(size_t)ed.e];
-            if (row_of.empty() || row_of.back() != ed.e) {
-                row_of.push_back(ed.e);
-                bl.insert(bl.end(), beliefs.begin() + (size_t)E.belief * nw, beliefs.begin() + (size_t)(E.belief + 1) * nw);
+            const AstarEdge &ed = edges[e0 + i];
+            const AstarSearch &s = S[ed.plan];
+            const porrt_astar::Node &u = s.nodes[(size_t)ed.u];
+            const porrt_astar::Expansion &E = s.exps[(size_t)ed.e];
+            if (i == 0 || edges[e0 + i - 1].plan != ed.plan || edges[e0 + i - 1].e != ed.e) {
+                bl.insert(bl.end(), s.belief_row(E.belief), s.belief_row(E.belief) + nw);
+                ++rows;
             }
             AstarChildIn &a = in[i];
             a.parent_ec = u.ec; a.rp = E.rp;
             a.remaining = u.remaining & ~(1ull << E.zone[ed.i]);
             a.obs_row = i; a.pick_row = pick_row[i];
-            a.belief_row = (uint32_t)row_of.size() - 1; a.target = E.zone[ed.i];
+            a.belief_row = rows - 1; a.target = E.zone[ed.i];
         }
         AstarChildIn *d_in = nullptr;
         double *d_bl = nullptr;
@@ -220,174 +188,281 @@ static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double
         HIPCHK_CTX(c, hipMemcpyAsync(d_bl, bl.data(), bl.size() * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_astar_children, dim3((m + 63u) / 64u), dim3(64), 0, st, d_in, m, d_obs, d_pick, d_bl, nw, d_zpos, d_cur, d_out);
         HIPCHK_CTX(c, hipGetLastError());
-        std::vector<AstarChildOut> out(m);
-        HIPCHK_CTX(c, hipMemcpyAsync(out.data(), d_out, m * sizeof(AstarChildOut), hipMemcpyDeviceToHost, st));
+        std::vector<AstarChildOut> got(m);
+        HIPCHK_CTX(c, hipMemcpyAsync(got.data(), d_out, m * sizeof(AstarChildOut), hipMemcpyDeviceToHost, st));
         HIPCHK_CTX(c, hipStreamSynchronize(st));
-        A.cursor_ub = out[0].cursor;                           // exact: nothing has been gathered since
-        A.info.arena_used = out[0].cursor;
+        A.cursor_ub = got[0].cursor;                           // exact: nothing has been gathered since
+        A.info.arena_used = got[0].cursor;
         for (uint32_t i = 0; i < m; ++i) {
-            if (out[i].status == kAstarSlot || out[i].status == kAstarScratch) return astar_bad_record(c, out[i].status);
-            exps[(size_t)edges[e0 + i].e].rec[edges[e0 + i].i] = out[i];
+            const AstarChildOut &o = got[i];
+            if (o.status == kAstarSlot || o.status == kAstarScratch) return bad_record(o.status, edges[e0 + i].plan);
+            AstarChildRecord &r = out[i];
+            r.ec = o.ec; r.priority = o.priority; r.ox = o.ox; r.oy = o.oy;
+            r.obs_off = o.obs_off; r.obs_len = o.obs_len; r.pick_off = o.pick_off; r.pick_len = o.pick_len;
+            r.status = o.status == kAstarOk ? porrt_astar::kChildOk : o.status == kAstarNoObs ? porrt_astar::kChildNoObs : porrt_astar::kChildNoPick;
         }
         A.info.children_s += now_s() - t0;
         return PORRT_OK;
-    };
-    // the observation records of m rows: the pickup queries start from their end states
-    auto fetch_obs = [&](const BestPath *d_obs, uint32_t m, std::vector<BestPath> &meta) -> int {
+    }
+
+    // the observation records of m rows (those of edges[e0 ..)): the pickup queries start from their end states
+    int fetch_obs(const BestPath *d_obs, uint32_t m, std::vector<BestPath> &meta, const std::vector<AstarEdge> &edges, size_t e0) {
         const double t0 = now_s();
         meta.resize(m);
         HIPCHK_CTX(c, hipMemcpyAsync(meta.data(), d_obs, m * sizeof(BestPath), hipMemcpyDeviceToHost, st));
         HIPCHK_CTX(c, hipStreamSynchronize(st));
         size_t end = 0;
-        for (const BestPath &b : meta) {
-            if (b.status >= 2u) return astar_bad_record(c, b.status == 3u ? (uint32_t)kAstarSlot : (uint32_t)kAstarScratch);
+        for (uint32_t i = 0; i < m; ++i) {
+            const BestPath &b = meta[i];
+            if (b.status >= 2u) return bad_record(b.status == 3u ? (uint32_t)kAstarSlot : (uint32_t)kAstarScratch, edges[e0 + i].plan);
             if (b.status == 0u) end = std::max<size_t>(end, (size_t)b.off + b.len);
         }
         if (end) A.cursor_ub = end;                            // exact: the cursor only grows, and these rows were the last to move it
         T.info.path_s += now_s() - t0;
         return PORRT_OK;
-    };
+    }
 
-    // tamp_streams = 0: node uid's children one after the other on the lead.  uid is the top of the queue and is popped next, so
-    // the first query without a path ends the plan.
-    auto expand_sequential = [&](int64_t uid) -> int64_t {
-        const int64_t ei = open_expansion(uid);
-        nodes[(size_t)uid].kids = ei;
-        const uint32_t m = (uint32_t)exps[(size_t)ei].zone.size();
+    // tamp_streams = 0 (one plan, one node per round): the node's children one after the other on the lead.  The node is the top of
+    // the queue and is popped next, so the first query without a path ends the plan.
+    int expand_sequential(const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) {
+        const AstarSearch &s = S[edges[e0].plan];
+        const porrt_astar::Node &u = s.nodes[(size_t)edges[e0].u];
         BestPath *d_obs = nullptr, *d_pick = nullptr;
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
-        std::vector<Edge> edges;
         std::vector<uint32_t> pick_row(m);
         std::vector<BestPath> meta;
         porrt_ctx *one = c;
         for (uint32_t i = 0; i < m; ++i) {
-            const uint32_t t = exps[(size_t)ei].zone[i];
-            edges.push_back({uid, ei, i});
+            const uint32_t t = s.zone_of(edges[e0 + i]);
             pick_row[i] = i;
-            double st2[2] = {nodes[(size_t)uid].ox, nodes[(size_t)uid].oy};
+            double st2[2] = {u.ox, u.oy};
             for (int which = 0; which < 2; ++which) {
                 int rr = F.grow_lead(st2, t, which);
                 if (rr < 0) return rr;
                 if ((rr = astar_gather(c, T, A, &one, 1, d_cur, (which == 0 ? d_obs : d_pick) + i)) < 0) return rr;
-                if ((rr = fetch_obs((which == 0 ? d_obs : d_pick) + i, 1, meta)) < 0) return rr;
-                if (meta[0].status == 1u) return tamp_fail(c, T, (int64_t)nodes.size() + i, (int32_t)t, which);
+                if ((rr = fetch_obs((which == 0 ? d_obs : d_pick) + i, 1, meta, edges, e0 + i)) < 0) return rr;
+                if (meta[0].status == 1u) return tamp_fail(c, T, (int64_t)s.nodes.size() + i, (int32_t)t, which);
                 st2[0] = meta[0].end_x; st2[1] = meta[0].end_y;
             }
         }
-        return children(edges, 0, m, pick_row, d_obs, d_pick);
-    };
+        return children(edges, e0, m, pick_row, d_obs, d_pick, out);
+    }
 
-    // tamp_streams = 1: the nodes of `batch` together, chunked by the pool
-    auto expand_wave = [&](const std::vector<int64_t> &batch) -> int64_t {
-        std::vector<Edge> edges;
-        for (int64_t uid : batch) {
-            const int64_t ei = open_expansion(uid);
-            nodes[(size_t)uid].kids = ei;
-            for (uint32_t i = 0; i < exps[(size_t)ei].zone.size(); ++i) edges.push_back({uid, ei, i});
-        }
+    // tamp_streams = 1: the rows edges[e0 .. e0 + m), of whichever searches, together: one observation batch, one gather, one record
+    // download, one pickup batch on the rows that saw their zone, one gather, one k_astar_children
+    int expand_chunk(const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) {
+        int rr = tamp_ensure_pool(c, T, m);
+        if (rr < 0) return rr;
+        BestPath *d_obs = nullptr, *d_pick = nullptr;
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
+        HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
+        auto node_of = [&](size_t e) -> const porrt_astar::Node & { return S[edges[e].plan].nodes[(size_t)edges[e].u]; };
+        auto zone_of = [&](size_t e) { return S[edges[e].plan].zone_of(edges[e]); };
+        auto grown = [&](int r) {
+            if (r < 0 && named) c->set_err("tamp astar batch: the growth of a chunk holding plans " + std::to_string(edges[e0].plan) + " .. " +
+                                           std::to_string(edges[e0 + m - 1].plan) + " failed: " + c->err);
+            return r;
+        };
+        std::vector<double> starts(2 * (size_t)m);
+        for (uint32_t i = 0; i < m; ++i) { starts[2 * i] = node_of(e0 + i).ox; starts[2 * i + 1] = node_of(e0 + i).oy; }
+        rr = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) {
+            return F.seed_and_goal(T.pool[i], porrt_astar::edge_seed(node_of(e0 + i).h, zone_of(e0 + i)), zone_of(e0 + i), 0);
+        });
+        if (rr < 0) return grown(rr);
+        if ((rr = astar_gather(c, T, A, T.pool.data(), m, d_cur, d_obs)) < 0) return rr;
         std::vector<BestPath> meta;
-        auto zone_of = [&](size_t e) { return exps[(size_t)edges[e].e].zone[edges[e].i]; };
-        for (size_t e0 = 0; e0 < edges.size(); e0 += F.pool_cap) {
-            const uint32_t m = (uint32_t)std::min<size_t>(F.pool_cap, edges.size() - e0);
-            int rr = tamp_ensure_pool(c, T, m);
-            if (rr < 0) return rr;
-            BestPath *d_obs = nullptr, *d_pick = nullptr;
-            HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
-            HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
-            std::vector<double> starts(2 * (size_t)m);
-            for (uint32_t i = 0; i < m; ++i) { starts[2 * i] = nodes[(size_t)edges[e0 + i].u].ox; starts[2 * i + 1] = nodes[(size_t)edges[e0 + i].u].oy; }
-            rr = F.grow_rows(T.pool.data(), m, starts.data(), [&](uint32_t i) {
-                return F.seed_and_goal(T.pool[i], tamp_edge_seed(nodes[(size_t)edges[e0 + i].u].h, zone_of(e0 + i)), zone_of(e0 + i), 0);
-            });
-            if (rr < 0) return rr;
-            if ((rr = astar_gather(c, T, A, T.pool.data(), m, d_cur, d_obs)) < 0) return rr;
-            if ((rr = fetch_obs(d_obs, m, meta)) < 0) return rr;
-            // the pickup queries of the rows that saw their zone, on the same contexts: their streams run on
-            std::vector<porrt_ctx *> sub;
-            std::vector<uint32_t> pick_row(m, 0xFFFFFFFFu), sub_zone;
-            std::vector<double> pstarts;
-            for (uint32_t i = 0; i < m; ++i) {
-                if (meta[i].status != 0u) continue;
-                pick_row[i] = (uint32_t)sub.size();
-                sub.push_back(T.pool[i]);
-                sub_zone.push_back(zone_of(e0 + i));
-                pstarts.push_back(meta[i].end_x); pstarts.push_back(meta[i].end_y);
+        if ((rr = fetch_obs(d_obs, m, meta, edges, e0)) < 0) return rr;
+        // the pickup queries of the rows that saw their zone, on the same contexts: their streams run on
+        std::vector<porrt_ctx *> sub;
+        std::vector<uint32_t> pick_row(m, 0xFFFFFFFFu), sub_zone;
+        std::vector<double> pstarts;
+        for (uint32_t i = 0; i < m; ++i) {
+            if (meta[i].status != 0u) continue;
+            pick_row[i] = (uint32_t)sub.size();
+            sub.push_back(T.pool[i]);
+            sub_zone.push_back(zone_of(e0 + i));
+            pstarts.push_back(meta[i].end_x); pstarts.push_back(meta[i].end_y);
+        }
+        if (!sub.empty()) {
+            const uint32_t mp = (uint32_t)sub.size();
+            if ((rr = F.grow_rows(sub.data(), mp, pstarts.data(), [&](uint32_t j) { return F.set_goal(sub[j], sub_zone[j], 1); })) < 0) return grown(rr);
+            if ((rr = astar_gather(c, T, A, sub.data(), mp, d_cur, d_pick)) < 0) return rr;
+        }
+        return children(edges, e0, m, pick_row, d_obs, d_pick, out);
+    }
+
+    // The end of the searches `solved`, all of which found their leaf: one k_astar_chain and one k_tamp_shortcut launch over the
+    // 2 x depth paths of all their chains (the draws per path length are shared, as within one plan), then the assembly and the
+    // expected cost per plan on the host, into out[i] / expected[i] for solved[i].
+    int policies(const std::vector<uint32_t> &solved, const std::vector<TampPolicyArrays> &out, std::vector<double> &expected) {
+        std::vector<std::vector<int64_t>> chains;
+        std::vector<uint64_t> off{0};
+        TampChainSource src;
+        src.arena = A.arena; src.ev = A.ev;
+        for (uint32_t p : solved) {
+            chains.push_back(S[p].chain());
+            for (int64_t k : chains.back()) {
+                const porrt_astar::Node &n = S[p].nodes[(size_t)k];
+                off.push_back(off.back() + n.obs_len);
+                src.paths.push_back({n.obs_off, n.obs_len, 0u, 0u});
+                off.push_back(off.back() + n.pick_len);
+                src.paths.push_back({n.pick_off, n.pick_len, 0u, 0u});
             }
-            if (!sub.empty()) {
-                const uint32_t mp = (uint32_t)sub.size();
-                if ((rr = F.grow_rows(sub.data(), mp, pstarts.data(), [&](uint32_t j) { return F.set_goal(sub[j], sub_zone[j], 1); })) < 0) return rr;
-                if ((rr = astar_gather(c, T, A, sub.data(), mp, d_cur, d_pick)) < 0) return rr;
-            }
-            if ((rr = children(edges, e0, m, pick_row, d_obs, d_pick)) < 0) return rr;
+        }
+        std::vector<double> xy(2 * (size_t)off.back(), 0.0);      // only written: the paths are on the device
+        const double t0 = now_s();
+        const int r = tamp_shortcut_device(c, T, xy, off, nullptr, &src);
+        if (r < 0) return r;
+        T.info.shortcut_s = now_s() - t0;
+        A.info.chain_s = src.chain_s;
+        expected.assign(solved.size(), 0.0);
+        size_t at = 0;
+        for (size_t i = 0; i < solved.size(); ++i) {
+            const AstarSearch &s = S[solved[i]];
+            std::vector<int32_t> target;
+            std::vector<const double *> belief;
+            for (int64_t k : chains[i]) { target.push_back(s.nodes[(size_t)k].target); belief.push_back(s.belief_row(s.nodes[(size_t)k].belief)); }
+            expected[i] = tamp_assemble_policy(nw, chains[i].size(), target.data(), belief.data(), xy, off.data() + at, out[i]);
+            at += 2 * chains[i].size();
         }
         return PORRT_OK;
-    };
+    }
+};
 
-    porrt_astar::Queue queue;
-    queue.push(0.0, 0);
-    int64_t solution = -1;
-    while (solution < 0 && !queue.empty()) {
-        // the replay: pops while the top is a leaf or has its children
-        while (!queue.empty()) {
-            const int64_t uid = (int64_t)queue.top().id;
-            if (nodes[(size_t)uid].remaining && nodes[(size_t)uid].kids < 0) break;
-            queue.pop();
-            nodes[(size_t)uid].popped = true;
-            if (nodes[(size_t)uid].kids >= 0) {
-                const AstarExpansion &E = exps[(size_t)nodes[(size_t)uid].kids];
-                for (uint32_t i = 0; i < E.zone.size(); ++i) {
-                    const AstarChildOut &o = E.rec[i];
-                    if (o.status != kAstarOk) return tamp_fail(c, T, (int64_t)nodes.size(), (int32_t)E.zone[i], o.status == kAstarNoObs ? 0 : 1);
-                    AstarNode v;
-                    const AstarNode &u = nodes[(size_t)uid];
-                    v.target = (int32_t)E.zone[i]; v.parent = uid;
-                    v.remaining = u.remaining & ~(1ull << E.zone[i]);
-                    v.ox = o.ox; v.oy = o.oy; v.rp = E.rp; v.ec = o.ec; v.priority = o.priority;
-                    v.belief = E.belief;
-                    v.h = tamp_edge_seed(u.h, E.zone[i]);
-                    v.obs_off = o.obs_off; v.obs_len = o.obs_len; v.pick_off = o.pick_off; v.pick_len = o.pick_len;
-                    queue.push(v.priority, (uint64_t)nodes.size());
-                    nodes.push_back(v);
-                }
-            }
-            if (!nodes[(size_t)uid].remaining) { solution = uid; break; }
-        }
-        if (solution >= 0 || queue.empty()) break;
-        // the top has no children yet: it and the next best entries like it
-        std::vector<porrt_astar::QueueEntry> held;
-        std::vector<int64_t> batch;
-        while (!queue.empty() && batch.size() < F.wave) {
-            const porrt_astar::QueueEntry e = queue.pop();
-            held.push_back(e);
-            if (nodes[(size_t)e.id].remaining && nodes[(size_t)e.id].kids < 0) batch.push_back((int64_t)e.id);
-        }
-        for (const porrt_astar::QueueEntry &e : held) queue.push(e.priority, e.id);
-        ++T.info.waves;
-        const int64_t rr = F.streams == 0 ? expand_sequential(batch[0]) : expand_wave(batch);
-        if (rr < 0) return rr;
-    }
-    if (solution < 0) { c->set_err("No solution found!"); return PORRT_ERR_NO_PATH; }
-    for (const AstarNode &n : nodes) if (n.kids >= 0 && !n.popped) ++A.info.speculated;
-    std::vector<int64_t> chain;
-    for (int64_t k = solution; k >= 0; k = nodes[(size_t)k].parent) chain.push_back(k);
-    std::reverse(chain.begin(), chain.end());
-    // the chain as TampNodes for the frame's finish: the paths stay on the device, tamp_build_policy sees their lengths
-    std::vector<TampNode> cn(chain.size());
-    TampChainSource src;
-    src.arena = A.arena; src.ev = A.ev;
-    for (size_t i = 0; i < chain.size(); ++i) {
-        const AstarNode &n = nodes[(size_t)chain[i]];
-        cn[i].target = n.target; cn[i].parent = (int64_t)i - 1; cn[i].ec = n.ec;
-        cn[i].belief.assign(beliefs.begin() + (size_t)n.belief * nw, beliefs.begin() + (size_t)(n.belief + 1) * nw);
-        cn[i].path_obs.assign(2 * (size_t)n.obs_len, 0.0);
-        cn[i].path_pick.assign(2 * (size_t)n.pick_len, 0.0);
-        src.paths.push_back({n.obs_off, n.obs_len, 0u, 0u});
-        src.paths.push_back({n.pick_off, n.pick_len, 0u, 0u});
-    }
-    const int64_t n = F.finish(cn, (int64_t)cn.size() - 1, &src, A.info.children_s);
-    if (n >= 0) A.info.chain_s = src.chain_s;
+static uint32_t astar_zone_order(const AstarSearch &s, uint32_t *order) {
+    uint32_t n = 0;
+    for (int64_t k : s.chain()) if (s.nodes[(size_t)k].parent >= 0) order[n++] = (uint32_t)s.nodes[(size_t)k].target;
     return n;
+}
+
+static int astar_check_zones(porrt_ctx *c, uint32_t nw) {
+    if (nw > 64) { c->set_err("tamp astar: at most 64 zones"); return PORRT_ERR_INVALID; }
+    return PORRT_OK;
+}
+
+// the driver (porrt_astar::run) with one plan: the only one that may run on the lead's own stream
+static int64_t tamp_plan_astar(porrt_ctx *c, const double start[2], const double *belief, uint32_t nw, double max_step, double search_radius,
+                               uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
+    TampFrame F;
+    int r = F.begin(c, start, belief, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K, [&](int stage) -> int {
+        if (stage == 0) return astar_check_zones(c, nw);
+        for (uint32_t w = 0; w < nw; ++w)
+            if (!(belief[w] > 0.0)) { c->set_err("tamp astar: every entry of the prior must be > 0 (below the last positive zone every priority would be NaN)"); return PORRT_ERR_INVALID; }
+        return PORRT_OK;
+    });
+    if (r < 0) return r;
+    TampState &T = *F.T;
+    AstarState &A = astar_state(T);
+    memset(&A.info, 0, sizeof A.info);
+    A.parents.clear(); A.targets.clear(); A.ec.clear(); A.priority.clear();
+
+    std::vector<AstarSearch> S(1);
+    AstarSearch &s = S[0];
+    s.begin(start, belief, nw, c->s_seed);
+    // the nodes as they stand go to the state whichever way the plan ends (porrt_tamp_astar_nodes)
+    struct Keep {
+        AstarState &A; TampState &T; const AstarSearch &s;
+        ~Keep() {
+            for (const porrt_astar::Node &n : s.nodes) { A.parents.push_back(n.parent); A.targets.push_back(n.target); A.ec.push_back(n.ec); A.priority.push_back(n.priority); }
+            T.info.search_nodes = s.nodes.size();
+            A.info.arena_states = A.arena_cap;
+        }
+    } keep{A, T, s};
+    AstarRun R{c, F, T, A, S, false};
+    if ((r = R.begin()) < 0) return r;
+    if (F.streams == 0)
+        r = porrt_astar::run(S, 1u, ~(size_t)0, T.info.waves,
+                             [&](const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) { return R.expand_sequential(edges, e0, m, out); });
+    else
+        r = porrt_astar::run(S, F.wave, F.pool_cap, T.info.waves,
+                             [&](const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) { return R.expand_chunk(edges, e0, m, out); });
+    if (r < 0) return r;
+    if (s.state == AstarSearch::kFailed) return tamp_fail(c, T, s.fail_node, s.fail_zone, s.fail_query);
+    if (s.state != AstarSearch::kSolved) { c->set_err("No solution found!"); return PORRT_ERR_NO_PATH; }
+    A.info.speculated = s.speculated();
+    porrt_tamp_info &I = T.info;
+    I.search_cost = s.nodes[(size_t)s.solution].ec;
+    I.n_order = astar_zone_order(s, I.zone_order);
+    if (F.restore) { c->crng = F.crng0; F.restore = false; }
+    std::vector<double> expected;
+    if ((r = R.policies({0u}, {TampPolicyArrays{T.xy, T.beliefs, T.parents, T.leaf}}, expected)) < 0) return r;
+    I.expected_cost = expected[0];
+    T.valid = true;
+    F.close(A.info.children_s);
+    return (int64_t)T.parents.size();
+}
+
+// porrt_tamp_rrt_plan_astar_batch: the driver over n_plans searches that share map, zones and parameters.
+// Plan p is the search of tamp_plan_astar with root stream seed seeds[p]; its rows ride in the same porrt_grow_batch as the others'.
+static int64_t tamp_plan_astar_batch(porrt_ctx *c, uint32_t n_plans, const double *starts, const double *priors, const uint64_t *seeds, uint32_t nw,
+                                     double max_step, double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t K) {
+    if (n_plans == 0 || n_plans > 65536u) { c->set_err("tamp astar batch: n_plans must be in 1..65536"); return PORRT_ERR_INVALID; }
+    if (!starts || !priors) { c->set_err("tamp astar batch: starts and priors"); return PORRT_ERR_INVALID; }
+    if (!c->opt_tamp_streams) { c->set_err("tamp astar batch: needs per-edge streams (tamp_streams 1): one continuous stream cannot be shared by plans"); return PORRT_ERR_INVALID; }
+    TampFrame F;
+    int r = F.begin(c, starts, priors, nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, K, [&](int stage) -> int {
+        if (stage != 0) return PORRT_OK;
+        if (astar_check_zones(c, nw) < 0) return PORRT_ERR_INVALID;
+        for (uint32_t p = 0; p < n_plans; ++p) {                // every plan's prior, before anything runs
+            const double *b = priors + (size_t)p * nw;
+            double sum = 0.0;
+            for (uint32_t w = 0; w < nw; ++w) sum = sum + b[w];
+            if (!(std::fabs(sum - 1.0) < 0.001)) { c->set_err("tamp astar batch: plan " + std::to_string(p) + ": the prior does not sum to 1 (check_belief_state, common.rs:390)"); return PORRT_ERR_INVALID; }
+            for (uint32_t w = 0; w < nw; ++w)
+                if (!(b[w] > 0.0)) { c->set_err("tamp astar batch: plan " + std::to_string(p) + ": every entry of the prior must be > 0"); return PORRT_ERR_INVALID; }
+        }
+        return PORRT_OK;
+    });
+    if (r < 0) return r;
+    TampState &T = *F.T;
+    AstarState &A = astar_state(T);
+    memset(&A.info, 0, sizeof A.info);
+    A.parents.clear(); A.targets.clear(); A.ec.clear(); A.priority.clear();      // the last single plan is replaced
+    A.batch.clear();
+    A.batch_nw = nw;
+
+    std::vector<AstarSearch> S(n_plans);
+    for (uint32_t p = 0; p < n_plans; ++p) S[p].begin(starts + 2 * (size_t)p, priors + (size_t)p * nw, nw, seeds ? seeds[p] : c->s_seed);
+    AstarRun R{c, F, T, A, S, true};
+    if ((r = R.begin()) < 0) return r;
+    r = porrt_astar::run(S, F.wave, F.pool_cap, T.info.waves,
+                         [&](const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) { return R.expand_chunk(edges, e0, m, out); });
+    A.info.arena_states = A.arena_cap;
+    for (const AstarSearch &s : S) T.info.search_nodes += s.nodes.size();
+    if (r < 0) return r;
+
+    std::vector<AstarBatchPlan> plans(n_plans);
+    std::vector<uint32_t> solved;
+    std::vector<TampPolicyArrays> arrays;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const AstarSearch &s = S[p];
+        AstarBatchPlan &B = plans[p];
+        porrt_tamp_batch_plan &rec = B.rec;
+        memset(&rec, 0, sizeof rec);
+        rec.status = s.state == AstarSearch::kSolved ? PORRT_OK : PORRT_ERR_NO_PATH;
+        rec.fail_node = s.fail_node; rec.fail_zone = s.fail_zone; rec.fail_query = s.fail_query;
+        rec.search_nodes = s.nodes.size(); rec.queries = s.queries; rec.waves = s.waves;
+        for (const porrt_astar::Node &n : s.nodes) { B.node_parents.push_back(n.parent); B.node_targets.push_back(n.target); B.node_ec.push_back(n.ec); B.node_priority.push_back(n.priority); }
+        if (s.state != AstarSearch::kSolved) continue;
+        rec.speculated = s.speculated();
+        A.info.speculated += rec.speculated;
+        rec.search_cost = s.nodes[(size_t)s.solution].ec;
+        rec.n_order = astar_zone_order(s, rec.zone_order);
+        solved.push_back(p);
+        arrays.push_back(TampPolicyArrays{B.xy, B.beliefs, B.parents, B.leaf});
+    }
+    if (!solved.empty()) {
+        std::vector<double> expected;
+        if ((r = R.policies(solved, arrays, expected)) < 0) return r;
+        for (size_t i = 0; i < solved.size(); ++i) {
+            plans[solved[i]].rec.expected_cost = expected[i];
+            plans[solved[i]].rec.policy_nodes = plans[solved[i]].parents.size();
+        }
+    }
+    A.batch = std::move(plans);
+    F.close(A.info.children_s);
+    return (int64_t)solved.size();
 }
 
 // the shortcut's device-resident input form on explicit paths: they are put into the arena as a plan's gathers would leave them

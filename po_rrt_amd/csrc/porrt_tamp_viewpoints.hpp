@@ -85,7 +85,7 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
         TampNode v;
         v.target = (int32_t)e.t; v.parent = e.u;
         v.remaining = e.remaining; v.belief = e.belief; v.rp = e.rp;
-        v.h = tamp_splitmix64(e.ho ^ (((uint64_t)rank + 1) << 32));
+        v.h = porrt_astar::splitmix64(e.ho ^ (((uint64_t)rank + 1) << 32));
         v.path_obs.assign(S.xy.begin() + 2 * S.off[s], S.xy.begin() + 2 * (S.off[s] + S.lens[s]));
         v.obs_cost = S.costs[s];
         v.ox = v.path_obs[v.path_obs.size() - 2]; v.oy = v.path_obs.back();
@@ -110,8 +110,8 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
                 VpEdge e;
                 e.u = uid; e.t = t;
                 e.remaining = tamp_remaining_without(u.remaining, t, c->drng);
-                std::tie(e.belief, e.rp) = tamp_child_belief(u.belief.data(), u.target, u.rp, nw);
-                e.ho = tamp_edge_seed(u.h, t);
+                std::tie(e.belief, e.rp) = porrt_astar::child_belief(u.belief.data(), u.target, u.rp, nw);
+                e.ho = porrt_astar::edge_seed(u.h, t);
                 edges.push_back(std::move(e));
             }
             made.push_back({uid, {e0, edges.size()}});
@@ -194,7 +194,7 @@ static int64_t tamp_plan_viewpoints(porrt_ctx *c, const double start[2], const d
     }
     T.vinfo.n_ranks = 0;
     for (int64_t k : tamp_chain(nodes, B.best_leaf)) if (k > 0) T.vinfo.ranks[T.vinfo.n_ranks++] = rank_of[(size_t)k];
-    return F.finish(nodes, B.best_leaf, nullptr, T.vinfo.solutions_s);
+    return F.finish(nodes, B.best_leaf, T.vinfo.solutions_s);
 }
 
 } // namespace

@@ -47,6 +47,7 @@ SYMBOLS = [
     "porrt_tamp_rrt_plan", "porrt_tamp_rrt_policy", "porrt_tamp_rrt_get_info", "porrt_tamp_shortcut_paths", "porrt_best_paths",
     "porrt_solutions", "porrt_tamp_rrt_plan_viewpoints", "porrt_tamp_rrt_get_viewpoints_info",
     "porrt_tamp_rrt_plan_astar", "porrt_tamp_rrt_get_astar_info", "porrt_tamp_astar_nodes", "porrt_tamp_shortcut_paths_resident",
+    "porrt_tamp_rrt_plan_astar_batch", "porrt_tamp_batch_get_plan", "porrt_tamp_batch_policy", "porrt_tamp_batch_astar_nodes",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
@@ -78,6 +79,14 @@ class TampAstarInfo(C.Structure):
     """porrt_tamp_astar_info"""
     _fields_ = [("speculated", C.c_uint64), ("arena_states", C.c_uint64), ("arena_used", C.c_uint64), ("arena_grown", C.c_uint64),
                 ("children_s", C.c_double), ("chain_s", C.c_double)]
+
+
+class TampBatchPlan(C.Structure):
+    """porrt_tamp_batch_plan"""
+    _fields_ = [("status", C.c_int32), ("fail_zone", C.c_int32), ("fail_query", C.c_int32), ("fail_node", C.c_int64),
+                ("search_cost", C.c_double), ("expected_cost", C.c_double), ("search_nodes", C.c_uint64), ("queries", C.c_uint64),
+                ("waves", C.c_uint64), ("speculated", C.c_uint64), ("policy_nodes", C.c_uint64), ("n_order", C.c_uint32),
+                ("pad", C.c_uint32), ("zone_order", C.c_uint32 * 64)]
 
 
 class TampViewpointsInfo(C.Structure):
@@ -279,6 +288,11 @@ def load_library():
     sig("porrt_tamp_rrt_get_astar_info", C.c_int, vp, C.POINTER(TampAstarInfo))
     sig("porrt_tamp_astar_nodes", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_tamp_shortcut_paths_resident", C.c_int, vp, C.c_void_p, _u64p, C.c_uint64, C.c_void_p)
+    sig("porrt_tamp_rrt_plan_astar_batch", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double,
+        C.c_uint64, C.c_uint64, C.c_double, C.c_uint32)
+    sig("porrt_tamp_batch_get_plan", C.c_int, vp, C.c_uint32, C.POINTER(TampBatchPlan))
+    sig("porrt_tamp_batch_policy", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
+    sig("porrt_tamp_batch_astar_nodes", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_solutions", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
         C.c_void_p, C.c_uint64)
     sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
@@ -499,6 +513,50 @@ class Engine:
         par, tgt = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
         ec, pr = np.zeros(n), np.zeros(n)
         self._chk(self._l.porrt_tamp_astar_nodes(self._c, par.ctypes.data, tgt.ctypes.data, ec.ctypes.data, pr.ctypes.data, n))
+        return dict(parents=par, targets=tgt, ec=ec, priority=pr)
+
+    def plan_tamp_rrt_astar_batch(self, starts, priors, seeds=None, max_step=0.1, search_radius=2.0, n_iter_min=2500, n_iter_max=10000,
+                                  goal_radius=0.05, batch_K=128):
+        """porrt_tamp_rrt_plan_astar_batch: many A* plans on this engine's map in one call, plan p from starts[p] with prior
+        priors[p] and root stream seed seeds[p] (None: the engine's sampler seed for every plan).  Each plan is, bit for bit, what
+        plan_tamp_rrt_astar gives alone on an engine whose sampler seed is seeds[p].  Returns one dict per plan with the keys of
+        plan_tamp_rrt_astar's dict plus `status` (0, or -10 for a plan that found no path: it has no policy arrays, and fail_* say
+        where it failed).  search_cost, expected_cost, search_nodes, queries, waves, speculated, zone_order and fail_* are the
+        plan's own; the seconds, streams, wave, pool and the arena figures are the call's.  A failed plan does not raise; every
+        other failure raises PorrtError for the whole call."""
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, 2))
+        n = st.shape[0]
+        pr = np.ascontiguousarray(np.asarray(priors, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1)))
+        nw = pr.shape[1]
+        sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
+        self._chk(self._l.porrt_tamp_rrt_plan_astar_batch(self._c, n, st.ctypes.data, pr.ctypes.data, None if sd is None else sd.ctypes.data,
+                                                           nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K))
+        call = self.tamp_info()
+        call.update(self.tamp_astar_info())
+        out = []
+        for p in range(n):
+            rec = TampBatchPlan()
+            self._chk(self._l.porrt_tamp_batch_get_plan(self._c, p, C.byref(rec)))
+            d = dict(call)
+            d.update({k: getattr(rec, k) for k in ("status", "fail_node", "fail_zone", "fail_query", "search_cost", "expected_cost",
+                                                   "search_nodes", "queries", "waves", "speculated")})
+            d["zone_order"] = [int(rec.zone_order[k]) for k in range(rec.n_order)]
+            if rec.status == 0:
+                m = int(rec.policy_nodes)
+                xy, par = np.zeros((m, 2)), np.zeros(m, dtype=np.int64)
+                leaf, bel = np.zeros(m, dtype=np.uint8), np.zeros((m, nw))
+                self._chk(self._l.porrt_tamp_batch_policy(self._c, p, xy.ctypes.data, par.ctypes.data, leaf.ctypes.data, bel.ctypes.data, m, None))
+                d.update(xy=xy, parents=par, is_leaf=leaf, beliefs=bel)
+            out.append(d)
+        return out
+
+    def tamp_batch_astar_nodes(self, plan):
+        """the search nodes of plan `plan` of the last plan_tamp_rrt_astar_batch in id order (of a failed plan: those made so far):
+        dict(parents, targets, ec, priority)"""
+        n = self._chk(self._l.porrt_tamp_batch_astar_nodes(self._c, plan, None, None, None, None, 0))
+        par, tgt = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        ec, pr = np.zeros(n), np.zeros(n)
+        self._chk(self._l.porrt_tamp_batch_astar_nodes(self._c, plan, par.ctypes.data, tgt.ctypes.data, ec.ctypes.data, pr.ctypes.data, n))
         return dict(parents=par, targets=tgt, ec=ec, priority=pr)
 
     def tamp_viewpoints_info(self):
