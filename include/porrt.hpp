@@ -593,6 +593,31 @@ public:
         ctx_.check(porrt_qmdp_info(ctx_.get(), &i));
         return i;
     }
+    // get_policy_graph (qmdp_policy_extractor.rs:125-127, pto_graph.rs:363-419) after plan_qmdp: the graph pruned to the edges that
+    // are the right decision under some belief.  keep / how: one byte per adjacency entry of the original graph in push order;
+    // children[u] / parents[u]: the pruned lists in push order.
+    struct PolicyGraph {
+        std::vector<uint8_t> keep, how;
+        std::vector<std::vector<uint32_t>> children, parents;
+        struct porrt_policy_graph_info info;
+    };
+    PolicyGraph get_policy_graph() {
+        ctx_.check(porrt_qmdp_policy_graph(ctx_.get()));
+        PolicyGraph g;
+        ctx_.check(porrt_qmdp_policy_graph_info(ctx_.get(), &g.info));
+        const size_t n = (size_t)porrt_num_nodes(ctx_.get());
+        g.keep.resize(g.info.entries + 1); g.how.resize(g.info.entries + 1);
+        std::vector<uint64_t> coff(n + 1), poff(n + 1);
+        std::vector<uint32_t> cid(g.info.kept + 1), pid(g.info.kept + 1);
+        ctx_.check(porrt_qmdp_policy_graph_get(ctx_.get(), g.keep.data(), g.how.data(), coff.data(), cid.data(), poff.data(), pid.data()));
+        g.keep.resize(g.info.entries); g.how.resize(g.info.entries);
+        g.children.resize(n); g.parents.resize(n);
+        for (size_t u = 0; u < n; ++u) {
+            g.children[u].assign(cid.begin() + coff[u], cid.begin() + coff[u + 1]);
+            g.parents[u].assign(pid.begin() + poff[u], pid.begin() + poff[u + 1]);
+        }
+        return g;
+    }
     // the expansion without copying the lists to the host (plan_belief_space only needs the policy)
     void build_belief_graph_on_device(const BeliefState &start_belief_state) {
         ctx_.check(porrt_build_belief_graph(ctx_.get(), start_belief_state.data(), (uint32_t)start_belief_state.size()));
@@ -624,6 +649,34 @@ inline std::vector<std::vector<double>> qmdp_costs(const std::vector<State> &sta
     if (r != PORRT_OK) throw std::runtime_error("porrt_qmdp_costs failed (" + std::to_string(r) + ")");
     std::vector<std::vector<double>> out(nw);
     for (size_t w = 0; w < nw; ++w) out[w].assign(flat.begin() + w * n, flat.begin() + (w + 1) * n);
+    return out;
+}
+
+// get_policy_graph (pto_graph.rs:363-419) of an explicit graph (porrt_policy_graph): children[i] in push order, costs[world][node]
+// (+inf allowed).  Returns the pruned children lists; keep / how (one byte per adjacency entry in push order) and info on request.
+inline std::vector<std::vector<uint32_t>> policy_graph(const std::vector<std::vector<uint32_t>> &children, const std::vector<std::vector<double>> &costs,
+                                                       std::vector<uint8_t> *keep_out = nullptr, std::vector<uint8_t> *how_out = nullptr,
+                                                       struct porrt_policy_graph_info *info = nullptr, int device = 0) {
+    const size_t n = children.size(), nw = costs.size();
+    std::vector<double> flat(n * nw + 1);
+    std::vector<uint64_t> coff(n + 1, 0);
+    std::vector<uint32_t> cid;
+    for (size_t i = 0; i < n; ++i) { cid.insert(cid.end(), children[i].begin(), children[i].end()); coff[i + 1] = cid.size(); }
+    for (size_t w = 0; w < nw; ++w) {
+        if (costs[w].size() != n) throw std::runtime_error("policy_graph: costs[world][node], one value per node");
+        std::copy(costs[w].begin(), costs[w].end(), flat.begin() + w * n);
+    }
+    const size_t ne = cid.size();
+    cid.push_back(0);                                        // (never read: keeps data() non-null for empty lists)
+    std::vector<uint8_t> keep(ne + 1), how(ne + 1);
+    const int r = porrt_policy_graph(device, (uint64_t)n, (uint32_t)nw, coff.data(), cid.data(), flat.data(), keep.data(), how.data(), info);
+    if (r != PORRT_OK) throw std::runtime_error("porrt_policy_graph failed (" + std::to_string(r) + ")");
+    keep.resize(ne); how.resize(ne);
+    std::vector<std::vector<uint32_t>> out(n);
+    for (size_t i = 0; i < n; ++i)
+        for (uint64_t k = coff[i]; k < coff[i + 1]; ++k) if (keep[k]) out[i].push_back(cid[k]);
+    if (keep_out) *keep_out = keep;
+    if (how_out) *how_out = how;
     return out;
 }
 

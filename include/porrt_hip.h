@@ -503,7 +503,7 @@ int      porrt_reparent_policies_info(const porrt_ctx *ctx, struct porrt_reparen
  * has the world) from Reachability::get_final_nodes_for_world(w) (pto_reachability.rs:58-63).  All worlds are solved in one set
  * of device sweeps over cost planes interleaved per node; any evaluation order ends in the reference's fixpoint, bit for bit.
  * The costs stay on the device.  PORRT_ERR_INVALID with "We should have final node ids for each world" when a world has no final
- * node (:28-30), or when the context holds no PTO graph.  get_policy_graph (pto_graph.rs:363-419, an LP) is not offered. */
+ * node (:28-30), or when the context holds no PTO graph.  get_policy_graph (pto_graph.rs:363-419) is porrt_qmdp_policy_graph below. */
 int      porrt_qmdp_plan(porrt_ctx *ctx);
 /* out[w * N + id] = cost_to_goals[w][id], n_worlds * N doubles, N = porrt_num_nodes(ctx); +inf where no final node of w is reached */
 int      porrt_qmdp_get_costs(const porrt_ctx *ctx, double *out);
@@ -535,6 +535,46 @@ int64_t  porrt_qmdp_react(porrt_ctx *ctx, const double *starts, const double *be
 int      porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *node_validity, const uint64_t *validities,
                           uint32_t n_validities, uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids,
                           const uint64_t *final_off, const uint64_t *final_ids, double *out);
+
+/* ---- get_policy_graph (pto_graph.rs:363-419; QMdpPolicyExtractor::get_policy_graph, qmdp_policy_extractor.rs:125-127): the PTO
+ * graph pruned to the edges that are the right decision under some belief.  For an adjacency entry (u, t): V = the worlds where
+ * cost_to_goals[w][t] is finite; one row per entry o of children(u) with o != t (by id; duplicates give duplicate rows):
+ * d_o[w] = cost[w][t] - cost[w][o] for w in V, 0 where cost[w][o] is +inf (the reference leaves the term out).  The entry is kept iff
+ * some b >= 0 on V with sum b = 1 has d_o . b <= 0 for every o, i.e. the game value v* = min_b max_o d_o . b is <= 0.  The cost of
+ * the edge u -> t itself is not in the LP (the reference's rule).  Every decision is taken on the original graph.
+ * how[e], one byte per entry in push order (kept iff 1, 3 or 5):
+ *   0 V empty: pruned.   1 some world w of V has d_o[w] <= 0 for all o: kept.   2 some rival has d_o[w] > 0 on all of V: pruned.
+ *   3 / 4  the f64 simplex of DESIGN.md section 26 (Bland's rule, serial sums in world order, no contraction) reached
+ *          v <= PORRT_POLICY_GRAPH_TOL * scale: kept / stopped at an optimum above it: pruned; scale = max |d_o[w]| of the entry.
+ *   5 option "policy_graph_max_pivots" (default 4096) used up: undecided, kept -- pruning happens only on proof.
+ * PORRT_POLICY_GRAPH_TOL is this interface's own tolerance (the reference solves through the minilp crate, whose tolerances are its
+ * own): the f64 value is within 1e-12 * scale of the exact one on the inputs of tests/test_policy_graph_cpu.py, and an entry with
+ * 0 < v* <= 2 * TOL * scale (a tie in exact arithmetic that rounding of the costs opened) may go either way.
+ * PORRT_POLICY_GRAPH_EPS: multipliers, rates and pivot elements below it (relative) count as zero inside the simplex. */
+#define PORRT_POLICY_GRAPH_TOL 1e-9
+#define PORRT_POLICY_GRAPH_EPS 1e-13
+/* Counts: entries, kept, entries per how value, residual (entries that went to the simplex), pivots in total and the most of one
+ * entry.  Milliseconds on the device (HIP events) and wall for the three passes: classify (how 0-2), simplex, compaction. */
+struct porrt_policy_graph_info {
+    uint64_t entries, kept, how[6], residual, pivots_total, pivots_max;
+    double ms_classify_device, ms_classify_wall, ms_simplex_device, ms_simplex_wall, ms_compact_device, ms_compact_wall;
+};
+/* On the graph and the costs of the last porrt_qmdp_plan of this context.  PORRT_ERR_INVALID without a porrt_qmdp_plan since the
+ * last growth (the rule of porrt_qmdp_react). */
+int      porrt_qmdp_policy_graph(porrt_ctx *ctx);
+/* The result of the last porrt_qmdp_policy_graph; any pointer may be NULL.  keep, how: one byte per adjacency entry of the original
+ * graph in push order (2 * edges).  child_off (N + 1) / child_ids (kept entries): the pruned children lists in push order.
+ * parent_off / parent_ids: the pruned parents lists -- parents[x] of a PTO graph has the order of children[x], and its entry p
+ * survives iff the entry (p, x) survived (remove_edge, pto_graph.rs:214-217). */
+int      porrt_qmdp_policy_graph_get(const porrt_ctx *ctx, uint8_t *keep, uint8_t *how, uint64_t *child_off, uint32_t *child_ids,
+                                     uint64_t *parent_off, uint32_t *parent_ids);
+int      porrt_qmdp_policy_graph_info(const porrt_ctx *ctx, struct porrt_policy_graph_info *out);
+/* The same decision on explicit host arrays (the form of the reference's tests, pto_graph.rs:574-623), no context: children as CSR
+ * in push order, costs[w * n + id].  keep, how: child_off[n] bytes each; keep, how and info may be NULL.  Children only: the push
+ * order of the parents lists cannot be recovered from a children CSR.  PORRT_ERR_INVALID for a NaN or -inf cost, an id >= n, or
+ * n_worlds outside 1 .. 64.  max_pivots is fixed at the default here. */
+int      porrt_policy_graph(int device, uint64_t n, uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids,
+                            const double *costs, uint8_t *keep, uint8_t *how, struct porrt_policy_graph_info *info);
 
 /* ---- measurement */
 typedef struct {
@@ -582,7 +622,9 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * box of its end pixels holds free pixels only, and walk it otherwise; 0 = always walk), "prm_rows" (porrt_prm_plan_paths: rows of
  * costs swept together in one pass, 1 .. 4096, default 256), "prm_xcd_rows" (1, default: a row's sweep workgroups are placed together
  * on one XCD; 0 = the plain grid order).  None of them changes a result.  "qmdp_max_states" (porrt_qmdp_react: a walk that would emit
- * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there.  "policy_max_nodes" (porrt_bg_extract_policies,
+ * more states than this is an error, 1 .. 2^31 - 1, default 1 << 16) is a safety bound: the reference does not terminate there.
+ * "policy_graph_max_pivots" (porrt_qmdp_policy_graph: an entry whose simplex would need more pivots is left undecided and kept, how 5;
+ * 0 .. 2^31 - 1, default 4096) is a bound of the same kind: no entry of the measured graphs came near it.  "policy_max_nodes" (porrt_bg_extract_policies,
  * porrt_mm_extract_policies: a policy that would have more nodes is status 4, 1 .. 2^24, default 1 << 16) is one too.
  * "refine_short_lds" (the batch refiner, default 1: the pieces of <= 256 nodes run in a launch of their own whose waves take 4 KiB
  * of LDS instead of 16; 0 = every piece in one launch; the results are the same bits). */

@@ -21,6 +21,7 @@
 #include "porrt_refine_batch.hpp"
 #include "porrt_reparent.hpp"
 #include "porrt_qmdp.hpp"
+#include "porrt_policy_graph.hpp"
 #include "porrt_join.hpp"
 
 #include <algorithm>
@@ -317,6 +318,9 @@ struct porrt_ctx {
     GrowScratch qmdp_scratch;              //   slots 0-4: the plan's buffers, 5-: a react call's
     uint32_t opt_qmdp_max_states = 1u << 16;       // "qmdp_max_states": a QMDP walk that would emit more states is an error (the reference would not terminate)
     int qmdp_plan();
+    PolicyGraphState pg;                   // porrt_qmdp_policy_graph: the pruned graph of the last call (host copies; qmdp_scratch slots 14-27)
+    uint32_t opt_policy_graph_max_pivots = 4096;   // "policy_graph_max_pivots": an entry whose simplex needs more is left undecided and kept (how 5)
+    int qmdp_policy_graph();
     int64_t qmdp_react(const double *starts, const double *beliefs, uint32_t n_worlds_in, const double *horizons, uint64_t n, uint64_t *path_off,
                        uint64_t *common_len, double *path_xy, uint64_t cap);
     EdgeOrderState eo;                     // adjacency order of the last PTO graph / roadmap (device)
@@ -2811,6 +2815,50 @@ int porrt_ctx::qmdp_plan() {
     return PORRT_OK;
 }
 
+// get_policy_graph (pto_graph.rs:363-419) on the graph and the cost planes of the last qmdp_plan (porrt_policy_graph.hpp): both are
+// on the device already.  A PTO graph's parents lists are its children lists (add_bi_edge), so the pruned parents come from the same
+// adjacency.  The results are kept on the host for porrt_qmdp_policy_graph_get.
+int porrt_ctx::qmdp_policy_graph() {
+    pg.valid = false;
+    if (!qmdp.valid || qmdp.tag != results_tag || !have_results) { set_err("qmdp_policy_graph: no costs for this graph: call porrt_qmdp_plan after the growth"); return PORRT_ERR_INVALID; }
+    HIPCHK(hipSetDevice(device));
+    int r = ensure_edge_order();
+    if (r) return r;
+    const size_t N = qmdp.N;
+    const unsigned long long E = 2ull * (unsigned long long)counters.n_edges;
+    GrowScratch &sc = qmdp_scratch;
+    PgDevice d{};
+    d.N = qmdp.N; d.W = qmdp.W; d.Wp = qmdp.Wp; d.E = E;
+    d.off = eo.d_adj_off; d.id = eo.d_adj_id; d.cost = qmdp.d_cost;
+    if (sc.get(14, d.how, E) != hipSuccess || sc.get(15, d.keep, E) != hipSuccess || sc.get(16, d.pkeep, E) != hipSuccess ||
+        sc.get(17, d.piv, E) != hipSuccess || sc.get(18, d.res_e, E) != hipSuccess || sc.get(19, d.res_u, E) != hipSuccess ||
+        sc.get(20, d.n_res, 1) != hipSuccess || sc.get(21, d.cnt, N) != hipSuccess || sc.get(22, d.c_off, N + 1) != hipSuccess ||
+        sc.get(23, d.p_off, N + 1) != hipSuccess || sc.get(24, d.c_id, E) != hipSuccess || sc.get(25, d.p_id, E) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err("qmdp_policy_graph: cannot allocate");
+        return PORRT_ERR_CAPACITY;
+    }
+    std::string e;
+    std::vector<uint32_t> piv;
+    if ((r = pg_run(d, opt_policy_graph_max_pivots, stream, pg.how, piv, pg.info, e))) { set_err(e); return r; }
+    pg.keep.resize(E);
+    for (unsigned long long k = 0; k < E; ++k) pg.keep[k] = (pg.how[k] == 1 || pg.how[k] == 3 || pg.how[k] == 5) ? 1 : 0;
+    pg.child_off.resize(N + 1); pg.parent_off.resize(N + 1);
+    HIPCHK(hipMemcpyAsync(pg.child_off.data(), d.c_off, (N + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(pg.parent_off.data(), d.p_off, (N + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (pg.child_off[N] != pg.info.kept || pg.parent_off[N] != pg.info.kept) { set_err("qmdp_policy_graph: the compaction disagrees with the flags"); return PORRT_ERR_DEVICE; }
+    pg.child_ids.resize(pg.info.kept); pg.parent_ids.resize(pg.info.kept);
+    if (pg.info.kept) {
+        HIPCHK(hipMemcpyAsync(pg.child_ids.data(), d.c_id, pg.info.kept * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(pg.parent_ids.data(), d.p_id, pg.info.kept * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    pg.tag = results_tag;
+    pg.valid = true;
+    return PORRT_OK;
+}
+
 // react_qmdp (qmdp_policy_extractor.rs:38-49) for n queries: the nearest node of every start on the host (the literal kd traversal,
 // as PRM::plan_path's), get_common_path by one wave per query and get_path by one wave per (query, world) on the device, each
 // counted first and written after the offsets are known.  Only lengths and states are downloaded.
@@ -4593,6 +4641,81 @@ int porrt_qmdp_costs(int device, uint64_t n, const double *xy, const uint32_t *n
     });
 }
 
+// ---- get_policy_graph (pto_graph.rs:363-419; porrt_policy_graph.hpp)
+int porrt_qmdp_policy_graph(porrt_ctx *c) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int { return c->qmdp_policy_graph(); });
+}
+
+static bool pg_ok(const porrt_ctx *c) { return qmdp_ok(c) && c->pg.valid && c->pg.tag == c->results_tag; }
+
+int porrt_qmdp_policy_graph_get(const porrt_ctx *c, uint8_t *keep, uint8_t *how, uint64_t *child_off, uint32_t *child_ids, uint64_t *parent_off,
+                                uint32_t *parent_ids) {
+    if (!c) return PORRT_ERR_INVALID;
+    if (!pg_ok(c)) { const_cast<porrt_ctx *>(c)->set_err("qmdp_policy_graph_get: no policy graph for this graph: call porrt_qmdp_policy_graph after porrt_qmdp_plan"); return PORRT_ERR_INVALID; }
+    const PolicyGraphState &g = c->pg;
+    auto out = [](void *dst, const void *src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+    out(keep, g.keep.data(), g.keep.size());
+    out(how, g.how.data(), g.how.size());
+    out(child_off, g.child_off.data(), g.child_off.size() * 8);
+    out(child_ids, g.child_ids.data(), g.child_ids.size() * 4);
+    out(parent_off, g.parent_off.data(), g.parent_off.size() * 8);
+    out(parent_ids, g.parent_ids.data(), g.parent_ids.size() * 4);
+    return PORRT_OK;
+}
+
+int porrt_qmdp_policy_graph_info(const porrt_ctx *c, struct porrt_policy_graph_info *out) {
+    if (!c || !out) return PORRT_ERR_INVALID;
+    if (!pg_ok(c)) { const_cast<porrt_ctx *>(c)->set_err("qmdp_policy_graph_info: no policy graph for this graph: call porrt_qmdp_policy_graph after porrt_qmdp_plan"); return PORRT_ERR_INVALID; }
+    *out = c->pg.info;
+    return PORRT_OK;
+}
+
+int porrt_policy_graph(int device, uint64_t n, uint32_t n_worlds, const uint64_t *child_off, const uint32_t *child_ids, const double *costs,
+                       uint8_t *keep, uint8_t *how, struct porrt_policy_graph_info *info) {
+    if (!n || !child_off || !costs || n_worlds < 1 || n_worlds > 64) return PORRT_ERR_INVALID;
+    const uint32_t W = n_worlds, Wp = (W + kQmdpLanes - 1) / kQmdpLanes * kQmdpLanes;
+    if (n >= 0xFFFFFFFFull / Wp || child_off[0] != 0) return PORRT_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) if (child_off[i + 1] < child_off[i]) return PORRT_ERR_INVALID;
+    const uint64_t nc = child_off[n];
+    if (nc && !child_ids) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < n * W; ++k) if (!(costs[k] >= -std::numeric_limits<double>::max())) return PORRT_ERR_INVALID;      // NaN, -inf
+    return abi_guard([&]() -> int {
+        if (hipSetDevice(device) != hipSuccess) return (int)PORRT_ERR_DEVICE;
+        std::vector<double> planes((size_t)n * Wp, std::numeric_limits<double>::infinity());            // node-major, the padding +inf
+        for (uint32_t w = 0; w < W; ++w)
+            for (uint64_t i = 0; i < n; ++i) planes[i * Wp + w] = costs[(size_t)w * n + i];
+        DeviceUploads dev;
+        PgDevice d{};
+        d.N = (uint32_t)n; d.W = W; d.Wp = Wp; d.E = nc;
+        d.off = dev.up<unsigned long long>(child_off, n + 1);
+        d.id = dev.up<uint32_t>(child_ids, nc);
+        d.cost = dev.up<double>(planes.data(), planes.size());
+        d.how = dev.up<uint8_t>(nullptr, nc); d.keep = dev.up<uint8_t>(nullptr, nc); d.pkeep = nullptr;
+        d.piv = dev.up<uint32_t>(nullptr, nc); d.res_e = dev.up<unsigned long long>(nullptr, nc); d.res_u = dev.up<uint32_t>(nullptr, nc);
+        d.n_res = dev.up<unsigned long long>(nullptr, 1); d.cnt = dev.up<unsigned long long>(nullptr, n);
+        d.c_off = dev.up<unsigned long long>(nullptr, n + 1); d.c_id = dev.up<uint32_t>(nullptr, nc);
+        int r = PORRT_ERR_DEVICE;
+        if (d.off && d.id && d.cost && d.how && d.keep && d.piv && d.res_e && d.res_u && d.n_res && d.cnt && d.c_off && d.c_id) {
+            std::string err;
+            std::vector<uint8_t> h_how;
+            std::vector<uint32_t> h_piv;
+            struct porrt_policy_graph_info i;
+            r = pg_run(d, 4096, nullptr, h_how, h_piv, i, err);
+            if (r == PORRT_OK) {
+                if (info) *info = i;
+                for (uint64_t k = 0; k < nc; ++k) {
+                    if (how) how[k] = h_how[k];
+                    if (keep) keep[k] = (h_how[k] == 1 || h_how[k] == 3 || h_how[k] == 5) ? 1 : 0;
+                }
+            }
+        }
+        (void)hipGetLastError();
+        return r;
+    });
+}
+
 // ---- MapShelfDomainTampRRT::plan(.., BranchAndBound) (porrt_tamp.hpp)
 int64_t porrt_tamp_rrt_plan(porrt_ctx *c, const double start[2], const double *initial_belief, uint32_t n_worlds, double max_step,
                             double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K) {
@@ -4902,6 +5025,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "prm_rows")) *value = c->opt_prm_rows;
     else if (!strcmp(name, "prm_xcd_rows")) *value = c->opt_prm_xcd_rows;
     else if (!strcmp(name, "qmdp_max_states")) *value = c->opt_qmdp_max_states;
+    else if (!strcmp(name, "policy_graph_max_pivots")) *value = c->opt_policy_graph_max_pivots;
     else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
     else if (!strcmp(name, "plan_batch_max_belief_nodes")) *value = (int64_t)c->opt_plan_batch_max_belief_nodes;
     else if (!strcmp(name, "plan_batch_host_ranks")) *value = c->opt_plan_batch_host_ranks;
@@ -4962,6 +5086,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "policy_max_nodes")) { if (value < 1 || value > (int64_t)kPolMaxNodesLimit) { c->set_err("policy_max_nodes: 1 .. 2^24"); return PORRT_ERR_INVALID; } c->opt_policy_max_nodes = (uint32_t)value; }
     else if (!strcmp(name, "plan_batch_max_belief_nodes")) { if (value < 1 || value > (int64_t)kJoinBeliefNodesLimit) { c->set_err("plan_batch_max_belief_nodes: 1 .. 2^32 - 2"); return PORRT_ERR_INVALID; } c->opt_plan_batch_max_belief_nodes = (uint64_t)value; }
     else if (!strcmp(name, "plan_batch_host_ranks")) c->opt_plan_batch_host_ranks = value != 0;
+    else if (!strcmp(name, "policy_graph_max_pivots")) { if (value < 0 || value > (int64_t)0x7FFFFFFF) { c->set_err("policy_graph_max_pivots: 0 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_policy_graph_max_pivots = (uint32_t)value; }
     else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again

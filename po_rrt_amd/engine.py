@@ -49,6 +49,7 @@ SYMBOLS = [
     "porrt_tamp_rrt_plan_astar", "porrt_tamp_rrt_get_astar_info", "porrt_tamp_astar_nodes", "porrt_tamp_shortcut_paths_resident",
     "porrt_tamp_rrt_plan_astar_batch", "porrt_tamp_batch_get_plan", "porrt_tamp_batch_policy", "porrt_tamp_batch_astar_nodes",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
+    "porrt_qmdp_policy_graph", "porrt_qmdp_policy_graph_get", "porrt_qmdp_policy_graph_info", "porrt_policy_graph",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
     "porrt_policies_info",
     "porrt_bg_refine_policies", "porrt_mm_refine_policies", "porrt_refine_policies", "porrt_refine_policies_info",
@@ -107,6 +108,17 @@ class QmdpInfo(C.Structure):
     _fields_ = [("nodes", C.c_uint64), ("edges", C.c_uint64), ("worlds", C.c_uint64), ("sweeps", C.c_uint64), ("queries", C.c_uint64),
                 ("ms_plan_device", C.c_double), ("ms_plan_wall", C.c_double), ("ms_react_device", C.c_double), ("ms_react_wall", C.c_double),
                 ("ms_nearest", C.c_double)]
+
+
+class PolicyGraphInfo(C.Structure):
+    """struct porrt_policy_graph_info"""
+    _fields_ = [("entries", C.c_uint64), ("kept", C.c_uint64), ("how", C.c_uint64 * 6), ("residual", C.c_uint64),
+                ("pivots_total", C.c_uint64), ("pivots_max", C.c_uint64),
+                ("ms_classify_device", C.c_double), ("ms_classify_wall", C.c_double), ("ms_simplex_device", C.c_double),
+                ("ms_simplex_wall", C.c_double), ("ms_compact_device", C.c_double), ("ms_compact_wall", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "how" else getattr(self, k)) for k, _ in self._fields_}
 
 
 class PoliciesInfo(C.Structure):
@@ -301,6 +313,10 @@ def load_library():
     sig("porrt_qmdp_get_costs", C.c_int, vp, _f64p)
     sig("porrt_qmdp_info", C.c_int, vp, C.POINTER(QmdpInfo))
     sig("porrt_qmdp_react", C.c_int64, vp, _f64p, _f64p, C.c_uint32, _f64p, C.c_uint64, _u64p, _u64p, C.c_void_p, C.c_uint64)
+    sig("porrt_qmdp_policy_graph", C.c_int, vp)
+    sig("porrt_qmdp_policy_graph_get", C.c_int, vp, vp, vp, vp, vp, vp, vp)
+    sig("porrt_qmdp_policy_graph_info", C.c_int, vp, C.POINTER(PolicyGraphInfo))
+    sig("porrt_policy_graph", C.c_int, C.c_int, C.c_uint64, C.c_uint32, _u64p, _u32p, vp, vp, vp, C.POINTER(PolicyGraphInfo))
     sig("porrt_qmdp_costs", C.c_int, C.c_int, C.c_uint64, _f64p, _u32p, _u64p, C.c_uint32, C.c_uint32, _u64p, _u32p, _u64p, _u64p, _f64p)
     sig("porrt_bg_extract_policies", C.c_int64, vp, _u64p, C.c_uint64, _u64p, _u8p, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_bg_get_policies", C.c_int64, vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
@@ -801,6 +817,28 @@ class Engine:
             self._chk(int(self._l.porrt_qmdp_react(*args, xy.ctypes.data_as(C.c_void_p), total)))
         paths = [[xy[int(off[q * nw + w]):int(off[q * nw + w + 1])] for w in range(nw)] for q in range(n)]
         return (paths, cl[:n].copy()) if with_common_len else paths
+
+    def qmdp_policy_graph(self):
+        """get_policy_graph (pto_graph.rs:363-419) on the graph and costs of the last qmdp_plan; the result stays with the context"""
+        self._chk(self._l.porrt_qmdp_policy_graph(self._c))
+
+    def qmdp_policy_graph_get(self):
+        """the last qmdp_policy_graph: dict of keep, how (one byte per adjacency entry in push order) and the pruned children and
+        parents lists as CSR (child_off, child_ids, parent_off, parent_ids)"""
+        i = self.qmdp_policy_graph_info()
+        n = self.num_nodes()
+        keep, how = np.zeros(i["entries"], dtype=np.uint8), np.zeros(i["entries"], dtype=np.uint8)
+        co, po = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+        ci, pi = np.zeros(i["kept"], dtype=np.uint32), np.zeros(i["kept"], dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self._l.porrt_qmdp_policy_graph_get(self._c, p(keep), p(how), p(co), p(ci), p(po), p(pi)))
+        return dict(keep=keep.astype(bool), how=how, child_off=co, child_ids=ci, parent_off=po, parent_ids=pi)
+
+    def qmdp_policy_graph_info(self):
+        """porrt_qmdp_policy_graph_info of the last qmdp_policy_graph"""
+        i = PolicyGraphInfo()
+        self._chk(self._l.porrt_qmdp_policy_graph_info(self._c, C.byref(i)))
+        return i.as_dict()
 
     def qmdp_info(self):
         """porrt_qmdp_info of the last qmdp_plan / qmdp_react"""
@@ -1322,6 +1360,28 @@ def qmdp_costs_explicit(xy, node_validity, validities, children, finals, device=
     if rc != 0:
         raise RuntimeError("porrt_qmdp_costs failed (%d)" % rc)
     return out
+
+
+def policy_graph_explicit(children, costs, device=0):
+    """porrt_policy_graph: get_policy_graph's decision (pto_graph.rs:363-419) for every adjacency entry of an explicit graph on the
+    GPU.  children: per-node lists in push order; costs[w][id] (+inf allowed).  Returns (keep, how, info): one entry per adjacency
+    entry in push order, and the counts and times as a dict."""
+    L = load_library()
+    n = len(children)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(c) for c in children])
+    ids = np.array([i for c in children for i in c], dtype=np.uint32)
+    cost = _f64(costs)
+    if cost.ndim != 2 or cost.shape[1] != n:
+        raise ValueError("policy_graph_explicit: costs[w][id], one row per world")
+    keep, how = np.zeros(max(len(ids), 1), dtype=np.uint8), np.zeros(max(len(ids), 1), dtype=np.uint8)
+    info = PolicyGraphInfo()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = L.porrt_policy_graph(device, n, cost.shape[0], off, ids if len(ids) else np.zeros(1, dtype=np.uint32), p(cost), p(keep), p(how),
+                              C.byref(info))
+    if rc != 0:
+        raise RuntimeError("porrt_policy_graph failed (%d)" % rc)
+    return keep[:len(ids)].astype(bool), how[:len(ids)], info.as_dict()
 
 
 def exchange_decide(entries):
