@@ -98,7 +98,15 @@ int porrt_set_observation_goal(porrt_ctx *ctx, uint32_t zone_id);
  * PORRT_MODE_RRT and PTO::grow_graph (pto.rs:55-139) when PORRT_MODE_PTO.
  * batch_K samples are expanded per step against the tree as it stands at the start
  * of the step; batch_K = 1 is the reference's loop.  Returns PORRT_OK,
- * PORRT_INCOMPLETE (PTO only) or an error. */
+ * PORRT_INCOMPLETE (PTO only) or an error.
+ * Replays: the call runs the growth again, from the sampler state it was entered with, when a neighbour list overflowed (the lists
+ * grow: "cand_cap"), when a float draw of the device sampler would have been redrawn (again with the exact host stream), when the
+ * PTO edge pool overflowed ("edge_per_node" * 4) and when the pool of deferred equal-cost parents overflowed ("tie_pool_ids", or
+ * the default pool, * 4); at most 12 attempts.  The results are those of the attempt that went through.
+ * What a failed growth leaves: after PORRT_ERR_CAPACITY (a pool that may grow no more, the region page pool, the attempts used up)
+ * the context has NO results -- the getters answer as on a context that never grew -- and its samplers stand where the call found
+ * them; likewise after every other error that leaves no results ("injected sample stream exhausted", a device error).
+ * PORRT_ERR_RASTER of a porrt_grow keeps the results and the sampler state of the run that met it. */
 int porrt_grow(porrt_ctx *ctx, const double start[2], double max_step, double search_radius,
                uint64_t n_iter_min, uint64_t n_iter_max, uint32_t batch_K, int mode);
 
@@ -111,6 +119,11 @@ int porrt_grow(porrt_ctx *ctx, const double start[2], double max_step, double se
  * starts = n_ctx x 2.  Every context keeps its own map, goal, sampler state and results, exactly as after n_ctx porrt_grow calls
  * with the same arguments; the getters are per context.  Contexts must not be used concurrently elsewhere during the call.
  * Returns the worst member code (PORRT_INCOMPLETE if a PTO member's final set is incomplete).
+ * Only the neighbour lists are regrown for a batch.  A member whose draw would have been redrawn (PORRT_ERR_INVALID, "grow this
+ * context on its own") or whose edge or deferred-tie pool overflowed (PORRT_ERR_CAPACITY) fails the call, as does any other negative
+ * member code; then EVERY context of the call is as the call found it -- sampler and world streams, injected stream positions --
+ * except that none has results and none belongs to a batch: each can be grown on its own, or the batch again, as if the call had
+ * not been made.  (A call refused for its arguments before a context was begun on leaves that context untouched, results included.)
  * porrt_grow_batch_each: the same with n_iter_min[q], n_iter_max[q] per context. */
 int porrt_grow_batch(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *starts, double max_step,
                      double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, uint32_t batch_K, int mode);
@@ -594,7 +607,11 @@ typedef struct {
 } porrt_metrics;
 int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
 /* options: "profile" (0/1 per-kernel HIP events), "cand_cap" (initial neighbour-list
- * capacity per sample), "graph" (0/1 replay the growth loop as a hipGraph), "kd_group" (steps whose
+ * capacity per sample), "edge_per_node" and "tie_pool_ids" (TEST SEAMS, the same kind of initial capacity: the PTO edge pool holds
+ * (n_iter_max + 2) * edge_per_node + 4096 edges, 1 .. 65536, default 256; the pool of deferred equal-cost parents holds tie_pool_ids
+ * node ids, 1 .. 2^30, or with the default 0 max(2^20, 16 * n_iter_max); a porrt_grow whose pool overflows multiplies the one in
+ * force by 4 and runs again, see "Replays" below; a context that has grown before keeps its larger edge buffers),
+ * "graph" (0/1 replay the growth loop as a hipGraph), "kd_group" (steps whose
  * new nodes enter the tie-order structure together; 0 = chosen from batch_K), "group_lanes" (RRT*
  * step kernels: 16 / 32 / 64 lanes per sample, 0 = one wave per sample, -1 = chosen from the number
  * of contexts advanced together), "batch_streams" (on the FIRST context of a porrt_grow_batch: the
@@ -635,7 +652,9 @@ int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
  * this context led -- needed the whole kd structure, which was built after its steps), "kd_lca_steps" (this context's own need: 1 + the
  * last step with a tie that took that structure, 0 = none), "compactions" (how often the last batch this context led gathered the
  * members still running), "n_heavy" (samples of this context's last grow with more hits than their LDS list holds: served by a whole wave
- * from the lists in memory), "conn_wg_waves", "conn_riders_first", "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed), "dp_wide_rows", "dp_levels" and "dp_wide_levels" (the levels of the last layered expected costs, 0 when the
+ * from the lists in memory), "conn_wg_waves", "conn_riders_first", "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed),
+ * "edge_per_node" and "tie_pool_ids" (likewise: what the last attempt ran with; tie_pool_ids stays 0 while the default pool is in force),
+ * "tie_pooled_ids" and "tie_records" (the last growth's last attempt: node ids that deferred ties asked the pool for, and their records), "dp_wide_rows", "dp_levels" and "dp_wide_levels" (the levels of the last layered expected costs, 0 when the
  * general sweeps ran; bit k of the mask: level k -- k-th smallest number of possible worlds -- ran the wide kernel) */
 int porrt_get_option(const porrt_ctx *ctx, const char *name, int64_t *value);
 

@@ -123,6 +123,7 @@ def lib():
     sig("orc_pcg64_seed_from_u64", None, vp, C.c_uint64)
     sig("orc_pcg64_next_u64", C.c_uint64, vp)
     sig("orc_pcg64_get_state", None, vp, _u64p)
+    sig("orc_pcg64_advance_u64", None, vp, C.c_uint64, C.c_uint64)
     sig("orc_gen_range_f64", C.c_double, vp, C.c_double, C.c_double)
     sig("orc_gen_range_usize", C.c_uint64, vp, C.c_uint64, C.c_uint64)
     # kd-tree
@@ -191,6 +192,16 @@ class Pcg64:
         out = np.zeros(4, dtype=np.uint64)
         lib().orc_pcg64_get_state(self._p, out)
         return out
+
+    def advance(self, delta):
+        """the jump-ahead the product's device sampler takes (orc_pcg64_advance)"""
+        m = (1 << 64) - 1
+        lib().orc_pcg64_advance_u64(self._p, delta & m, delta >> 64)
+
+    def copy(self):
+        r = Pcg64()
+        C.memmove(r._buf, self._buf, 32)
+        return r
 
 
 class Oracle:

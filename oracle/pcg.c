@@ -108,6 +108,10 @@ void orc_pcg64_advance(orc_pcg64 *r, u128 delta) {
     r->state = acc_mult * r->state + acc_plus;
 }
 
+void orc_pcg64_advance_u64(orc_pcg64 *r, uint64_t delta_lo, uint64_t delta_hi) {
+    orc_pcg64_advance(r, ((u128)delta_hi << 64) | delta_lo);
+}
+
 static double u64_bits_to_f64(uint64_t b) {
     double d;
     memcpy(&d, &b, 8);

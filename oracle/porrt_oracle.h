@@ -55,6 +55,7 @@ uint64_t orc_gen_range_usize(orc_pcg64 *r, uint64_t low, uint64_t high);
 /* flat helpers for ctypes (no __int128 in the signature) */
 void     orc_pcg64_new_u64(orc_pcg64 *r, uint64_t state_lo, uint64_t state_hi, uint64_t stream_lo, uint64_t stream_hi);
 void     orc_pcg64_get_state(const orc_pcg64 *r, uint64_t out4[4]);
+void     orc_pcg64_advance_u64(orc_pcg64 *r, uint64_t delta_lo, uint64_t delta_hi);
 
 /* --------------------------------------------------------------- domain.c */
 double orc_norm1(const double a[2], const double b[2]);

@@ -172,6 +172,7 @@ struct porrt_ctx {
     uint64_t opt_dp_wide_rows = kDpWideRows;   // "dp_wide_rows": a level of the layered costs with N * W >= this sweeps wide (0 = every level)
     uint32_t opt_cand_cap = 2048;
     uint64_t edge_per_node = 256, tie_pool_mult = 16;      // pool sizes: grown and the run replayed when one overflows (as the neighbour lists)
+    uint64_t tie_pool_ids = 0;             // "tie_pool_ids" (test seam): the deferred-tie pool in ids, 0 = max(2^20, tie_pool_mult * n_iter_max)
     // ---- device buffers
     DevBuf<double> d_nx, d_ny, d_distA, d_distB, d_sx, d_sy, d_qx, d_qy, d_pgxy, d_pgd, d_candxy, d_candval, d_radT2, d_inj, d_ssx, d_ssy, d_bqx, d_bqy, d_t2at;
     DevBuf<int> d_parent, d_qnn, d_qvid, d_pgid, d_candid, d_gid, d_kdup;
@@ -1119,7 +1120,8 @@ static std::vector<std::pair<uint32_t, uint32_t>> kd_after_ties(uint32_t K, uint
 // The end of a growth: the counters into results, tags, sampler state and metrics, the error bits into codes and texts.  The context
 // has results afterwards unless the run is to be replayed or was refused (have_results).  member: a row of a porrt_grow_batch -- a
 // redraw is an error there (alone: -101, replayed with the exact host stream host_rng), and an edge or deferred-tie pool that
-// overflowed is a capacity error (alone: -102 / -103, replayed with a larger pool).
+// overflowed is a capacity error (alone: -102 / -103, replayed with a larger pool).  A capacity error leaves no results: n_edges counts
+// the edges that found no slot as well, and a tie that found no record left its node's parent unset.
 int porrt_ctx::finish_growth(const Counters &hc, uint32_t n_final_nodes, uint64_t iters, uint32_t steps, uint32_t own_steps, float device_ms, bool member,
                              const Pcg64 *host_rng) {
     if (!member && hc.coop_abort) { set_err("the persistent step loop gave up waiting (a barrier or a kd kernel beside it): results discarded"); return PORRT_ERR_DEVICE; }
@@ -1130,7 +1132,7 @@ int porrt_ctx::finish_growth(const Counters &hc, uint32_t n_final_nodes, uint64_
         return -101;
     }
     if (!member && (hc.err & ERR_EDGE_OVERFLOW) && ((uint64_t)rc.sched_max_nodes * edge_per_node + 4096 < (1ull << 31))) return -102;
-    if (!member && (hc.err & ERR_TIE_POOL) && tie_pool_mult < (1ull << 12)) return -103;
+    if (!member && (hc.err & ERR_TIE_POOL) && (tie_pool_ids ? tie_pool_ids <= (1ull << 28) : tie_pool_mult < (1ull << 12))) return -103;     // (a set pool grows to 2^30 ids at the most)
     counters = hc;
     if (member && getenv("PORRT_DEBUG_ALL") && hc.tim[10]) fprintf(stderr, "[porrt] member %u: longest k_kd_claim workgroup %.1f us, mean %.1f us\n", batch_slot, 1e-2 * (double)hc.tim[2], hc.tim[8] ? 1e-2 * (double)hc.tim[0] / (double)hc.tim[8] : 0.0);
     if (getenv("PORRT_DEBUG") && (!member || batch_slot == 0)) {
@@ -1143,6 +1145,11 @@ int porrt_ctx::finish_growth(const Counters &hc, uint32_t n_final_nodes, uint64_
         for (int t = 0; t < 8; ++t)
             if (hc.tim[t + 8]) fprintf(stderr, "[porrt] phase %d: %.2f us per wave over %llu waves (total %.1f wave-ms)\n", t, 1e-2 * (double)hc.tim[t] / (double)hc.tim[t + 8],
                                        (unsigned long long)hc.tim[t + 8], 1e-5 * (double)hc.tim[t]);
+    }
+    if (hc.err & (ERR_EDGE_OVERFLOW | ERR_TIE_POOL | ERR_PAGE_OVERFLOW)) {
+        counters.n_edges = counters.n_final = 0;           // (kept for the views of the pools alone)
+        set_err((hc.err & ERR_EDGE_OVERFLOW) ? "edge pool overflow" : "deferred-tie pool / region page pool overflow");
+        return PORRT_ERR_CAPACITY;
     }
     n_iter = iters;
     n_steps = steps;                 // n_at[steps] is the final size (carried along by k_row_sched if a batch's row ended earlier)
@@ -1164,8 +1171,6 @@ int porrt_ctx::finish_growth(const Counters &hc, uint32_t n_final_nodes, uint64_
     metrics.device_s = device_ms * 1e-3;
     metrics.total_s = metrics.device_s;          // (a stand-alone grow puts its host time here afterwards)
     if (hc.err & ERR_RASTER) { set_err("raster access outside the map, door pixel without zone id, or two zones on one segment (the reference panics here)"); return PORRT_ERR_RASTER; }
-    if (hc.err & ERR_EDGE_OVERFLOW) { set_err("edge pool overflow"); return PORRT_ERR_CAPACITY; }
-    if (hc.err & (ERR_TIE_POOL | ERR_PAGE_OVERFLOW)) { set_err("deferred-tie pool / region page pool overflow"); return PORRT_ERR_CAPACITY; }
     if (mode == PORRT_MODE_PTO && !complete) { set_err("final nodes are not reached for each world"); return PORRT_INCOMPLETE; }
     return PORRT_OK;
 }
@@ -1236,9 +1241,10 @@ int porrt_ctx::grow(const double start[2], double max_step, double search_radius
             host_samples = true;
         } else if (rc_ == -102) {   // edge pool (PTO: the reference's parameters reach ~240 neighbours per node): regrow and replay
             edge_per_node *= 4;
-        } else if (rc_ == -103) {   // deferred-tie pool
-            tie_pool_mult *= 4;
+        } else if (rc_ == -103) {   // deferred-tie pool: whichever size is in force
+            (tie_pool_ids ? tie_pool_ids : tie_pool_mult) *= 4;
         } else {
+            if (rc_ < 0 && !have_results) s0.restore(*this);         // a failure that leaves no results: the samplers as before the call
             return rc_;
         }
         s0.restore(*this);
@@ -1264,7 +1270,7 @@ int porrt_ctx::grow_once(const double start[2], double max_step, double search_r
     const uint32_t Kpad = vwords * 64;       // sample stride of the per-chunk arrays (multiple of the wave size)
     const uint32_t cand_cap = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(opt_cand_cap, 64), Nmax);
     // deferred equal-cost parents: at most one record per iteration; the pooled ids are bounded by experience
-    const uint64_t pend_cap = n_iter_max + 2, pool_cap = std::max<uint64_t>(1u << 20, tie_pool_mult * n_iter_max);
+    const uint64_t pend_cap = n_iter_max + 2, pool_cap = tie_pool_ids ? tie_pool_ids : std::max<uint64_t>(1u << 20, tie_pool_mult * n_iter_max);
     {
         double t0 = now_s();
         HIPCHK(d_nx.reserve(Nmax)); HIPCHK(d_ny.reserve(Nmax)); HIPCHK(d_distA.reserve(Nmax)); HIPCHK(d_distB.reserve(Nmax));
@@ -3511,10 +3517,8 @@ struct ThreadJoiner {
     ~ThreadJoiner() { for (auto &t : th) if (t.joinable()) t.join(); }
 };
 
-static int grow_batch_each(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *starts, double max_step, double search_radius, const uint64_t *n_iter_min,
-                           const uint64_t *n_iter_max, uint32_t batch_K, int mode) {
-    if (!ctxs || !n_ctx || !starts || !ctxs[0] || !n_iter_min || !n_iter_max) return PORRT_ERR_INVALID;
-    for (uint32_t q = 0; q < n_ctx; ++q) if (!ctxs[q]) return PORRT_ERR_INVALID;
+static int grow_batch_parts(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *starts, double max_step, double search_radius, const uint64_t *n_iter_min,
+                            const uint64_t *n_iter_max, uint32_t batch_K, int mode) {
     uint32_t G = ctxs[0]->opt_batch_streams ? ctxs[0]->opt_batch_streams : (n_ctx >= 32 ? 2u : 1u);
     G = std::min(G, n_ctx);
     if (G <= 1) { ctxs[0]->last_launch_mode = 0; return grow_batch(ctxs, n_ctx, starts, max_step, search_radius, n_iter_min, n_iter_max, batch_K, mode); }
@@ -3569,6 +3573,29 @@ static int grow_batch_each(porrt_ctx *const *ctxs, uint32_t n_ctx, const double 
         worst = std::max(worst, rcs[g]);
     }
     return worst;
+}
+
+// A porrt_grow_batch that fails leaves every context it had begun on as the call found it, but without results: members before the
+// failing one had results and samplers that had moved on, members behind it had drawn their worlds (stage 1) and had nothing.
+static int grow_batch_each(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *starts, double max_step, double search_radius, const uint64_t *n_iter_min,
+                           const uint64_t *n_iter_max, uint32_t batch_K, int mode) {
+    if (!ctxs || !n_ctx || !starts || !ctxs[0] || !n_iter_min || !n_iter_max) return PORRT_ERR_INVALID;
+    for (uint32_t q = 0; q < n_ctx; ++q) if (!ctxs[q]) return PORRT_ERR_INVALID;
+    std::vector<SamplerState> s0(n_ctx);
+    std::vector<uint64_t> tag0(n_ctx);
+    for (uint32_t q = 0; q < n_ctx; ++q) { s0[q] = SamplerState(*ctxs[q]); tag0[q] = ctxs[q]->results_tag; }
+    const int r = grow_batch_parts(ctxs, n_ctx, starts, max_step, search_radius, n_iter_min, n_iter_max, batch_K, mode);
+    if (r < 0)
+        for (uint32_t q = 0; q < n_ctx; ++q) {
+            porrt_ctx *x = ctxs[q];
+            if (x->results_tag == tag0[q]) continue;           // refused before this context was begun on: untouched
+            s0[q].restore(*x);
+            x->have_results = false;
+            x->batch_leader = nullptr;
+            for (porrt_ctx *m : x->batch_members) if (m && m->batch_leader == x) m->batch_leader = nullptr;      // (a sub-batch of the call that had ended well)
+            x->batch_members.clear();
+        }
+    return r;
 }
 
 int porrt_grow_batch_each(porrt_ctx *const *ctxs, uint32_t n_ctx, const double *starts, double max_step, double search_radius, const uint64_t *n_iter_min,
@@ -5015,6 +5042,10 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "nn_wg_waves")) *value = c->opt_nn_wg_waves;
     else if (!strcmp(name, "commit_flat")) *value = c->opt_commit_flat;
     else if (!strcmp(name, "cand_cap")) *value = c->opt_cand_cap;                     // (grown by a call whose lists overflowed: the call was replayed)
+    else if (!strcmp(name, "edge_per_node")) *value = (int64_t)c->edge_per_node;       // (test seam; likewise grown by a call whose edge pool overflowed)
+    else if (!strcmp(name, "tie_pool_ids")) *value = (int64_t)c->tie_pool_ids;         // (test seam; 0 = the default pool; likewise grown when set)
+    else if (!strcmp(name, "tie_pooled_ids")) *value = (int64_t)c->counters.pool_n;    // last growth (its last attempt): ids that deferred ties asked the pool for
+    else if (!strcmp(name, "tie_records")) *value = (int64_t)c->counters.pend_cnt;     //   and the records they asked for
     else if (!strcmp(name, "dp_wide_rows")) *value = (int64_t)c->opt_dp_wide_rows;
     else if (!strcmp(name, "dp_levels")) *value = c->dp.valid ? (int64_t)c->dp.levels : 0;          // levels of the last layered costs (0: the general sweeps ran)
     else if (!strcmp(name, "tamp_streams")) *value = c->opt_tamp_streams;
@@ -5041,6 +5072,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return PORRT_ERR_INVALID;
     if (!strcmp(name, "profile")) c->opt_profile = value != 0;
     else if (!strcmp(name, "cand_cap")) c->opt_cand_cap = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(value, 1 << 26));
+    else if (!strcmp(name, "edge_per_node")) { if (value < 1 || value > 65536) { c->set_err("edge_per_node: 1 .. 65536"); return PORRT_ERR_INVALID; } c->edge_per_node = (uint64_t)value; }
+    else if (!strcmp(name, "tie_pool_ids")) { if (value < 0 || value > (1ll << 30)) { c->set_err("tie_pool_ids: 0 (the default pool) or 1 .. 2^30"); return PORRT_ERR_INVALID; } c->tie_pool_ids = (uint64_t)value; }
     else if (!strcmp(name, "graph")) c->opt_graph = value != 0;
     else if (!strcmp(name, "group_lanes")) { if (value != -1 && value != 0 && value != 16 && value != 32 && value != 64) { c->set_err("group_lanes: -1 (auto), 0, 16, 32 or 64"); return PORRT_ERR_INVALID; } c->opt_group_req = (int)value; }
     else if (!strcmp(name, "dp_sweeps")) c->opt_dp_sweeps = value != 0;
