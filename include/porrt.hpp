@@ -766,6 +766,58 @@ public:
         return fetch(false, 0);
     }
     Policy refine_policy(size_t n_iterations) { return fetch(true, n_iterations); }
+    // plan() and refine_policy(refine_iterations) for many problems on this planner's map in one call (porrt_mm_plan_batch): plan p is
+    // what a fresh planner seeded with seeds[p] = (continuous, discrete) gives.  This planner's own last plan is left as it is.
+    // A plan without a policy (status != 0: 1 = the start has no finite expected cost) has no rows.
+    struct BatchedPlan {
+        uint8_t status = 0, refine_status = 0;
+        double expected_costs = 0.0, refined_costs = 0.0;
+        std::vector<State> states;                       // the refined policy's when refine_iterations > 0
+        std::vector<uint64_t> original_node_ids;         // the plan's own belief node ids
+        std::vector<int64_t> parents;                    // -1 = the root
+        std::vector<uint8_t> is_leaf;
+        porrt_mm_batch_plan counts{};
+    };
+    std::vector<BatchedPlan> plan_batch(const std::vector<State> &starts, const std::vector<BeliefState> &initial_belief_states,
+                                        const std::vector<std::pair<uint64_t, uint64_t>> &seeds, double max_step, double search_radius,
+                                        size_t n_iter_per_belief, size_t refine_iterations = 0) {
+        const size_t n = starts.size();
+        if (initial_belief_states.size() != n || seeds.size() != n) throw std::invalid_argument("plan_batch: one belief state and one seed pair per start");
+        const size_t nw = n ? initial_belief_states[0].size() : 0;
+        std::vector<double> s(2 * n), b(n * nw);
+        std::vector<uint64_t> cs(n), ds(n), off(n + 1);
+        for (size_t p = 0; p < n; ++p) {
+            if (initial_belief_states[p].size() != nw) throw std::invalid_argument("plan_batch: belief states of one length");
+            s[2 * p] = starts[p][0]; s[2 * p + 1] = starts[p][1];
+            std::copy(initial_belief_states[p].begin(), initial_belief_states[p].end(), b.begin() + p * nw);
+            cs[p] = seeds[p].first; ds[p] = seeds[p].second;
+        }
+        std::vector<uint8_t> st(n), rst(n);
+        std::vector<double> cost(n), rcost(n);
+        const int64_t total = porrt_mm_plan_batch(ctx_.get(), (uint32_t)n, s.data(), b.data(), cs.data(), ds.data(), (uint32_t)nw, max_step, search_radius,
+                                                  n_iter_per_belief, refine_iterations, off.data(), st.data(), cost.data(), rst.data(), rcost.data(), nullptr,
+                                                  nullptr, nullptr, nullptr, 0);
+        if (total < 0) ctx_.check((int)total);
+        std::vector<double> xy(2 * (size_t)total);
+        std::vector<uint64_t> oid((size_t)total);
+        std::vector<int64_t> par((size_t)total);
+        std::vector<uint8_t> leaf((size_t)total);
+        if (total) {
+            const int64_t r = porrt_mm_plan_batch_get_policies(ctx_.get(), nullptr, xy.data(), oid.data(), par.data(), leaf.data(), (uint64_t)total);
+            if (r < 0) ctx_.check((int)r);
+        }
+        std::vector<BatchedPlan> out(n);
+        for (size_t p = 0; p < n; ++p) {
+            BatchedPlan &o = out[p];
+            o.status = st[p]; o.refine_status = rst[p]; o.expected_costs = cost[p]; o.refined_costs = rcost[p];
+            for (uint64_t k = off[p]; k < off[p + 1]; ++k) {
+                o.states.push_back({xy[2 * k], xy[2 * k + 1]});
+                o.original_node_ids.push_back(oid[k]); o.parents.push_back(par[k]); o.is_leaf.push_back(leaf[k]);
+            }
+            ctx_.check(porrt_mm_plan_batch_get_plan(ctx_.get(), (uint32_t)p, &o.counts));
+        }
+        return out;
+    }
     const Context &context() const { return ctx_; }
 private:
     Policy fetch(bool refined, size_t n_iterations) {

@@ -450,6 +450,58 @@ struct porrt_plan_batch_info {
 };
 int      porrt_plan_batch_info(const porrt_ctx *leader, struct porrt_plan_batch_info *out);
 
+/* ---- MapShelfDomainTampPRM::plan (map_shelves_tamp_prm.rs:310-326) followed by PartialShortCut(refine_iterations), for n_plans
+ * problems on the context's map in one call: what main_baseline_comparison (main.rs:100-166) runs n_runs times per problem size, and
+ * what a replanner runs from many candidate starts and priors after an observation.  Plan p is, bit for bit, what a fresh context
+ * with the same raster, zones and sampler box gives after porrt_set_sampler(.., sampler_seeds[p]), porrt_set_discrete_seed(
+ * discrete_seeds[p]), porrt_mm_plan(starts + 2 p, priors + n_worlds p, ..) and, when refine_iterations > 0, porrt_mm_refine_policy:
+ * the extraction's status and the root's expected cost, the refinement's status and cost, the policy's states, ids (the plan's OWN
+ * belief node ids: mode offset + roadmap node), parents and leaf flags, the plan's whole cost vector and its counts.  The zone
+ * sampler is a fresh seed-0 stream per plan, as per single call.  sampler_seeds NULL: every plan clones the context's current
+ * continuous state; discrete_seeds NULL: every plan starts from a copy of the context's current discrete state (whatever
+ * sampler_seeds says).  The context's samplers are not advanced, and its last single
+ * growth, belief graph, costs and policy stay valid: a helper context owned by ctx carries the work.
+ * How: every mode of a plan clones the planner's never-advanced sampler, so the k-th random point of any mode of plan p is one
+ * point P_p[k].  The host runs grow_mm_prm's loop per plan (up to 8 threads) recording 32-bit codes -- an index into P_p or one of
+ * the explicit points (start, goal states, observation samples) -- and draws P_p once; the device expands them (k_mm_points), builds
+ * every roadmap of a pass in one launch sequence, the belief graph of the union, the expected costs, the policies from the plans'
+ * first nodes and their refinements.  Plans are taken in order into a pass while the sum of their roadmap nodes stays at or below
+ * option "mm_plan_batch_max_nodes" (default 2^23, at most 2^31 - 2); a plan that alone exceeds it is a pass of its own.  The answers
+ * do not depend on the cut.
+ * status[p]: that of porrt_mm_extract_policies, 0 .. 4 (1: the root has no finite cost: no rows, the other plans stand);
+ * refine_status / refined_costs (either may be NULL) as porrt_plan_belief_space_batch gives them (1 and +0.0 when refine_iterations is
+ * 0).  Policy p is rows pol_off[p] .. pol_off[p + 1].  pol_off (n_plans + 1), status and expected_costs are always written, the node
+ * arrays only if the total fits cap (cap = 0 sizes).  Returns the total number of policy nodes, or a negative error.
+ * PORRT_ERR_INVALID before any launch (porrt_last_error names the plan): n_plans outside 1 .. 65536, NULL starts / priors / pol_off /
+ * status / expected_costs, n_worlds not the context's, no shelf domain with zones, a prior that does not sum to 1 (summed as
+ * porrt_grow_mm_prm sums it), a belief without mass in a mode tree, a mode's belief that is not reachable.  PORRT_ERR_CAPACITY: an
+ * allocation that fails, or a pass of 2^31 nodes, 2^32 edges or 2^32 pairs; never a truncated answer.  A raster fault fails the call.
+ * porrt_mm_plan_batch_get_policies hands the kept answers out again; porrt_mm_plan_batch_get_expected_costs copies plan `plan`'s cost
+ * vector (its nodes doubles: what porrt_mm_get_expected_costs gives for the plan alone), plans of the LAST pass only;
+ * porrt_mm_plan_batch_get_plan the plan's counts (modes, transitions, reachable beliefs, roadmap nodes = belief nodes, forward roadmap
+ * edges, belief edges, final belief nodes) and the pass it ran in.  All four getters are an error before the first successful call.
+ * Info: sums over the passes, and milliseconds: the whole call, the host's mode trees and union tables, the points (uploads and
+ * k_mm_points), the roadmaps, the belief graph, the costs, the policy walk, the refinement -- host clock around stages that end in a
+ * synchronise -- and the HIP-event times those stages report themselves, summed. */
+int64_t  porrt_mm_plan_batch(porrt_ctx *ctx, uint32_t n_plans, const double *starts, const double *priors, const uint64_t *sampler_seeds,
+                             const uint64_t *discrete_seeds, uint32_t n_worlds, double max_step, double search_radius,
+                             uint64_t n_iter_per_belief, uint64_t refine_iterations, uint64_t *pol_off, uint8_t *status, double *expected_costs,
+                             uint8_t *refine_status, double *refined_costs, double *xy, uint64_t *original_ids, int64_t *parents,
+                             uint8_t *is_leaf, uint64_t cap);
+int64_t  porrt_mm_plan_batch_get_policies(const porrt_ctx *ctx, uint64_t *pol_off, double *xy, uint64_t *original_ids, int64_t *parents,
+                                          uint8_t *is_leaf, uint64_t cap);
+int      porrt_mm_plan_batch_get_expected_costs(const porrt_ctx *ctx, uint32_t plan, double *out);
+struct porrt_mm_batch_plan {
+    uint64_t modes, transitions, beliefs, nodes, forward_edges, belief_edges, finals, pass;
+};
+int      porrt_mm_plan_batch_get_plan(const porrt_ctx *ctx, uint32_t plan, struct porrt_mm_batch_plan *out);
+struct porrt_mm_plan_batch_info {
+    uint64_t plans, passes, modes, transitions, nodes, prefix_points, explicit_points, forward_edges, belief_edges, finals, policies_ok, policy_nodes,
+             upload_bytes;
+    double ms_wall, ms_host, ms_points, ms_roadmaps, ms_belief_graph, ms_costs, ms_policies, ms_refine, ms_device;
+};
+int      porrt_mm_plan_batch_info(const porrt_ctx *ctx, struct porrt_mm_plan_batch_info *out);
+
 /* ---- the other strategy: PTOPolicyRefiner::refine_solution(RefinmentStrategy::Reparent(radius)) (pto_policy_refiner.rs:209-322), of
  * one policy or many in one call, on the device.  Per piece of the policy (the decomposition above): build_tree makes the piece's path
  * a tree and adds belief-graph offsprings within `radius` of a path node; reparent pops the tree's nodes by distance from the root and

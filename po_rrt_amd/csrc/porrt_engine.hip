@@ -23,6 +23,7 @@
 #include "porrt_qmdp.hpp"
 #include "porrt_policy_graph.hpp"
 #include "porrt_join.hpp"
+#include "porrt_mm_recipe.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -73,6 +74,15 @@ struct Arena {
 #include "porrt_mmplan.hpp"
 #include "porrt_policy.hpp"
 #include "porrt_launch.hpp"
+
+// the device side of a roadmap pass (roadmaps_of_modes, porrt_mm_plan_batch): slots of the context's mm_scratch
+struct MmRoadmapDev {
+    double *x, *y;
+    uint32_t *base, *rank, *deg, *err, *seg, *aux, *sz, *tmp, *from, *to;
+    int *child, *par;
+    unsigned long long *off, *tot;
+    unsigned long long E;
+};
 
 struct porrt_ctx {
     int device = 0;
@@ -333,6 +343,8 @@ struct porrt_ctx {
     GrowScratch mm_scratch;                //   and the device buffers of roadmaps_of_modes, kept across calls
     int grow_mm_prm(const double start[2], const double *initial_belief, uint32_t n_worlds_in, double max_step, double search_radius, uint64_t n_iter_per_belief);
     int roadmaps_of_modes(double max_step, double search_radius);
+    int mm_roadmaps_prepare(size_t NT, size_t n_modes, size_t max_n, double max_step, double search_radius, MmRoadmapDev &d);
+    int mm_roadmaps_connect(MmRoadmapDev &d, size_t NT, size_t n_modes, hipEvent_t e0, hipEvent_t e1);
     int roadmap_of_points(const std::vector<double> &xy, double max_step, double search_radius, std::vector<uint32_t> &efrom, std::vector<uint32_t> &eto, double &dev_s);
     MmPlanState mmp;                       // porrt_mm_*: the mode-product belief graph, its expected costs and policy (porrt_mmplan.hpp)
     GrowScratch mmp_scratch;
@@ -345,11 +357,15 @@ struct porrt_ctx {
     uint64_t opt_tamp_arena_states = 1ull << 20;   // "tamp_arena_states": initial capacity of the A* search's path arena (states of 16 B; it grows)
     std::shared_ptr<void> plan_batch;      // porrt_plan_belief_space_batch (porrt_plan_batch.hpp): PlanBatchState -- the helper context that adopts a pass's union, the last call's answers
     uint64_t opt_plan_batch_max_belief_nodes = kJoinBeliefNodesDefault;    // "plan_batch_max_belief_nodes": members share a pass while their belief nodes stay at or below this
+    std::shared_ptr<void> mm_plan_batch;   // porrt_mm_plan_batch (porrt_mm_plan_batch.hpp): MmPlanBatchState -- the helper context that carries a pass's union, the last call's answers
+    uint64_t opt_mm_plan_batch_max_nodes = kMmBatchNodesDefault;           // "mm_plan_batch_max_nodes": plans share a pass while their roadmap nodes stay at or below this
     int opt_plan_batch_host_ranks = 1;     // "plan_batch_host_ranks": 1 = the union's kd pre-order ranks from the members' host kd-trees, 0 = made on the device (k_seg_kd_ranks, a workgroup per member)
     uint64_t n_final_belief_nodes = 0;     // final belief nodes of the last expected-cost run
     int opt_tamp_search = 0;               // "tamp_search": 0 = BranchAndBound; porrt_tamp_rrt_plan refuses 1 (AStar) and 2 (BranchAndBoundMultipleViewPoints), which have entry points of their own
     int mm_upload_roadmaps();
     int mm_build_belief_graph();
+    int mm_build_belief_graph_device(const std::vector<uint32_t> &tr_off, const std::vector<uint32_t> &tr_from, const std::vector<uint32_t> &tr_to,
+                                     const std::vector<unsigned long long> &pairs, double t0);
     int mm_compute_expected_costs();
     int mm_extract_policy();
     int64_t prm_plan_path(const double start[2], const double goal[2], double *path_xy, uint64_t cap);
@@ -2098,6 +2114,46 @@ int porrt_ctx::roadmaps_of_modes(double max_step, double search_radius) {
         }
         off[mm.modes.size()] = at; seg[mm.modes.size()] = (uint32_t)at;
     }
+    MmRoadmapDev d{};
+    int r = mm_roadmaps_prepare(NT, mm.modes.size(), max_n, max_step, search_radius, d);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(d.x, hx.data(), NT * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.y, hy.data(), NT * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.base, base.data(), NT * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d.seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, stream));
+    ScopedEvents<2> evs;
+    HIPCHK(evs.create());
+    if ((r = mm_roadmaps_connect(d, NT, mm.modes.size(), evs.e[0], evs.e[1]))) return r;
+    const unsigned long long E = d.E;
+    std::vector<uint32_t> hfrom(E), hto(E);
+    std::vector<unsigned long long> hoff(NT + 1);
+    uint32_t h_err = 0;
+    if (E) {
+        HIPCHK(hipMemcpyAsync(hfrom.data(), d.from, E * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(hto.data(), d.to, E * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipMemcpyAsync(hoff.data(), d.off, (NT + 1) * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&h_err, d.err, sizeof h_err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (h_err & ERR_RASTER) { set_err("raster access the reference would panic on (image::get_pixel out of range, door pixel without zone, two zones on one segment)"); return PORRT_ERR_RASTER; }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    mm.device_s += 1e-3 * (double)ms;
+    for (size_t mi = 0; mi < mm.modes.size(); ++mi) {
+        const size_t e0 = (size_t)hoff[off[mi]], e1 = (size_t)hoff[off[mi + 1]];
+        mm.modes[mi].efrom.assign(hfrom.begin() + e0, hfrom.begin() + e1);
+        mm.modes[mi].eto.assign(hto.begin() + e0, hto.begin() + e1);
+    }
+    mm.dev_edges = true;                                 // slots 0, 1, 6, 9 of mm_scratch: x, y, edge offsets, neighbours (porrt_mm_build_belief_graph)
+    return PORRT_OK;
+}
+
+// The device buffers of a roadmap pass over NT nodes in n_modes segments (the largest of max_n nodes), the raster, the radius table and
+// the run constants: what comes before the points are on the device.  The caller then fills d.x, d.y, d.base (every node's segment
+// start) and d.seg (n_modes + 1 segment starts) on the context's stream -- roadmaps_of_modes from the host, porrt_mm_plan_batch with
+// k_mm_points -- and calls mm_roadmaps_connect.
+int porrt_ctx::mm_roadmaps_prepare(size_t NT, size_t n_modes, size_t max_n, double max_step, double search_radius, MmRoadmapDev &d) {
     HIPCHK(d_radT2.reserve(max_n + 8)); HIPCHK(d_cnt.reserve(1)); HIPCHK(d_rc.reserve(1)); HIPCHK(d_cls.reserve(cls_bytes(W, H)));
     int r = layout_buffers();
     if (r) return r;
@@ -2112,58 +2168,36 @@ int porrt_ctx::roadmaps_of_modes(double max_step, double search_radius) {
     rc.rad_T2 = d_radT2.p;
     HIPCHK(hipMemcpyAsync(d_rc.p, &rc, sizeof rc, hipMemcpyHostToDevice, stream));
     GrowScratch &sc = mm_scratch;                        // kept by the context: the next call finds its buffers
-    double *dx = nullptr, *dy = nullptr;
-    uint32_t *dbase = nullptr, *drank = nullptr, *ddeg = nullptr, *derr = nullptr, *dtmp = nullptr, *dfrom = nullptr, *dto = nullptr, *dseg = nullptr, *daux = nullptr, *dsz = nullptr;
-    int *dchild = nullptr, *dpar = nullptr;
-    unsigned long long *doff = nullptr, *dtot = nullptr;
-    HIPCHK(sc.get(0, dx, NT)); HIPCHK(sc.get(1, dy, NT)); HIPCHK(sc.get(2, dbase, NT)); HIPCHK(sc.get(3, drank, NT)); HIPCHK(sc.get(4, ddeg, NT)); HIPCHK(sc.get(5, derr, 1));
-    HIPCHK(sc.get(6, doff, NT + 1)); HIPCHK(sc.get(7, dtot, (NT + kScanTile - 1) / kScanTile + 2));
-    HIPCHK(sc.get(11, dseg, seg.size())); HIPCHK(sc.get(12, dchild, 2 * NT)); HIPCHK(sc.get(13, dpar, NT)); HIPCHK(sc.get(14, daux, NT)); HIPCHK(sc.get(15, dsz, NT));
-    HIPCHK(hipMemcpyAsync(dx, hx.data(), NT * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dy, hy.data(), NT * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dbase, base.data(), NT * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(dseg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(derr, 0, sizeof(uint32_t), stream));
+    HIPCHK(sc.get(0, d.x, NT)); HIPCHK(sc.get(1, d.y, NT)); HIPCHK(sc.get(2, d.base, NT)); HIPCHK(sc.get(3, d.rank, NT)); HIPCHK(sc.get(4, d.deg, NT)); HIPCHK(sc.get(5, d.err, 1));
+    HIPCHK(sc.get(6, d.off, NT + 1)); HIPCHK(sc.get(7, d.tot, (NT + kScanTile - 1) / kScanTile + 2));
+    HIPCHK(sc.get(11, d.seg, n_modes + 1)); HIPCHK(sc.get(12, d.child, 2 * NT)); HIPCHK(sc.get(13, d.par, NT)); HIPCHK(sc.get(14, d.aux, NT)); HIPCHK(sc.get(15, d.sz, NT));
+    return PORRT_OK;
+}
+
+// The roadmaps of the segments of device-resident points: kd ranks, count, scan, fill, order, between the two events.  Leaves the
+// forward edges on the device (d.off, d.from, d.to, d.E of them) and the error word in d.err for the caller to fetch with whatever
+// else it downloads; it synchronises once, for the edge count.
+int porrt_ctx::mm_roadmaps_connect(MmRoadmapDev &d, size_t NT, size_t n_modes, hipEvent_t e0, hipEvent_t e1) {
+    GrowScratch &sc = mm_scratch;
+    HIPCHK(hipMemsetAsync(d.err, 0, sizeof(uint32_t), stream));
     MmConst p{};
-    p.NT = (uint32_t)NT; p.x = dx; p.y = dy; p.base = dbase; p.rank = drank; p.rad_T2 = d_radT2.p; p.deg = ddeg; p.edge_off = doff; p.err = derr;
-    ScopedEvents<2> evs;
-    HIPCHK(evs.create());
-    HIPCHK(hipEventRecord(evs.e[0], stream));
+    p.NT = (uint32_t)NT; p.x = d.x; p.y = d.y; p.base = d.base; p.rank = d.rank; p.rad_T2 = d_radT2.p; p.deg = d.deg; p.edge_off = d.off; p.err = d.err;
+    HIPCHK(hipEventRecord(e0, stream));
     const dim3 wgrid((unsigned)((NT + 3) / 4)), block(256);
     // every mode's kd-tree and the pre-order ranks of its nodes (what orders a node's neighbours), a workgroup per mode
-    hipLaunchKernelGGL(k_seg_kd_ranks, dim3((unsigned)mm.modes.size()), block, 0, stream, (const double *)dx, (const double *)dy, (const uint32_t *)dseg, dchild, dpar, daux, dsz, drank);
+    hipLaunchKernelGGL(k_seg_kd_ranks, dim3((unsigned)n_modes), block, 0, stream, (const double *)d.x, (const double *)d.y, (const uint32_t *)d.seg, d.child, d.par, d.aux, d.sz, d.rank);
     hipLaunchKernelGGL(k_mm_connect<false>, wgrid, block, 0, stream, (const RunConst *)d_rc.p, p);
-    bg_scan(ddeg, NT, dtot, doff, stream);
+    bg_scan(d.deg, NT, d.tot, d.off, stream);
     unsigned long long E = 0;
-    HIPCHK(hipMemcpyAsync(&E, doff + NT, sizeof E, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&E, d.off + NT, sizeof E, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (E >= 0xFFFFFFFFull) { set_err("multi-modal PRM: edge list too long"); return PORRT_ERR_CAPACITY; }
-    HIPCHK(sc.get(8, dtmp, E)); HIPCHK(sc.get(9, dfrom, E)); HIPCHK(sc.get(10, dto, E));
-    p.tmp = dtmp; p.efrom = dfrom; p.eto = dto;
+    HIPCHK(sc.get(8, d.tmp, E)); HIPCHK(sc.get(9, d.from, E)); HIPCHK(sc.get(10, d.to, E));
+    p.tmp = d.tmp; p.efrom = d.from; p.eto = d.to;
     hipLaunchKernelGGL(k_mm_connect<true>, wgrid, block, 0, stream, (const RunConst *)d_rc.p, p);
     hipLaunchKernelGGL(k_mm_order, wgrid, block, 0, stream, p);
-    HIPCHK(hipEventRecord(evs.e[1], stream));
-    std::vector<uint32_t> hfrom(E), hto(E);
-    std::vector<unsigned long long> hoff(NT + 1);
-    uint32_t h_err = 0;
-    if (E) {
-        HIPCHK(hipMemcpyAsync(hfrom.data(), dfrom, E * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(hto.data(), dto, E * 4, hipMemcpyDeviceToHost, stream));
-    }
-    HIPCHK(hipMemcpyAsync(hoff.data(), doff, (NT + 1) * 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(&h_err, derr, sizeof h_err, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    if (h_err & ERR_RASTER) { set_err("raster access the reference would panic on (image::get_pixel out of range, door pixel without zone, two zones on one segment)"); return PORRT_ERR_RASTER; }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-    mm.device_s += 1e-3 * (double)ms;
-    for (size_t mi = 0; mi < mm.modes.size(); ++mi) {
-        const size_t e0 = (size_t)hoff[off[mi]], e1 = (size_t)hoff[off[mi + 1]];
-        mm.modes[mi].efrom.assign(hfrom.begin() + e0, hfrom.begin() + e1);
-        mm.modes[mi].eto.assign(hto.begin() + e0, hto.begin() + e1);
-    }
-    mm.dev_edges = true;                                 // slots 0, 1, 6, 9 of mm_scratch: x, y, edge offsets, neighbours (porrt_mm_build_belief_graph)
+    HIPCHK(hipEventRecord(e1, stream));
+    d.E = E;
     return PORRT_OK;
 }
 
@@ -2396,8 +2430,18 @@ int porrt_ctx::mm_build_belief_graph() {
         pairs.insert(pairs.end(), tr.pairs.begin(), tr.pairs.end());
         if (!(s.support[tr.to] < s.support[tr.from])) s.support_shrinks = false;
     }
-    const uint64_t P = pairs.size() / 2;
-    tr_off[T] = (uint32_t)P;
+    tr_off[T] = (uint32_t)(pairs.size() / 2);
+    return mm_build_belief_graph_device(tr_off, tr_from, tr_to, pairs, t0);
+}
+
+// The device half of the build, on the tables of mmp (NT, n_modes, nw, mode_off, mode_bid, beliefs, finals, support_shrinks) and the
+// transitions given: the roadmaps' nodes and forward edges are in mm_scratch (slots 0, 1, 6, 9).  porrt_mm_plan_batch calls it on the
+// union of a pass's plans, whose tables it lays end to end itself.
+int porrt_ctx::mm_build_belief_graph_device(const std::vector<uint32_t> &tr_off, const std::vector<uint32_t> &tr_from, const std::vector<uint32_t> &tr_to,
+                                            const std::vector<unsigned long long> &pairs, double t0) {
+    MmPlanState &s = mmp;
+    const uint64_t NT = s.NT, P = pairs.size() / 2;
+    const uint32_t nw = s.nw, M = (uint32_t)s.n_modes, T = (uint32_t)tr_from.size();
     if (P + NT >= 0xFFFFFFFFull) { set_err("mm_build_belief_graph: too many observation pairs"); return PORRT_ERR_CAPACITY; }
     if (!mm.dev_edges) { const int r = mm_upload_roadmaps(); if (r) return r; }
     double *dx = nullptr, *dy = nullptr;
@@ -3310,6 +3354,7 @@ static BatchRows porrt_batch_rows(porrt_ctx *const *ctxs, uint32_t n, uint32_t q
 #include "porrt_tamp_viewpoints.hpp"
 #include "porrt_tamp_astar.hpp"
 #include "porrt_plan_batch.hpp"
+#include "porrt_mm_plan_batch.hpp"
 
 extern "C" {
 
@@ -3340,6 +3385,7 @@ void porrt_destroy(porrt_ctx *c) {
     if (!c) return;
     c->tamp.reset();                          // the TAMP planner's worker contexts and buffers
     c->plan_batch.reset();                    // porrt_plan_belief_space_batch's helper context and answers
+    c->mm_plan_batch.reset();                 // porrt_mm_plan_batch's
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (hipStream_t st : c->sub_streams) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -4522,6 +4568,55 @@ int64_t porrt_mm_plan(porrt_ctx *c, const double start[2], const double *initial
         return (int)c->mm_policy.original.size();
     });
 }
+// ---- MapShelfDomainTampPRM::plan and PartialShortCut for many problems on the context's map in one call (porrt_mm_plan_batch.hpp)
+int64_t porrt_mm_plan_batch(porrt_ctx *c, uint32_t n_plans, const double *starts, const double *priors, const uint64_t *sampler_seeds, const uint64_t *discrete_seeds,
+                            uint32_t n_worlds, double max_step, double search_radius, uint64_t n_iter_per_belief, uint64_t refine_iterations, uint64_t *pol_off,
+                            uint8_t *status, double *expected_costs, uint8_t *refine_status, double *refined_costs, double *xy, uint64_t *original_ids,
+                            int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    if (!c) return PORRT_ERR_INVALID;
+    return abi_guard([&]() -> int64_t {
+        return mm_plan_batch(c, n_plans, starts, priors, sampler_seeds, discrete_seeds, n_worlds, max_step, search_radius, n_iter_per_belief, refine_iterations, pol_off,
+                             status, expected_costs, refine_status, refined_costs, xy, original_ids, parents, is_leaf, cap);
+    });
+}
+static const MmPlanBatchState *mm_plan_batch_answers(const porrt_ctx *c, const char *who) {
+    if (!c) return nullptr;
+    const MmPlanBatchState *S = (const MmPlanBatchState *)c->mm_plan_batch.get();
+    if (!S || !S->valid) { const_cast<porrt_ctx *>(c)->set_err(std::string(who) + ": no answers: call porrt_mm_plan_batch first"); return nullptr; }
+    return S;
+}
+int64_t porrt_mm_plan_batch_get_policies(const porrt_ctx *c, uint64_t *pol_off, double *xy, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap) {
+    const MmPlanBatchState *S = mm_plan_batch_answers(c, "mm_plan_batch_get_policies");
+    if (!S) return PORRT_ERR_INVALID;
+    return mm_plan_batch_copy_out(*S, pol_off, nullptr, nullptr, nullptr, nullptr, xy, original_ids, parents, is_leaf, cap);
+}
+int porrt_mm_plan_batch_get_expected_costs(const porrt_ctx *c, uint32_t plan, double *out) {
+    const MmPlanBatchState *S = mm_plan_batch_answers(c, "mm_plan_batch_get_expected_costs");
+    if (!S || !out) return PORRT_ERR_INVALID;
+    porrt_ctx *m = const_cast<porrt_ctx *>(c);
+    const size_t n_last = S->last_noff.size() ? S->last_noff.size() - 1 : 0;
+    if (plan < S->last_first || plan - S->last_first >= n_last || !S->helper->mm_costs_current()) {
+        m->set_err("mm_plan_batch_get_expected_costs: plan " + std::to_string(plan) + " is not of the last pass (its costs are gone)");
+        return PORRT_ERR_INVALID;
+    }
+    const uint32_t q = plan - S->last_first;
+    HIPCHK_CTX(m, hipSetDevice(c->device));
+    HIPCHK_CTX(m, hipMemcpy(out, S->helper->mmp.dp.d_dist + S->last_noff[q], (S->last_noff[q + 1] - S->last_noff[q]) * sizeof(double), hipMemcpyDeviceToHost));
+    return PORRT_OK;
+}
+int porrt_mm_plan_batch_get_plan(const porrt_ctx *c, uint32_t plan, struct porrt_mm_batch_plan *out) {
+    const MmPlanBatchState *S = mm_plan_batch_answers(c, "mm_plan_batch_get_plan");
+    if (!S || !out) return PORRT_ERR_INVALID;
+    if (plan >= S->plans.size()) { const_cast<porrt_ctx *>(c)->set_err("mm_plan_batch_get_plan: no plan " + std::to_string(plan) + " in the last call"); return PORRT_ERR_INVALID; }
+    *out = S->plans[plan];
+    return PORRT_OK;
+}
+int porrt_mm_plan_batch_info(const porrt_ctx *c, struct porrt_mm_plan_batch_info *out) {
+    const MmPlanBatchState *S = mm_plan_batch_answers(c, "mm_plan_batch_info");
+    if (!S || !out) return PORRT_ERR_INVALID;
+    *out = S->info;
+    return PORRT_OK;
+}
 // seconds of the last steps: grow (porrt_mm_plan only), build, build on the device, expected costs, on the device, policy walk, refine, on the device
 int porrt_mm_get_plan_seconds(const porrt_ctx *c, double *out, uint32_t n) {
     if (!c || !out) return PORRT_ERR_INVALID;
@@ -5060,6 +5155,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "policy_max_nodes")) *value = c->opt_policy_max_nodes;
     else if (!strcmp(name, "plan_batch_max_belief_nodes")) *value = (int64_t)c->opt_plan_batch_max_belief_nodes;
     else if (!strcmp(name, "plan_batch_host_ranks")) *value = c->opt_plan_batch_host_ranks;
+    else if (!strcmp(name, "mm_plan_batch_max_nodes")) *value = (int64_t)c->opt_mm_plan_batch_max_nodes;
     else if (!strcmp(name, "refine_short_lds")) *value = c->opt_refine_short_lds ? 1 : 0;
     else if (!strcmp(name, "reparent_max_tree_nodes")) *value = c->opt_reparent_max_tree_nodes;
     else if (!strcmp(name, "reparent_max_pops_per_node")) *value = c->opt_reparent_max_pops_per_node;
@@ -5119,6 +5215,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "policy_max_nodes")) { if (value < 1 || value > (int64_t)kPolMaxNodesLimit) { c->set_err("policy_max_nodes: 1 .. 2^24"); return PORRT_ERR_INVALID; } c->opt_policy_max_nodes = (uint32_t)value; }
     else if (!strcmp(name, "plan_batch_max_belief_nodes")) { if (value < 1 || value > (int64_t)kJoinBeliefNodesLimit) { c->set_err("plan_batch_max_belief_nodes: 1 .. 2^32 - 2"); return PORRT_ERR_INVALID; } c->opt_plan_batch_max_belief_nodes = (uint64_t)value; }
     else if (!strcmp(name, "plan_batch_host_ranks")) c->opt_plan_batch_host_ranks = value != 0;
+    else if (!strcmp(name, "mm_plan_batch_max_nodes")) { if (value < 1 || value > (int64_t)kMmBatchNodesLimit) { c->set_err("mm_plan_batch_max_nodes: 1 .. 2^31 - 2"); return PORRT_ERR_INVALID; } c->opt_mm_plan_batch_max_nodes = (uint64_t)value; }
     else if (!strcmp(name, "policy_graph_max_pivots")) { if (value < 0 || value > (int64_t)0x7FFFFFFF) { c->set_err("policy_graph_max_pivots: 0 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_policy_graph_max_pivots = (uint32_t)value; }
     else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }

@@ -56,6 +56,8 @@ SYMBOLS = [
     "porrt_bg_reparent_policies", "porrt_bg_get_reparented_policies", "porrt_bg_reparent_policy", "porrt_reparent_policies",
     "porrt_reparent_policies_info",
     "porrt_plan_belief_space_batch", "porrt_plan_batch_get_policies", "porrt_plan_batch_get_expected_costs", "porrt_plan_batch_info",
+    "porrt_mm_plan_batch", "porrt_mm_plan_batch_get_policies", "porrt_mm_plan_batch_get_expected_costs", "porrt_mm_plan_batch_get_plan",
+    "porrt_mm_plan_batch_info",
 ]
 
 
@@ -144,6 +146,19 @@ class PlanBatchInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("members", "passes", "graph_nodes", "graph_edges", "beliefs", "belief_nodes", "belief_edges",
                                           "final_belief_nodes", "policies_ok", "policy_nodes")] + \
                [(k, C.c_double) for k in ("ms_wall", "ms_join", "ms_edge_order", "ms_belief_graph", "ms_costs", "ms_policies", "ms_refine", "ms_device")]
+
+
+class MmBatchPlan(C.Structure):
+    """struct porrt_mm_batch_plan"""
+    _fields_ = [(k, C.c_uint64) for k in ("modes", "transitions", "beliefs", "nodes", "forward_edges", "belief_edges", "finals", "pass_")]
+
+
+class MmPlanBatchInfo(C.Structure):
+    """struct porrt_mm_plan_batch_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("plans", "passes", "modes", "transitions", "nodes", "prefix_points", "explicit_points", "forward_edges",
+                                          "belief_edges", "finals", "policies_ok", "policy_nodes", "upload_bytes")] + \
+               [(k, C.c_double) for k in ("ms_wall", "ms_host", "ms_points", "ms_roadmaps", "ms_belief_graph", "ms_costs", "ms_policies", "ms_refine",
+                                          "ms_device")]
 
 
 class TreeDeviceView(C.Structure):
@@ -340,6 +355,12 @@ def load_library():
     sig("porrt_plan_batch_get_policies", C.c_int64, vp, vp, vp, vp, vp, vp, C.c_uint64)
     sig("porrt_plan_batch_get_expected_costs", C.c_int, vp, C.c_uint32, vp)
     sig("porrt_plan_batch_info", C.c_int, vp, C.POINTER(PlanBatchInfo))
+    sig("porrt_mm_plan_batch", C.c_int64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
+        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64)
+    sig("porrt_mm_plan_batch_get_policies", C.c_int64, vp, vp, vp, vp, vp, vp, C.c_uint64)
+    sig("porrt_mm_plan_batch_get_expected_costs", C.c_int, vp, C.c_uint32, vp)
+    sig("porrt_mm_plan_batch_get_plan", C.c_int, vp, C.c_uint32, C.POINTER(MmBatchPlan))
+    sig("porrt_mm_plan_batch_info", C.c_int, vp, C.POINTER(MmPlanBatchInfo))
     _LIB = L
     return L
 
@@ -1263,6 +1284,60 @@ class Engine:
             (xy, oid, par, leaf), cost = self.mm_refine_policy(refine_iterations)
             return (oid, par, leaf, xy), cost
         return self.mm_extract_policy()
+
+    # ---- MapShelfDomainTampPRM::plan + PartialShortCut for many problems on this engine's map in one device call (porrt_mm_plan_batch)
+    def plan_mm_prm_batch_raw(self, starts, priors, max_step, search_radius, n_iter_per_belief, refine_iterations=0, sampler_seeds=None,
+                              discrete_seeds=None):
+        """porrt_mm_plan_batch as arrays: pol_off [n + 1], status [n], expected costs [n], refine status [n], refined costs [n], and the
+        policies' rows (states [total, 2], the plans' own belief node ids, parents, leaf flags) from porrt_mm_plan_batch_get_policies.
+        sampler_seeds / discrete_seeds None: every plan clones the engine's current continuous / discrete sampler state."""
+        starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 2)
+        n = starts.shape[0]
+        priors = np.ascontiguousarray(priors, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1))
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        seeds = [None if v is None else np.ascontiguousarray(v, dtype=np.uint64) for v in (sampler_seeds, discrete_seeds)]
+        for v in seeds:
+            if v is not None and v.shape != (n,):
+                raise PorrtError(-1, "plan_mm_prm_batch: one seed per plan")
+        off, status, cost = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        rstatus, rcost = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
+        total = self._chk(int(self._l.porrt_mm_plan_batch(self._c, n, p(starts), p(priors), p(seeds[0]), p(seeds[1]), priors.shape[1], float(max_step),
+                                                          float(search_radius), int(n_iter_per_belief), int(refine_iterations), p(off), p(status), p(cost),
+                                                          p(rstatus), p(rcost), None, None, None, None, 0)))
+        xy, oid, par, leaf = np.zeros((total, 2)), np.zeros(total, dtype=np.uint64), np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.uint8)
+        if total:
+            self._chk(int(self._l.porrt_mm_plan_batch_get_policies(self._c, None, p(xy), p(oid), p(par), p(leaf), total)))
+        return off, status[:n], cost[:n], rstatus[:n], rcost[:n], xy, oid, par, leaf
+
+    def plan_mm_prm_batch(self, starts, priors, max_step, search_radius, n_iter_per_belief, refine_iterations=0, sampler_seeds=None, discrete_seeds=None):
+        """One dict per plan: status, cost (the root's expected cost), refine_status, refined_cost and policy = (belief node ids, parents,
+        leaf flags, states), the refined policy when refine_iterations > 0; a plan with nonzero status has an empty policy."""
+        off, status, cost, rstatus, rcost, xy, oid, par, leaf = self.plan_mm_prm_batch_raw(starts, priors, max_step, search_radius, n_iter_per_belief,
+                                                                                           refine_iterations, sampler_seeds, discrete_seeds)
+        out = []
+        for q in range(len(status)):
+            a, b = int(off[q]), int(off[q + 1])
+            out.append(dict(status=int(status[q]), cost=float(cost[q]), refine_status=int(rstatus[q]), refined_cost=float(rcost[q]),
+                            policy=(oid[a:b], par[a:b], leaf[a:b], xy[a:b])))
+        return out
+
+    def mm_plan_batch_info(self):
+        """porrt_mm_plan_batch_info of the last plan_mm_prm_batch: counts summed over the passes and milliseconds per stage"""
+        i = MmPlanBatchInfo()
+        self._chk(self._l.porrt_mm_plan_batch_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in MmPlanBatchInfo._fields_}
+
+    def mm_plan_batch_plan(self, plan):
+        """porrt_mm_plan_batch_get_plan: modes, transitions, beliefs, nodes, forward_edges, belief_edges, finals and pass of one plan"""
+        i = MmBatchPlan()
+        self._chk(self._l.porrt_mm_plan_batch_get_plan(self._c, int(plan), C.byref(i)))
+        return {k.rstrip("_"): getattr(i, k) for k, _ in MmBatchPlan._fields_}
+
+    def mm_plan_batch_expected_costs(self, plan):
+        """the expected costs of one plan of the last pass of the last plan_mm_prm_batch (what mm_expected_costs gives for the plan alone)"""
+        d = np.zeros(self.mm_plan_batch_plan(plan)["nodes"])
+        self._chk(self._l.porrt_mm_plan_batch_get_expected_costs(self._c, int(plan), d.ctypes.data_as(C.c_void_p)))
+        return d
 
     def mm_plan_seconds(self):
         v = np.zeros(8)
