@@ -924,8 +924,55 @@ public:
         }
         const int64_t r = porrt_tamp_rrt_plan_astar_batch(ctx_.get(), (uint32_t)n, st.data(), pr.data(), seeds.empty() ? nullptr : seeds.data(),
                                                           (uint32_t)nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius_, batch_K);
+        return read_batch<AstarBatch>(r, n, nw);
+    }
+    // plan(.., BranchAndBound) for many (start, prior, seed, discrete seed) on this planner's map in one device call
+    // (porrt_tamp_rrt_plan_batch): plan p is, bit for bit, plan(.., BranchAndBound) alone on a fresh planner
+    // whose continuous sampler is seeded seeds[p] and whose discrete sampler discrete_seeds[p] (seeds empty: this planner's seed for
+    // every plan; discrete_seeds empty: seeds[p]).  This planner's own samplers are left alone.  A plan without a path has status
+    // PORRT_ERR_NO_PATH in its record and an empty policy; it does not throw.
+    struct Batch {
+        std::vector<Policy> policies;
+        std::vector<porrt_tamp_batch_plan> plans;
+        std::vector<uint64_t> pruned;          // per plan: children not pushed
+        size_t n_ok = 0;
+    };
+    Batch plan_batch(const std::vector<State> &starts, const std::vector<BeliefState> &priors, const std::vector<uint64_t> &seeds,
+                     const std::vector<uint64_t> &discrete_seeds, double max_step, double search_radius, size_t n_iter_min, size_t n_iter_max,
+                     uint32_t batch_K = 128) {
+        if (starts.size() != priors.size() || (!seeds.empty() && seeds.size() != starts.size()) ||
+            (!discrete_seeds.empty() && discrete_seeds.size() != starts.size()))
+            throw std::runtime_error("MapShelfDomainTampRRT::plan_batch: one start, one prior and (if any) one seed and one discrete seed per plan");
+        const size_t n = starts.size(), nw = n ? priors[0].size() : 0;
+        std::vector<double> st, pr;
+        for (size_t p = 0; p < n; ++p) {
+            if (priors[p].size() != nw) throw std::runtime_error("MapShelfDomainTampRRT::plan_batch: priors of different sizes");
+            st.insert(st.end(), starts[p].begin(), starts[p].end());
+            pr.insert(pr.end(), priors[p].begin(), priors[p].end());
+        }
+        const int64_t r = porrt_tamp_rrt_plan_batch(ctx_.get(), (uint32_t)n, st.data(), pr.data(), seeds.empty() ? nullptr : seeds.data(),
+                                                    discrete_seeds.empty() ? nullptr : discrete_seeds.data(), (uint32_t)nw, max_step, search_radius,
+                                                    n_iter_min, n_iter_max, goal_radius_, batch_K);
+        Batch out = read_batch<Batch>(r, n, nw);
+        out.pruned.resize(n);
+        for (size_t p = 0; p < n; ++p) ctx_.check(porrt_tamp_batch_get_pruned(ctx_.get(), (uint32_t)p, &out.pruned[p]));
+        return out;
+    }
+    porrt_tamp_astar_info astar_info() const { porrt_tamp_astar_info i; ctx_.check(porrt_tamp_rrt_get_astar_info(ctx_.get(), &i)); return i; }
+    porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
+    porrt_tamp_viewpoints_info viewpoints_info() const { porrt_tamp_viewpoints_info i; ctx_.check(porrt_tamp_rrt_get_viewpoints_info(ctx_.get(), &i)); return i; }
+    const Context &context() const { return ctx_; }
+private:
+    Policy read_policy(int64_t r, size_t nw) {
+        return read_policy(r, nw, [&](double *xy, int64_t *par, uint8_t *leaf, double *bel, uint64_t cap, double *cost) {
+            return porrt_tamp_rrt_policy(ctx_.get(), xy, par, leaf, bel, cap, cost);
+        });
+    }
+    // the records and policies of the batch call that returned r, of either search
+    template <class BatchT>
+    BatchT read_batch(int64_t r, size_t n, size_t nw) {
         if (r < 0) ctx_.check((int)r);
-        AstarBatch out;
+        BatchT out;
         out.n_ok = (size_t)r;
         out.policies.resize(n);
         out.plans.resize(n);
@@ -938,16 +985,6 @@ public:
             });
         }
         return out;
-    }
-    porrt_tamp_astar_info astar_info() const { porrt_tamp_astar_info i; ctx_.check(porrt_tamp_rrt_get_astar_info(ctx_.get(), &i)); return i; }
-    porrt_tamp_info info() const { porrt_tamp_info i; ctx_.check(porrt_tamp_rrt_get_info(ctx_.get(), &i)); return i; }
-    porrt_tamp_viewpoints_info viewpoints_info() const { porrt_tamp_viewpoints_info i; ctx_.check(porrt_tamp_rrt_get_viewpoints_info(ctx_.get(), &i)); return i; }
-    const Context &context() const { return ctx_; }
-private:
-    Policy read_policy(int64_t r, size_t nw) {
-        return read_policy(r, nw, [&](double *xy, int64_t *par, uint8_t *leaf, double *bel, uint64_t cap, double *cost) {
-            return porrt_tamp_rrt_policy(ctx_.get(), xy, par, leaf, bel, cap, cost);
-        });
     }
     // fetch(xy, parents, is_leaf, beliefs, cap, expected_cost): porrt_tamp_rrt_policy, or a batch plan's porrt_tamp_batch_policy
     template <class Fetch>

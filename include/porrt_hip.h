@@ -1036,6 +1036,47 @@ int64_t  porrt_tamp_batch_policy(const porrt_ctx *ctx, uint32_t plan, double *xy
                                  uint64_t cap, double *expected_cost);
 int64_t  porrt_tamp_batch_astar_nodes(const porrt_ctx *ctx, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, double *priority,
                                       uint64_t cap);
+/* ---- many branch-and-bound plans on one map in one call.  Plan p is the search of porrt_tamp_rrt_plan
+ * ("tamp_search" 0) from starts[p] with prior priors[p].  Its root stream seed is seeds[p] (NULL: the context's sampler seed for
+ * every plan) and its per-edge streams are splitmix64 of that seed and the zone prefix, as under "tamp_streams" 1.  Its shuffles
+ * draw from a discrete sampler of the plan's own, seeded discrete_seeds[p] (NULL: seeds[p], which is what porrt_set_sampler(.., seed)
+ * leaves in a fresh context).  Map, zones, sampler box and every numeric parameter are shared.
+ * Needs "tamp_streams" 1 and "tamp_search" 0 (PORRT_ERR_INVALID otherwise, the latter with porrt_tamp_rrt_plan's message).  Every
+ * plan of a batch is then, bit for bit, the plan porrt_tamp_rrt_plan gives alone on a fresh context whose sampler seed is seeds[p]
+ * and whose discrete seed is discrete_seeds[p], at the same "tamp_wave" with "tamp_streams" 1: policy states, parents, leaf flags
+ * and beliefs, search_cost, expected_cost, zone_order, search_nodes, queries, waves and pruned -- whatever else is in the batch,
+ * whatever "tamp_pool" is and wherever a chunk is cut.  The searches run in the rounds of the A* batch above: every live plan
+ * closes its last wave and pops its next ("tamp_wave" nodes per plan), and the children of all plans, in plan then node then zone
+ * order, go through porrt_grow_batch in chunks of "tamp_pool" rows; their paths share one arena ("tamp_arena_states": its first
+ * capacity; it is never reclaimed during a call), and the chains of all plans that hold a leaf are shortcut in one launch.  A caller
+ * of large batches sets "tamp_wave" 8 and "tamp_pool" 2048: narrower waves leave the rows empty even with 100 plans, wider ones
+ * run up to 2.3 times the queries (DESIGN.md section 28 has the measurements).
+ * Returns the number of plans that found a policy (0 is no error), or a negative code.  PORRT_ERR_NO_PATH is per plan and follows
+ * the single plan's rule: the plan fails at the first child of its wave, in the sequential order, whose observation query or
+ * (observation found) pickup query has no path; fail_node is that child's id, search_nodes the nodes made up to and including that
+ * wave.  A failed plan's queries and waves are not pinned (the single plan stops mid-chunk, a batch cannot).  The other plans go
+ * on.  Everything else fails the call and names the plan in porrt_last_error where one is to blame: PORRT_ERR_INVALID before
+ * anything runs (a prior whose sum is not within 0.001 of 1 -- zero entries are allowed here --, n_worlds != zones, n_plans outside
+ * 1..65536, NULL starts or priors), PORRT_ERR_CAPACITY from the arena or a path slot, device errors, and whatever
+ * porrt_grow_batch answers.
+ * The call leaves the context's continuous stream, its goal-independent state and ITS DISCRETE SAMPLER alone -- unlike
+ * porrt_tamp_rrt_plan, whose shuffles move the context's discrete sampler.  It replaces the context's last single plan
+ * (porrt_tamp_rrt_policy then answers as after a failed plan) and the last batch of either kind.  The per-plan results come through
+ * porrt_tamp_batch_get_plan (speculated = 0) and porrt_tamp_batch_policy above, `pruned` through porrt_tamp_batch_get_pruned
+ * (porrt_tamp_batch_plan has no room for it; 0 after an A* batch).  porrt_tamp_rrt_get_info holds the call's totals (queries,
+ * waves = rounds of the driver, search_nodes, pruned, the seconds, pool) and porrt_tamp_rrt_get_astar_info the arena figures. */
+int64_t  porrt_tamp_rrt_plan_batch(porrt_ctx *ctx, uint32_t n_plans, const double *starts /* n x 2 */,
+                                   const double *priors /* n x n_worlds */, const uint64_t *seeds /* n, or NULL */,
+                                   const uint64_t *discrete_seeds /* n, or NULL */, uint32_t n_worlds, double max_step,
+                                   double search_radius, uint64_t n_iter_min, uint64_t n_iter_max, double goal_radius, uint32_t batch_K);
+int      porrt_tamp_batch_get_pruned(const porrt_ctx *ctx, uint32_t plan, uint64_t *pruned);
+/* the search nodes of plan `plan` of the last porrt_tamp_rrt_plan_batch in id order (a node has its id from the moment it is made;
+ * also of a failed plan: every node made up to and including the failing wave): parents (-1 = root), targets (zone; -1 = root), ec
+ * (0 for a child whose query found no path), pushed (1 = it went onto the stack, 0 = pruned or never closed).  Returns their count;
+ * with cap below it nothing is written.  PORRT_ERR_INVALID after an A* batch, as porrt_tamp_batch_astar_nodes is after a
+ * branch-and-bound batch. */
+int64_t  porrt_tamp_batch_bnb_nodes(const porrt_ctx *ctx, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, uint8_t *pushed,
+                                    uint64_t cap);
 /* porrt_tamp_shortcut_paths through the shortcut's device-resident input form: the paths are first put into the A* search's arena
  * and reach the shortcut's staging planes by k_astar_chain, as the winning chain of a plan does.  Same result, bit for bit. */
 int      porrt_tamp_shortcut_paths_resident(porrt_ctx *ctx, const double *xy, const uint64_t *offsets, uint64_t n_paths, double *out);

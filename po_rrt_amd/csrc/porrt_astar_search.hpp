@@ -1,7 +1,7 @@
 // porrt_astar_search.hpp -- what is one plan's own in the TAMP-RRT A* search (porrt_tamp_astar.hpp, DESIGN.md sections 23 and 25):
 // the node and expansion tables, the belief table, the queue, the replay, the selection of a wave, taking a child's record back and
-// the failure rule -- and the rounds that drive many such searches in lockstep.  Plain C++, no HIP: tests/astar_search_check.cpp
-// builds it on its own under the sanitizers, with a stub in place of the device.
+// the failure rule -- and the rounds that drive many searches of one type in lockstep (these, or porrt_bnb_search.hpp's).  Plain
+// C++, no HIP: tests/astar_search_check.cpp builds it on its own under the sanitizers, with a stub in place of the device.
 //
 // A search never grows anything itself.  Per round it REPLAYS (pops while the top of its queue is a leaf or already has its
 // children; popping gives the children their ids and pushes them), then SELECTS up to W expandable queue entries and hands out
@@ -116,7 +116,11 @@ public:
     }
 
     const double *belief_row(uint32_t row) const { return beliefs.data() + (size_t)row * nw; }
+    // what the driver's device side asks of an edge, whichever search it drives
     uint32_t zone_of(const Edge &ed) const { return exps[(size_t)ed.e].zone[ed.i]; }
+    double edge_rp(const Edge &ed) const { return exps[(size_t)ed.e].rp; }
+    const double *edge_belief(const Edge &ed) const { return belief_row(exps[(size_t)ed.e].belief); }
+    unsigned long long edge_remaining(const Edge &ed) const { return nodes[(size_t)ed.u].remaining & ~(1ull << zone_of(ed)); }
     bool expandable(uint64_t id) const { return nodes[(size_t)id].remaining && nodes[(size_t)id].kids < 0; }
 
     // pops while the top is a leaf or has its children; ids are given here
@@ -205,21 +209,25 @@ private:
     }
 };
 
-// The driver of n searches, in rounds: every live search replays; solved, failed and exhausted ones leave; the rest select their
-// wave; all selected edges, in plan then node then zone order, are cut into chunks of `chunk` rows wherever the cut falls, and
-// expand(edges, e0, m, out) fills out[0 .. m) for edges[e0 .. e0 + m) -- a negative return ends the run with that code -- before
-// the records go back to their searches.  `rounds` counts the rounds that expanded something.
-template <class Expand>
-static int run(std::vector<Search> &S, uint32_t wave, size_t chunk, uint64_t &rounds, Expand expand) {
+// The driver of n searches of one type, in rounds: every live search replays; solved, failed and exhausted ones leave; the rest
+// select their wave; all selected edges, in plan then node then zone order, are cut into chunks of `chunk` rows wherever the cut
+// falls, and expand(edges, e0, m, out) fills out[0 .. m) for edges[e0 .. e0 + m) -- a negative return ends the run with that code --
+// before the records go back to their searches.  `rounds` counts the rounds that expanded something; a round in which the live
+// searches selected nothing to expand (a branch and bound that popped only leaves) just goes on to the next replay.
+// SearchT (Search here, porrt_bnb::Search): State with kLive, replay(), select(wave, plan, edges), take(edge, record).
+template <class SearchT, class Expand>
+static int run(std::vector<SearchT> &S, uint32_t wave, size_t chunk, uint64_t &rounds, Expand expand) {
     std::vector<Edge> edges;
     std::vector<ChildRecord> out;
     if (wave == 0) wave = 1;
     if (chunk == 0) chunk = 1;
     while (true) {
         edges.clear();
+        bool live = false;
         for (uint32_t p = 0; p < S.size(); ++p)
-            if (S[p].replay() == Search::kLive) S[p].select(wave, p, edges);
-        if (edges.empty()) return 0;
+            if (S[p].replay() == SearchT::kLive) { live = true; S[p].select(wave, p, edges); }
+        if (!live) return 0;
+        if (edges.empty()) continue;
         ++rounds;
         for (size_t e0 = 0; e0 < edges.size(); e0 += chunk) {
             const uint32_t m = (uint32_t)std::min(chunk, edges.size() - e0);

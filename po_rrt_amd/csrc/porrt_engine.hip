@@ -3353,6 +3353,7 @@ static BatchRows porrt_batch_rows(porrt_ctx *const *ctxs, uint32_t n, uint32_t q
 #include "porrt_tamp.hpp"
 #include "porrt_tamp_viewpoints.hpp"
 #include "porrt_tamp_astar.hpp"
+#include "porrt_tamp_bnb_batch.hpp"
 #include "porrt_plan_batch.hpp"
 #include "porrt_mm_plan_batch.hpp"
 
@@ -4974,8 +4975,19 @@ int64_t porrt_tamp_batch_policy(const porrt_ctx *cc, uint32_t plan, double *xy, 
     return (int64_t)n;
 }
 
-int64_t porrt_tamp_batch_astar_nodes(const porrt_ctx *cc, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap) {
+// the last batch's plan as the caller of one search's getter may see it: nullptr (and the reason) after a batch of the other search
+static const AstarBatchPlan *astar_batch_plan_of(const porrt_ctx *cc, uint32_t plan, bool bnb) {
     const AstarBatchPlan *B = astar_batch_plan(cc, plan);
+    if (B && ((const AstarState *)((const TampState *)cc->tamp.get())->astar.get())->batch_bnb != bnb) {
+        const_cast<porrt_ctx *>(cc)->set_err(bnb ? "tamp batch: the last batch was an A* batch: its nodes come through porrt_tamp_batch_astar_nodes"
+                                                 : "tamp astar batch: the last batch was a branch-and-bound batch: its nodes come through porrt_tamp_batch_bnb_nodes");
+        return nullptr;
+    }
+    return B;
+}
+
+int64_t porrt_tamp_batch_astar_nodes(const porrt_ctx *cc, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, double *priority, uint64_t cap) {
+    const AstarBatchPlan *B = astar_batch_plan_of(cc, plan, false);
     if (!B) return PORRT_ERR_INVALID;
     const uint64_t n = B->node_parents.size();
     if (cap < n) return (int64_t)n;
@@ -4983,6 +4995,40 @@ int64_t porrt_tamp_batch_astar_nodes(const porrt_ctx *cc, uint32_t plan, int64_t
     if (targets) memcpy(targets, B->node_targets.data(), n * sizeof(int32_t));
     if (ec) memcpy(ec, B->node_ec.data(), n * sizeof(double));
     if (priority) memcpy(priority, B->node_priority.data(), n * sizeof(double));
+    return (int64_t)n;
+}
+
+// ---- many branch-and-bound plans on one map in one call (tamp_plan_bnb_batch, porrt_tamp_bnb_batch.hpp)
+int64_t porrt_tamp_rrt_plan_batch(porrt_ctx *c, uint32_t n_plans, const double *starts, const double *priors, const uint64_t *seeds,
+                                  const uint64_t *discrete_seeds, uint32_t n_worlds, double max_step, double search_radius, uint64_t n_iter_min,
+                                  uint64_t n_iter_max, double goal_radius, uint32_t batch_K) {
+    if (!c) return PORRT_ERR_INVALID;
+    int64_t out = 0;
+    const int r = abi_guard([&]() {
+        const int64_t n = tamp_plan_bnb_batch(c, n_plans, starts, priors, seeds, discrete_seeds, n_worlds, max_step, search_radius, n_iter_min,
+                                              n_iter_max, goal_radius, batch_K);
+        out = n;
+        return n < 0 ? (int)n : (int)PORRT_OK;
+    });
+    return r < 0 ? r : out;
+}
+
+int porrt_tamp_batch_get_pruned(const porrt_ctx *cc, uint32_t plan, uint64_t *pruned) {
+    const AstarBatchPlan *B = astar_batch_plan(cc, plan);
+    if (!B || !pruned) return PORRT_ERR_INVALID;
+    *pruned = B->pruned;
+    return PORRT_OK;
+}
+
+int64_t porrt_tamp_batch_bnb_nodes(const porrt_ctx *cc, uint32_t plan, int64_t *parents, int32_t *targets, double *ec, uint8_t *pushed, uint64_t cap) {
+    const AstarBatchPlan *B = astar_batch_plan_of(cc, plan, true);
+    if (!B) return PORRT_ERR_INVALID;
+    const uint64_t n = B->node_parents.size();
+    if (cap < n) return (int64_t)n;
+    if (parents) memcpy(parents, B->node_parents.data(), n * sizeof(int64_t));
+    if (targets) memcpy(targets, B->node_targets.data(), n * sizeof(int32_t));
+    if (ec) memcpy(ec, B->node_ec.data(), n * sizeof(double));
+    if (pushed) memcpy(pushed, B->node_pushed.data(), n);
     return (int64_t)n;
 }
 

@@ -19,6 +19,8 @@
 //      device (k_best_path), the pickup queries grow in a second batch, and the children are pushed in the sequential order.
 // Both modes draw the shuffles from the lead's discrete sampler (porrt_set_discrete_seed; RRT growth never draws from it), which
 // runs on across plans.
+// Many such plans on one map in one call, each with a discrete sampler of its own, are porrt_tamp_bnb_batch.hpp (DESIGN.md
+// section 28); the search cut into operations a driver of many can call is porrt_bnb_search.hpp.
 #pragma once
 
 #include <algorithm>
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "porrt_astar_search.hpp"
+#include "porrt_bnb_search.hpp"
 
 namespace {
 
@@ -36,7 +39,7 @@ constexpr uint32_t kTampPathSlot = 1024;      // states of one query's best path
 constexpr uint32_t kTampShortcutIterations = 100;   // map_shelves_tamp_rrt.rs:581
 
 // the stream and belief arithmetic of a search edge (splitmix64, edge_seed, normalize, transition_probability, child_belief) is that
-// of the host-only porrt_astar_search.hpp: one statement of each for the three searches
+// of the host-only porrt_astar_search.hpp, the shuffles are those of porrt_bnb_search.hpp: one statement of each for the searches
 
 struct TampNode {
     int32_t target = -1;
@@ -294,17 +297,7 @@ static int tamp_shortcut_device(porrt_ctx *c, TampState &T, std::vector<double> 
     return PORRT_OK;
 }
 
-static std::vector<uint32_t> tamp_shuffled(const std::vector<uint32_t> &v, Pcg64 &rng) {     // :20-32
-    std::vector<uint32_t> to = v, out;
-    out.reserve(v.size());
-    while (!to.empty()) {
-        const size_t i = (size_t)rng.gen_range_usize(to.size());
-        out.push_back(to[i]);
-        to[i] = to.back();                       // swap_remove
-        to.pop_back();
-    }
-    return out;
-}
+static std::vector<uint32_t> tamp_shuffled(const std::vector<uint32_t> &v, Pcg64 &rng) { return porrt_bnb::shuffled(v, rng); }     // :20-32
 
 // Policy::compute_expected_costs_to_goals (common.rs:131-154) from node 0: sum over the children in order of
 // p * q * cost + rec(p * q, child), q = transition_probability (common.rs:187-190), cost = norm2 (pto_graph.rs:150).
@@ -427,9 +420,7 @@ static int tamp_fail(porrt_ctx *c, TampState &T, int64_t node, int32_t zone, int
 
 // a fresh shuffle of `remaining` without zone t: one per child, from the discrete sampler (the branch-and-bound searches only)
 static std::vector<uint32_t> tamp_remaining_without(const std::vector<uint32_t> &remaining, uint32_t t, Pcg64 &rng) {
-    std::vector<uint32_t> out;
-    for (uint32_t z : tamp_shuffled(remaining, rng)) if (z != t) out.push_back(z);
-    return out;
+    return porrt_bnb::remaining_without(remaining, t, rng);
 }
 
 static std::vector<int64_t> tamp_chain(const std::vector<TampNode> &nodes, int64_t leaf) {     // root .. leaf

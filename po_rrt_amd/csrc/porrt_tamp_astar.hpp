@@ -35,10 +35,11 @@
 // 2 x depth paths of the winning chain into the shortcut's staging planes, where k_tamp_shortcut runs on them unchanged.
 //
 // What is one plan's own -- tables, queue, replay, selection, the failure rule -- is porrt_astar::Search, and the rounds are
-// porrt_astar::run (porrt_astar_search.hpp, host only).  This file is the device side of those rounds (AstarRun) and the two
-// callers: tamp_plan_astar, the driver with one plan, and tamp_plan_astar_batch, the same driver over many
-// plans on one map whose rows share the batches, the arena, one k_astar_children per chunk and one k_astar_chain /
-// k_tamp_shortcut at the end.  With per-edge streams a plan of a batch is, bit for bit, the plan it is alone.
+// porrt_astar::run (porrt_astar_search.hpp, host only).  This file is the device side of those rounds (SearchRun, a template over
+// the search type: AstarRun here, the branch and bound's in porrt_tamp_bnb_batch.hpp) and the two callers: tamp_plan_astar, the
+// driver with one plan, and tamp_plan_astar_batch, the same driver over many plans on one map whose rows
+// share the batches, the arena, one k_astar_children per chunk and one k_astar_chain / k_tamp_shortcut at the end.  With per-edge
+// streams a plan of a batch is, bit for bit, the plan it is alone.
 #pragma once
 
 #include "porrt_astar_search.hpp"
@@ -49,14 +50,16 @@ using AstarSearch = porrt_astar::Search;
 using AstarEdge = porrt_astar::Edge;
 using AstarChildRecord = porrt_astar::ChildRecord;
 
-struct AstarBatchPlan {                        // one plan of the last porrt_tamp_rrt_plan_astar_batch
+struct AstarBatchPlan {                        // one plan of the last batch call, of either search
     porrt_tamp_batch_plan rec;
+    uint64_t pruned = 0;                       // branch and bound: children not pushed
     std::vector<double> xy, beliefs;           // its policy (empty for a failed plan)
     std::vector<int64_t> parents;
     std::vector<uint8_t> leaf;
     std::vector<int64_t> node_parents;         // its search nodes, in id order
     std::vector<int32_t> node_targets;
-    std::vector<double> node_ec, node_priority;
+    std::vector<double> node_ec, node_priority;      // priority: A* only
+    std::vector<uint8_t> node_pushed;          // branch and bound only
 };
 
 struct AstarState {
@@ -70,6 +73,7 @@ struct AstarState {
     std::vector<double> ec, priority;
     std::vector<AstarBatchPlan> batch;         // the last batch call's plans
     uint32_t batch_nw = 0;
+    bool batch_bnb = false;                    // the last batch was porrt_tamp_rrt_plan_batch (porrt_tamp_bnb_batch.hpp)
     AstarState() { memset(&info, 0, sizeof info); }
     ~AstarState() {
         if (arena) (void)hipFree(arena);
@@ -118,13 +122,17 @@ static int astar_gather(porrt_ctx *c, TampState &T, AstarState &A, porrt_ctx *co
 // The device side of one call over the searches S: the arena and what the kernels read call-wide (begin), the records of a chunk
 // of edges of any of the searches (expand_chunk, and expand_sequential for the one plan on the lead's own stream), and the end of
 // every search that found its leaf (policies).  `named`: errors name the plan they came from (a batch).
-struct AstarRun {
+// SearchT is porrt_astar::Search or porrt_bnb::Search (porrt_tamp_bnb_batch.hpp): nodes with ox, oy, h, ec, target, belief and the
+// arena offsets of their two paths, belief_row(), chain(), and per edge zone_of, edge_rp, edge_belief, edge_remaining.
+template <class SearchT>
+struct SearchRun {
     porrt_ctx *c;
     TampFrame &F;
     TampState &T;
     AstarState &A;
-    std::vector<AstarSearch> &S;
+    std::vector<SearchT> &S;
     bool named;
+    const char *tag = "tamp astar";            // what the errors begin with
     uint32_t nw = 0;
     hipStream_t st = nullptr;
     uint32_t *d_cur = nullptr;
@@ -151,8 +159,8 @@ struct AstarRun {
     }
 
     int bad_record(uint32_t status, uint32_t plan) {
-        c->set_err((status == kAstarSlot ? "tamp astar: a best path longer than its slot of " + std::to_string(kTampPathSlot) + " states"
-                                         : std::string("tamp astar: the best-cost scratch of a query overflowed")) + of_plan(plan));
+        c->set_err(std::string(tag) + (status == kAstarSlot ? ": a best path longer than its slot of " + std::to_string(kTampPathSlot) + " states"
+                                                            : std::string(": the best-cost scratch of a query overflowed")) + of_plan(plan));
         return PORRT_ERR_CAPACITY;
     }
 
@@ -165,18 +173,16 @@ struct AstarRun {
         uint32_t rows = 0;                                     // belief rows uploaded: one per run of edges of one expansion
         for (uint32_t i = 0; i < m; ++i) {
             const AstarEdge &ed = edges[e0 + i];
-            const AstarSearch &s = S[ed.plan];
-            const porrt_astar::Node &u = s.nodes[(size_t)ed.u];
-            const porrt_astar::Expansion &E = s.exps[(size_t)ed.e];
-            if (i == 0 || edges[e0 + i - 1].plan != ed.plan || edges[e0 + i - 1].e != ed.e) {
-                bl.insert(bl.end(), s.belief_row(E.belief), s.belief_row(E.belief) + nw);
+            const SearchT &s = S[ed.plan];
+            if (i == 0 || edges[e0 + i - 1].plan != ed.plan || edges[e0 + i - 1].u != ed.u) {      // the children of a node share a belief
+                bl.insert(bl.end(), s.edge_belief(ed), s.edge_belief(ed) + nw);
                 ++rows;
             }
             AstarChildIn &a = in[i];
-            a.parent_ec = u.ec; a.rp = E.rp;
-            a.remaining = u.remaining & ~(1ull << E.zone[ed.i]);
+            a.parent_ec = s.nodes[(size_t)ed.u].ec; a.rp = s.edge_rp(ed);
+            a.remaining = s.edge_remaining(ed);
             a.obs_row = i; a.pick_row = pick_row[i];
-            a.belief_row = rows - 1; a.target = E.zone[ed.i];
+            a.belief_row = rows - 1; a.target = s.zone_of(ed);
         }
         AstarChildIn *d_in = nullptr;
         double *d_bl = nullptr;
@@ -225,8 +231,8 @@ struct AstarRun {
     // tamp_streams = 0 (one plan, one node per round): the node's children one after the other on the lead.  The node is the top of
     // the queue and is popped next, so the first query without a path ends the plan.
     int expand_sequential(const std::vector<AstarEdge> &edges, size_t e0, uint32_t m, AstarChildRecord *out) {
-        const AstarSearch &s = S[edges[e0].plan];
-        const porrt_astar::Node &u = s.nodes[(size_t)edges[e0].u];
+        const SearchT &s = S[edges[e0].plan];
+        const auto &u = s.nodes[(size_t)edges[e0].u];
         BestPath *d_obs = nullptr, *d_pick = nullptr;
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
@@ -257,10 +263,10 @@ struct AstarRun {
         BestPath *d_obs = nullptr, *d_pick = nullptr;
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarObs, d_obs, m));
         HIPCHK_CTX(c, T.scratch.get(kSlotAstarPick, d_pick, m));
-        auto node_of = [&](size_t e) -> const porrt_astar::Node & { return S[edges[e].plan].nodes[(size_t)edges[e].u]; };
+        auto node_of = [&](size_t e) -> const auto & { return S[edges[e].plan].nodes[(size_t)edges[e].u]; };
         auto zone_of = [&](size_t e) { return S[edges[e].plan].zone_of(edges[e]); };
         auto grown = [&](int r) {
-            if (r < 0 && named) c->set_err("tamp astar batch: the growth of a chunk holding plans " + std::to_string(edges[e0].plan) + " .. " +
+            if (r < 0 && named) c->set_err(std::string(tag) + " batch: the growth of a chunk holding plans " + std::to_string(edges[e0].plan) + " .. " +
                                            std::to_string(edges[e0 + m - 1].plan) + " failed: " + c->err);
             return r;
         };
@@ -303,7 +309,7 @@ struct AstarRun {
         for (uint32_t p : solved) {
             chains.push_back(S[p].chain());
             for (int64_t k : chains.back()) {
-                const porrt_astar::Node &n = S[p].nodes[(size_t)k];
+                const auto &n = S[p].nodes[(size_t)k];
                 off.push_back(off.back() + n.obs_len);
                 src.paths.push_back({n.obs_off, n.obs_len, 0u, 0u});
                 off.push_back(off.back() + n.pick_len);
@@ -319,7 +325,7 @@ struct AstarRun {
         expected.assign(solved.size(), 0.0);
         size_t at = 0;
         for (size_t i = 0; i < solved.size(); ++i) {
-            const AstarSearch &s = S[solved[i]];
+            const SearchT &s = S[solved[i]];
             std::vector<int32_t> target;
             std::vector<const double *> belief;
             for (int64_t k : chains[i]) { target.push_back(s.nodes[(size_t)k].target); belief.push_back(s.belief_row(s.nodes[(size_t)k].belief)); }
@@ -330,7 +336,10 @@ struct AstarRun {
     }
 };
 
-static uint32_t astar_zone_order(const AstarSearch &s, uint32_t *order) {
+using AstarRun = SearchRun<AstarSearch>;
+
+template <class SearchT>
+static uint32_t astar_zone_order(const SearchT &s, uint32_t *order) {
     uint32_t n = 0;
     for (int64_t k : s.chain()) if (s.nodes[(size_t)k].parent >= 0) order[n++] = (uint32_t)s.nodes[(size_t)k].target;
     return n;
@@ -421,6 +430,7 @@ static int64_t tamp_plan_astar_batch(porrt_ctx *c, uint32_t n_plans, const doubl
     A.parents.clear(); A.targets.clear(); A.ec.clear(); A.priority.clear();      // the last single plan is replaced
     A.batch.clear();
     A.batch_nw = nw;
+    A.batch_bnb = false;
 
     std::vector<AstarSearch> S(n_plans);
     for (uint32_t p = 0; p < n_plans; ++p) S[p].begin(starts + 2 * (size_t)p, priors + (size_t)p * nw, nw, seeds ? seeds[p] : c->s_seed);

@@ -48,6 +48,7 @@ SYMBOLS = [
     "porrt_solutions", "porrt_tamp_rrt_plan_viewpoints", "porrt_tamp_rrt_get_viewpoints_info",
     "porrt_tamp_rrt_plan_astar", "porrt_tamp_rrt_get_astar_info", "porrt_tamp_astar_nodes", "porrt_tamp_shortcut_paths_resident",
     "porrt_tamp_rrt_plan_astar_batch", "porrt_tamp_batch_get_plan", "porrt_tamp_batch_policy", "porrt_tamp_batch_astar_nodes",
+    "porrt_tamp_rrt_plan_batch", "porrt_tamp_batch_get_pruned", "porrt_tamp_batch_bnb_nodes",
     "porrt_qmdp_plan", "porrt_qmdp_get_costs", "porrt_qmdp_info", "porrt_qmdp_react", "porrt_qmdp_costs",
     "porrt_qmdp_policy_graph", "porrt_qmdp_policy_graph_get", "porrt_qmdp_policy_graph_info", "porrt_policy_graph",
     "porrt_bg_extract_policies", "porrt_bg_get_policies", "porrt_mm_extract_policies", "porrt_mm_get_policies", "porrt_extract_policies",
@@ -320,6 +321,10 @@ def load_library():
     sig("porrt_tamp_batch_get_plan", C.c_int, vp, C.c_uint32, C.POINTER(TampBatchPlan))
     sig("porrt_tamp_batch_policy", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))
     sig("porrt_tamp_batch_astar_nodes", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
+    sig("porrt_tamp_rrt_plan_batch", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double,
+        C.c_double, C.c_uint64, C.c_uint64, C.c_double, C.c_uint32)
+    sig("porrt_tamp_batch_get_pruned", C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint64))
+    sig("porrt_tamp_batch_bnb_nodes", C.c_int64, vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
     sig("porrt_solutions", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
         C.c_void_p, C.c_uint64)
     sig("porrt_best_paths", C.c_int, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, _u64p, _f64p)
@@ -568,6 +573,10 @@ class Engine:
         sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
         self._chk(self._l.porrt_tamp_rrt_plan_astar_batch(self._c, n, st.ctypes.data, pr.ctypes.data, None if sd is None else sd.ctypes.data,
                                                            nw, max_step, search_radius, n_iter_min, n_iter_max, goal_radius, batch_K))
+        return self._tamp_batch_plans(n, nw)
+
+    def _tamp_batch_plans(self, n, nw, pruned=False):
+        """the per-plan dicts of the last batch call of either search; pruned: the plan's own count replaces the call's"""
         call = self.tamp_info()
         call.update(self.tamp_astar_info())
         out = []
@@ -578,6 +587,10 @@ class Engine:
             d.update({k: getattr(rec, k) for k in ("status", "fail_node", "fail_zone", "fail_query", "search_cost", "expected_cost",
                                                    "search_nodes", "queries", "waves", "speculated")})
             d["zone_order"] = [int(rec.zone_order[k]) for k in range(rec.n_order)]
+            if pruned:
+                own = C.c_uint64(0)
+                self._chk(self._l.porrt_tamp_batch_get_pruned(self._c, p, C.byref(own)))
+                d["pruned"] = own.value
             if rec.status == 0:
                 m = int(rec.policy_nodes)
                 xy, par = np.zeros((m, 2)), np.zeros(m, dtype=np.int64)
@@ -595,6 +608,36 @@ class Engine:
         ec, pr = np.zeros(n), np.zeros(n)
         self._chk(self._l.porrt_tamp_batch_astar_nodes(self._c, plan, par.ctypes.data, tgt.ctypes.data, ec.ctypes.data, pr.ctypes.data, n))
         return dict(parents=par, targets=tgt, ec=ec, priority=pr)
+
+    def plan_tamp_rrt_batch(self, starts, priors, seeds=None, discrete_seeds=None, max_step=0.1, search_radius=2.0, n_iter_min=2500,
+                            n_iter_max=10000, goal_radius=0.05, batch_K=128):
+        """porrt_tamp_rrt_plan_batch: many branch-and-bound plans on this engine's map in one call, plan p from starts[p] with prior
+        priors[p], root stream seed seeds[p] (None: the engine's sampler seed for every plan) and a discrete sampler of its own
+        seeded discrete_seeds[p] (None: seeds[p]).  Each plan is, bit for bit, what plan_tamp_rrt gives alone on a fresh engine
+        seeded alike at the same tamp_wave.  Returns one dict per plan in the shape plan_tamp_rrt_astar_batch returns: `status` (0,
+        or -10 for a plan that found no path: it has no policy arrays, and fail_* say where it failed), search_cost, expected_cost,
+        search_nodes, queries, waves, pruned, zone_order and fail_* are the plan's own (speculated is 0); the seconds, streams, wave,
+        pool and the arena figures are the call's.  The engine's own samplers are left alone.  A failed plan does not raise; every
+        other failure raises PorrtError for the whole call."""
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, 2))
+        n = st.shape[0]
+        pr = np.ascontiguousarray(np.asarray(priors, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1)))
+        nw = pr.shape[1]
+        sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(n))
+        ds = None if discrete_seeds is None else np.ascontiguousarray(np.asarray(discrete_seeds, dtype=np.uint64).reshape(n))
+        self._chk(self._l.porrt_tamp_rrt_plan_batch(self._c, n, st.ctypes.data, pr.ctypes.data, None if sd is None else sd.ctypes.data,
+                                                     None if ds is None else ds.ctypes.data, nw, max_step, search_radius, n_iter_min,
+                                                     n_iter_max, goal_radius, batch_K))
+        return self._tamp_batch_plans(n, nw, pruned=True)
+
+    def tamp_batch_bnb_nodes(self, plan):
+        """the search nodes of plan `plan` of the last plan_tamp_rrt_batch in id order (of a failed plan: those made up to and
+        including the failing wave): dict(parents, targets, ec, pushed)"""
+        n = self._chk(self._l.porrt_tamp_batch_bnb_nodes(self._c, plan, None, None, None, None, 0))
+        par, tgt = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        ec, pushed = np.zeros(n), np.zeros(n, dtype=np.uint8)
+        self._chk(self._l.porrt_tamp_batch_bnb_nodes(self._c, plan, par.ctypes.data, tgt.ctypes.data, ec.ctypes.data, pushed.ctypes.data, n))
+        return dict(parents=par, targets=tgt, ec=ec, pushed=pushed)
 
     def tamp_viewpoints_info(self):
         i = TampViewpointsInfo()
