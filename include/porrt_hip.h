@@ -681,7 +681,9 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * 0 = every level wide), "conn_wg_waves" (the group kernels' connect pass: 1, default: k_conn2 with one wave per workgroup, so that a finished
  * wave gives back its slot and its LDS lists whatever its neighbours still do, and the step's single workgroups -- page filing, goal-point copies,
  * goal path -- as k_conn2_riders, a kernel of its own on the same stream; 4 = everything in one kernel of four-wave workgroups, k_conn2_wg4),
- * "conn_riders_first" (1, default: k_conn2_riders before k_conn2 of its step; 0 = after it), "nn_wg_waves" (waves per workgroup of k_nn2: 4,
+ * "conn_riders_first" (1, default: k_conn2_riders before k_conn2 of its step; 0 = after it), "riders_fast" (developer option: 1, default: the
+ * step's single workgroups in their short forms -- the page filing and the goal path with their loads in one round trip, the goal copies' radius
+ * search by all four waves; 0 = the forms they had beside a long connect pass; 0 or 1), "nn_wg_waves" (waves per workgroup of k_nn2: 4,
  * default, or 1), "commit_flat" (the group kernels' rewire commit: 1, default: a workgroup takes 128 consecutive samples of its row and runs one
  * lane per candidate record -- k_nn2's commit workgroups and k_commit_flat after the last step; 0 = a group of lanes per sample, k_commit2 after
  * the last step), "compact_rows" (1, default: a
@@ -704,7 +706,8 @@ int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
  * this context led -- needed the whole kd structure, which was built after its steps), "kd_lca_steps" (this context's own need: 1 + the
  * last step with a tie that took that structure, 0 = none), "compactions" (how often the last batch this context led gathered the
  * members still running), "n_heavy" (samples of this context's last grow with more hits than their LDS list holds: served by a whole wave
- * from the lists in memory), "conn_wg_waves", "conn_riders_first", "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed),
+ * from the lists in memory), "conn_wg_waves", "conn_riders_first", "riders_fast", "tim0" .. "tim15" (developer builds with -DPORRT_TIMING: the phase
+ * timers of this context's last growth, 0 otherwise), "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed),
  * "edge_per_node" and "tie_pool_ids" (likewise: what the last attempt ran with; tie_pool_ids stays 0 while the default pool is in force),
  * "tie_pooled_ids" and "tie_records" (the last growth's last attempt: node ids that deferred ties asked the pool for, and their records), "dp_wide_rows", "dp_levels" and "dp_wide_levels" (the levels of the last layered expected costs, 0 when the
  * general sweeps ran; bit k of the mask: level k -- k-th smallest number of possible worlds -- ran the wide kernel) */

@@ -191,6 +191,11 @@ struct Counters {
 #define PORRT_TACC_H(rc, slot) do {} while (0)
 #define PORRT_TACC_S(rc, slot) do {} while (0)
 #endif
+// =5: the roles of k_conn2_riders, per row and window of steps (RIDERS_MARK, porrt_group.hpp); the samples' timers are off (they share the slots)
+#if defined(PORRT_TIMING) && PORRT_TIMING == 5
+#undef PORRT_TACC_B
+#define PORRT_TACC_B(rc, slot) do { (void)t__0; } while (0)
+#endif
 
 struct BestCost {
     unsigned long long cost_bits;   // f64 bits of the best cost (+inf bits when there is no final node)
@@ -801,9 +806,12 @@ __device__ __forceinline__ double disc_radius(double bound_d2, double qx, double
 //   flat     the box covers so many regions that streaming the id-ordered arrays nx/ny is cheaper
 //   sparse   few nodes per region (young tree): lane <-> region, slot by slot
 //   pages    lane <-> slot, region after region (four pages in flight)
+// share, nshare: the calling wave is one of nshare that scan the same disc together (the clone workgroup): it visits its share of the flat
+// array's blocks, of a sparse group's regions and of the pages (page j of the group's r-th region goes to wave (r + j) % nshare), so that
+// every node is visited by exactly one of them.  Constants at every other call: one wave, everything.
 template <class Visit>
 __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double qx, double qy, double rho, uint32_t N, uint32_t lane, Visit visit,
-                                          uint32_t skip_region = 0xFFFFFFFFu) {
+                                          uint32_t skip_region = 0xFFFFFFFFu, uint32_t share = 0u, uint32_t nshare = 1u) {
     int cx0, cy0, cx1, cy1;
     rep_cell(rc, qx - rho, qy - rho, kRG, cx0, cy0);
     rep_cell(rc, qx + rho, qy + rho, kRG, cx1, cy1);
@@ -811,7 +819,7 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
     const uint32_t w = uni((uint32_t)(cx1 - cx0 + 1)), nreg = w * uni((uint32_t)(cy1 - cy0 + 1));
     if (nreg * 16u > N) {
         auto gx = as_global(rc.nx), gy = as_global(rc.ny);
-        for (uint32_t j0 = 0; j0 < N; j0 += 128u) {
+        for (uint32_t j0 = share * 128u; j0 < N; j0 += nshare * 128u) {
             double x[2], y[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -841,6 +849,7 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
         // non-empty regions: then `max count` rounds of loads beat `regions` page loads.  Decided with ballots alone.
         const uint32_t npg = (uint32_t)__popcll(__ballot(cnt > 0u));        // pages if no region needs a second one
         if (__ballot(cnt >= npg || cnt > kPage) == 0ull && npg > 1u) {
+            if (nshare > 1u && r % nshare != share) cnt = 0u;       // (decided on every region's count: the same walk in every wave)
             uint32_t cmax = cnt;
             for (int off = 32; off > 0; off >>= 1) {
                 const uint32_t o = __shfl_xor(cmax, off);
@@ -866,6 +875,7 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
         for (uint32_t j = 0;; ++j) {
             unsigned long long m = __ballot(cnt > j * kPage);
             if (!m) break;
+            if (nshare > 1u) m = __ballot(cnt > j * kPage && (r + j) % nshare == share);
             if (j && cnt > j * kPage) page = gdir[(size_t)reg * rc.rg_maxp + j];
             while (m) {
                 uint32_t pg[2], pc[2];
@@ -1112,8 +1122,12 @@ __device__ void insert_step_pages(const RunConst &rc_arg, uint32_t b, uint32_t n
 // barrier (the samples, the old counts of all regions -- kept in LDS --, the valid mask, the page counter): one round trip
 // to memory instead of five.  Same result as insert_step_pages up to the order of a step's nodes inside a region's
 // pages, which nothing depends on.
+// The group kernels' riders call it too (GROUP, 256 threads: k_conn2_riders and k_conn2_wg4, where the filing is a link of the step's
+// chain as well since the connect pass became one-wave workgroups).  SPT: samples per thread, nb <= SPT * T.  GROUP keeps what a row
+// of a batch needs: the coordinates go to nx / ny only where the next step's search reads them ahead of the connect pass (q_stride),
+// and a row whose page pool has overflowed -- in this step or an earlier one -- stores no page.
 constexpr uint32_t kFileLds = 2u * kRegions * 4u + 4096u * 2u + 64u * 8u + 66u * 4u + 32u;
-template <uint32_t T = 1024u>
+template <uint32_t T = 1024u, uint32_t SPT = 4u, bool GROUP = false>
 __device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *scratch) {
     const RunConst &rc = rc_const(rc_arg);          // (out of line in k_step1_rrt and k_coop_rrt)
     uint32_t *s_add = reinterpret_cast<uint32_t *>(scratch);                               // [kRegions] new nodes per region
@@ -1122,7 +1136,7 @@ __device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, 
     unsigned long long *s_word = reinterpret_cast<unsigned long long *>(s_off + 4096);     // [64] the valid mask
     uint32_t *s_pref = reinterpret_cast<uint32_t *>(s_word + 64);                          // [65] valid samples before word w
     uint32_t *s_misc = s_pref + 66;                                                        // np, base, err, N
-    constexpr uint32_t SPT = 4u;                                                           // nb <= 4 T (1024 threads: batch_K <= 4096)
+    // nb <= SPT * T (1024 threads: batch_K <= 4096; the riders' 256: 1024, and the slow form above that)
     const uint32_t tid = threadIdx.x, qo = q_off(rc, b);
     auto rg_old = as_global(rc.rg_cnt) + (b & 1u) * kRegions, rg_new = as_global(rc.rg_cnt) + ((b + 1u) & 1u) * kRegions;
     // ---- loads, all in flight together
@@ -1140,12 +1154,12 @@ __device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, 
 #pragma unroll
     for (uint32_t h = 0; h < RPT; ++h) oldc[h] = tid + h * T < kRegions ? rg_old[tid + h * T] : 0u;
     const unsigned long long word = tid < vwords ? as_global(rc.valid_mask)[(size_t)b * vwords + tid] : 0ull;
-    uint32_t n_pages = 0, N0 = 0;
-    if (tid == T - 1u) { n_pages = rc.cnt->n_pages; N0 = as_global(rc.n_at)[b]; }
+    uint32_t n_pages = 0, N0 = 0, err0 = 0;
+    if (tid == T - 1u) { n_pages = rc.cnt->n_pages; N0 = as_global(rc.n_at)[b]; if (GROUP) err0 = rc.cnt->err & (uint32_t)ERR_PAGE_OVERFLOW; }
 #pragma unroll
     for (uint32_t h = 0; h < RPT; ++h) if (tid + h * T < kRegions) { s_add[tid + h * T] = 0; s_old[tid + h * T] = oldc[h]; }
     if (tid < 64u) s_word[tid] = word;
-    if (tid == T - 1u) { s_misc[0] = 0; s_misc[1] = kRegions + n_pages; s_misc[2] = 0; s_misc[3] = N0; }
+    if (tid == T - 1u) { s_misc[0] = 0; s_misc[1] = kRegions + n_pages; s_misc[2] = err0; s_misc[3] = N0; }
     __syncthreads();
     double t2_next = 0.0;
     if (tid == 0) {
@@ -1178,7 +1192,10 @@ __device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, 
     }
     __threadfence_block();
     __syncthreads();
-    if (s_misc[2]) return;
+    if (s_misc[2]) {                      // (a row of a batch goes on beside the others: its next step finds a radius, as after insert_step_pages)
+        if (GROUP && tid == 0) as_global(rc.t2_at)[b + 1] = t2_next;
+        return;
+    }
     const uint32_t N = s_misc[3];
     dbl2 *pxy = reinterpret_cast<dbl2 *>(rc.pg_xy);
 #pragma unroll
@@ -1193,8 +1210,10 @@ __device__ void file_step_fast(const RunConst &rc_arg, uint32_t b, uint32_t nb, 
         const uint32_t nid = N + s_pref[k >> 6] + (uint32_t)__popcll(s_word[k >> 6] & ((1ull << (k & 63u)) - 1ull));
         as_global(rc.pg_id)[(size_t)page * kPage + (slot % kPage)] = (int)nid;
         as_global(rc.slot_of)[nid] = page * kPage + (slot % kPage);
-        as_global(rc.nx)[nid] = x[q];        // the next step's search reads the coordinates before the connect pass has stored them: same bits
-        as_global(rc.ny)[nid] = y[q];
+        if (!GROUP || rc.q_stride) {         // the next step's search reads the coordinates before the connect pass has stored them: same bits
+            as_global(rc.nx)[nid] = x[q];
+            as_global(rc.ny)[nid] = y[q];
+        }
     }
 #pragma unroll
     for (uint32_t h = 0; h < RPT; ++h) {
@@ -2367,103 +2386,221 @@ template <int TAG> __device__ void g_track_step(const RunConst &rc_arg, uint32_t
     auto vm = as_global(rc.valid_mask) + (size_t)b * vwords;
     const uint32_t N = as_global(rc.n_at)[b];
     const uint32_t glen0 = rc.cnt->g_len, n_nd = rc.cnt->g_nd_len, d0 = rc.cnt->g_first_dup[0], d1 = rc.cnt->g_first_dup[1];
-    if (tid < 64u) s_cand[tid] = 0ull;
-    if (tid < 64u) {                             // valid samples before each word of the mask: a word per lane, a prefix sum over the wave
-        const uint32_t c = tid < vwords ? (uint32_t)__popcll(vm[tid]) : 0u;
-        uint32_t inc = c;
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
-        if (tid < vwords) s_wpre[tid] = inc - c;
-        if (tid == 63u) s_wpre[vwords] = inc;
+    // TAG 2, the riders of the group kernels with option riders_fast: the same results by fewer trips to memory (below)
+    constexpr bool FAST = TAG == 2;
+    uint32_t n_new = 0;
+    if constexpr (!FAST) {
+        if (tid < 64u) s_cand[tid] = 0ull;
+        if (tid < 64u) {                             // valid samples before each word of the mask: a word per lane, a prefix sum over the wave
+            const uint32_t c = tid < vwords ? (uint32_t)__popcll(vm[tid]) : 0u;
+            uint32_t inc = c;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
+            if (tid < vwords) s_wpre[tid] = inc - c;
+            if (tid == 63u) s_wpre[vwords] = inc;
+        }
+        for (uint32_t t2 = tid; t2 < n_nd && t2 < kNd; t2 += blockDim.x) {
+            const KdBox bx = rc.g_nd_box[t2];
+            s_ndi[t2] = as_global(rc.g_nd)[t2]; s_blx[t2] = bx.lox; s_bhx[t2] = bx.hix; s_bly[t2] = bx.loy; s_bhy[t2] = bx.hiy;
+        }
+        __syncthreads();
+        n_new = s_wpre[vwords];
+        for (uint32_t k = tid; k < nb; k += blockDim.x) {
+            const unsigned long long w = vm[k >> 6];
+            if ((w >> (k & 63u)) & 1ull) s_k[s_wpre[k >> 6] + (uint32_t)__popcll(w & ((1ull << (k & 63u)) - 1ull))] = (uint16_t)k;
+        }
+        __syncthreads();
     }
-    for (uint32_t t2 = tid; t2 < n_nd && t2 < kNd; t2 += blockDim.x) {
-        const KdBox bx = rc.g_nd_box[t2];
-        s_ndi[t2] = as_global(rc.g_nd)[t2]; s_blx[t2] = bx.lox; s_bhx[t2] = bx.hix; s_bly[t2] = bx.loy; s_bhy[t2] = bx.hiy;
-    }
-    __syncthreads();
-    const uint32_t n_new = s_wpre[vwords];
-    for (uint32_t k = tid; k < nb; k += blockDim.x) {
-        const unsigned long long w = vm[k >> 6];
-        if ((w >> (k & 63u)) & 1ull) s_k[s_wpre[k >> 6] + (uint32_t)__popcll(w & ((1ull << (k & 63u)) - 1ull))] = (uint16_t)k;
-    }
-    __syncthreads();
     const double px = rc.gp_x, py = rc.gp_y;
     auto gex = as_global(rc.kd_gexit);
     const uint32_t qo = q_off(rc, b);
     GT_MARK(0);
-    // every new node against G as it stands before the step: four nodes per thread, their coordinates fetched together.  A node follows G
-    // through a level iff it lies in the goal point's cell after that level, and the cells are nested: the first level it fails is found by
-    // bisection over the levels' cells (the first kNd of them in LDS) -- a node by the goal point used to walk a hundred levels one by one.
-    for (uint32_t t0 = tid; t0 < ((n_new + blockDim.x - 1u) / blockDim.x) * blockDim.x; t0 += 4u * blockDim.x) {
-        double cvx[4], cvy[4];
-        uint32_t cE[4], lo[4], hi[4];
+    if constexpr (FAST) {
+        // The same as below with the entry trips taken off the chain.  Everything that depends on nothing is asked for together, before the
+        // first barrier: a word of the mask per lane, the first kNd cells of G whatever g_nd_len says (masked by it afterwards; both tables
+        // hold g_cap entries) and each thread's samples BY SAMPLE INDEX with their words of the mask -- a thread finds the place t of its
+        // sample among the new nodes itself, so the coordinates no longer wait for the table s_k (two barriers and a trip).  What is written
+        // per node (kd_gexit, the bit in s_cand, s_k) does not depend on which thread serves it; the wave at the end is the one below.
+        constexpr uint32_t SPT = 4u;
+        const uint32_t T = blockDim.x;
+        double cvx[SPT], cvy[SPT];
+        unsigned long long cw[SPT];
+        uint32_t tt[SPT];
+        auto load_chunk = [&](uint32_t k0) {
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t t = t0 + u * blockDim.x;
-            const uint32_t k = t < n_new ? s_k[t] : 0u;
-            cvx[u] = t < n_new ? as_global(rc.q_x)[qo + k] : 0.0;
-            cvy[u] = t < n_new ? as_global(rc.q_y)[qo + k] : 0.0;
-            cE[u] = 0xFFFFFFFFu;
-            const bool open = t < n_new && !(cvx[u] == px && cvy[u] == py);   // (a copy of the goal point passes every level)
-            lo[u] = 0u; hi[u] = open ? n_nd : 0u;                             // the first failed level lies in [lo, hi]; hi == n_nd: none fails
+            for (uint32_t u = 0; u < SPT; ++u) {
+                const uint32_t k = k0 + tid + u * T;
+                cw[u] = k < nb ? vm[k >> 6] : 0ull;
+                cvx[u] = k < nb ? as_global(rc.q_x)[qo + k] : 0.0;
+                cvy[u] = k < nb ? as_global(rc.q_y)[qo + k] : 0.0;
+            }
+        };
+        const unsigned long long mword = tid < vwords && tid < 64u ? vm[tid] : 0ull;
+        load_chunk(0u);
+        const uint32_t n_stage = kNd < rc.g_cap ? kNd : rc.g_cap;
+        static_assert(kNd <= 256u, "one cell per thread");
+        KdBox sbx = g_box_all();
+        uint32_t sdi = 0u;
+        if (tid < n_stage) { sbx = rc.g_nd_box[tid]; sdi = as_global(rc.g_nd)[tid]; }
+        if (tid < 64u) {
+            s_cand[tid] = 0ull;
+            const uint32_t c = (uint32_t)__popcll(mword);
+            uint32_t inc = c;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
+            if (tid < vwords) s_wpre[tid] = inc - c;
+            if (tid == 63u) s_wpre[vwords] = inc;
         }
-        for (;;) {
-            bool more = false;
+        if (tid < n_stage && tid < n_nd) { s_ndi[tid] = sdi; s_blx[tid] = sbx.lox; s_bhx[tid] = sbx.hix; s_bly[tid] = sbx.loy; s_bhy[tid] = sbx.hiy; }
+        __syncthreads();
+        n_new = s_wpre[vwords];
+        for (uint32_t k0 = 0; k0 < nb; k0 += SPT * T) {          // (once at nb <= 4 T: the group kernels' usual K)
+            if (k0) load_chunk(k0);
+            uint32_t cE[SPT], lo[SPT], hi[SPT];
 #pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) more = more || lo[u] < hi[u];
-            if (!more) break;
+            for (uint32_t u = 0; u < SPT; ++u) {
+                const uint32_t k = k0 + tid + u * T;
+                const bool v = (cw[u] >> (k & 63u)) & 1ull;          // (no word past nb)
+                tt[u] = v ? s_wpre[k >> 6] + (uint32_t)__popcll(cw[u] & ((1ull << (k & 63u)) - 1ull)) : 0xFFFFFFFFu;
+                if (v) s_k[tt[u]] = (uint16_t)k;
+                cE[u] = 0xFFFFFFFFu;
+                const bool open = v && !(cvx[u] == px && cvy[u] == py);   // (a copy of the goal point passes every level)
+                lo[u] = 0u; hi[u] = open ? n_nd : 0u;
+            }
+            for (;;) {
+                bool more = false;
 #pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) {
-                if (lo[u] >= hi[u]) continue;
-                const uint32_t mid = (lo[u] + hi[u]) >> 1;
-                double blx, bhx, bly, bhy;
-                if (mid < kNd) { blx = s_blx[mid]; bhx = s_bhx[mid]; bly = s_bly[mid]; bhy = s_bhy[mid]; }
-                else { const KdBox bx = rc.g_nd_box[mid]; blx = bx.lox; bhx = bx.hix; bly = bx.loy; bhy = bx.hiy; }
-                const bool in = !(cvx[u] < blx) && cvx[u] < bhx && !(cvy[u] < bly) && cvy[u] < bhy;
-                if (in) lo[u] = mid + 1u; else hi[u] = mid;
+                for (uint32_t u = 0; u < SPT; ++u) more = more || lo[u] < hi[u];
+                if (!more) break;
+#pragma unroll
+                for (uint32_t u = 0; u < SPT; ++u) {
+                    if (lo[u] >= hi[u]) continue;
+                    const uint32_t mid = (lo[u] + hi[u]) >> 1;
+                    double blx, bhx, bly, bhy;
+                    if (mid < kNd) { blx = s_blx[mid]; bhx = s_bhx[mid]; bly = s_bly[mid]; bhy = s_bhy[mid]; }
+                    else { const KdBox bx = rc.g_nd_box[mid]; blx = bx.lox; bhx = bx.hix; bly = bx.loy; bhy = bx.hiy; }
+                    const bool in = !(cvx[u] < blx) && cvx[u] < bhx && !(cvy[u] < bly) && cvy[u] < bhy;
+                    if (in) lo[u] = mid + 1u; else hi[u] = mid;
+                }
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < SPT; ++u)
+                if (tt[u] != 0xFFFFFFFFu && !(cvx[u] == px && cvy[u] == py) && lo[u] < n_nd) cE[u] = lo[u] < kNd ? s_ndi[lo[u]] : as_global(rc.g_nd)[lo[u]];
+#pragma unroll
+            for (uint32_t u = 0; u < SPT; ++u) {
+                const uint32_t t = tt[u];
+                if (t == 0xFFFFFFFFu) continue;
+                uint32_t E = cE[u];
+                if (cvx[u] < px && d0 < E) E = d0;
+                if (cvy[u] < py && d1 < E) E = d1;
+                if (E != 0xFFFFFFFFu) gex[N + t] = E;
+                else atomicOr(&s_cand[t >> 6], 1ull << (t & 63u));
             }
         }
-        GT_MARK(4);
-#pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t t = t0 + u * blockDim.x;
-            if (t < n_new && !(cvx[u] == px && cvy[u] == py) && lo[u] < n_nd) cE[u] = lo[u] < kNd ? s_ndi[lo[u]] : as_global(rc.g_nd)[lo[u]];
+        __syncthreads();
+        if (tid < 64u) {
+            const uint32_t c = (uint32_t)__popcll(s_cand[tid]);
+            uint32_t inc = c;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
+            s_wpre[tid] = inc - c;                                               // (the sample prefix is no longer needed)
         }
+        __syncthreads();
+        if (nb <= SPT * T) {                     // the coordinates are still in the registers of the thread that fetched them
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t t = t0 + u * blockDim.x;
-            if (t >= n_new) continue;
-            uint32_t E = cE[u];
-            if (cvx[u] < px && d0 < E) E = d0;
-            if (cvy[u] < py && d1 < E) E = d1;
-            if (E != 0xFFFFFFFFu) gex[N + t] = E;
-            else atomicOr(&s_cand[t >> 6], 1ull << (t & 63u));
+            for (uint32_t u = 0; u < SPT; ++u) {
+                const uint32_t t = tt[u];
+                if (t == 0xFFFFFFFFu) continue;
+                const unsigned long long w = s_cand[t >> 6];
+                if (!((w >> (t & 63u)) & 1ull)) continue;
+                const uint32_t rank = s_wpre[t >> 6] + (uint32_t)__popcll(w & ((1ull << (t & 63u)) - 1ull));
+                if (rank < kCand) { s_cx[rank] = cvx[u]; s_cy[rank] = cvy[u]; }
+            }
+        } else {
+            for (uint32_t t = tid; t < n_new; t += T) {
+                const unsigned long long w = s_cand[t >> 6];
+                if (!((w >> (t & 63u)) & 1ull)) continue;
+                const uint32_t rank = s_wpre[t >> 6] + (uint32_t)__popcll(w & ((1ull << (t & 63u)) - 1ull));
+                if (rank < kCand) { const uint32_t k = s_k[t]; s_cx[rank] = as_global(rc.q_x)[qo + k]; s_cy[rank] = as_global(rc.q_y)[qo + k]; }
+            }
         }
+        __syncthreads();
     }
-    __syncthreads();
-    GT_MARK(5);
-    // the coordinates of the nodes that stay on G to its end, in id order (the first kCand of them), for the wave below
-    if (tid < 64u) {
-        const uint32_t c = (uint32_t)__popcll(s_cand[tid]);
-        uint32_t inc = c;
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
-        s_wpre[tid] = inc - c;                                               // (the sample prefix is no longer needed)
+    if constexpr (!FAST) {
+        // every new node against G as it stands before the step: four nodes per thread, their coordinates fetched together.  A node follows G
+        // through a level iff it lies in the goal point's cell after that level, and the cells are nested: the first level it fails is found by
+        // bisection over the levels' cells (the first kNd of them in LDS) -- a node by the goal point used to walk a hundred levels one by one.
+        for (uint32_t t0 = tid; t0 < ((n_new + blockDim.x - 1u) / blockDim.x) * blockDim.x; t0 += 4u * blockDim.x) {
+            double cvx[4], cvy[4];
+            uint32_t cE[4], lo[4], hi[4];
+    #pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t t = t0 + u * blockDim.x;
+                const uint32_t k = t < n_new ? s_k[t] : 0u;
+                cvx[u] = t < n_new ? as_global(rc.q_x)[qo + k] : 0.0;
+                cvy[u] = t < n_new ? as_global(rc.q_y)[qo + k] : 0.0;
+                cE[u] = 0xFFFFFFFFu;
+                const bool open = t < n_new && !(cvx[u] == px && cvy[u] == py);   // (a copy of the goal point passes every level)
+                lo[u] = 0u; hi[u] = open ? n_nd : 0u;                             // the first failed level lies in [lo, hi]; hi == n_nd: none fails
+            }
+            for (;;) {
+                bool more = false;
+    #pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) more = more || lo[u] < hi[u];
+                if (!more) break;
+    #pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) {
+                    if (lo[u] >= hi[u]) continue;
+                    const uint32_t mid = (lo[u] + hi[u]) >> 1;
+                    double blx, bhx, bly, bhy;
+                    if (mid < kNd) { blx = s_blx[mid]; bhx = s_bhx[mid]; bly = s_bly[mid]; bhy = s_bhy[mid]; }
+                    else { const KdBox bx = rc.g_nd_box[mid]; blx = bx.lox; bhx = bx.hix; bly = bx.loy; bhy = bx.hiy; }
+                    const bool in = !(cvx[u] < blx) && cvx[u] < bhx && !(cvy[u] < bly) && cvy[u] < bhy;
+                    if (in) lo[u] = mid + 1u; else hi[u] = mid;
+                }
+            }
+            GT_MARK(4);
+    #pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t t = t0 + u * blockDim.x;
+                if (t < n_new && !(cvx[u] == px && cvy[u] == py) && lo[u] < n_nd) cE[u] = lo[u] < kNd ? s_ndi[lo[u]] : as_global(rc.g_nd)[lo[u]];
+            }
+    #pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t t = t0 + u * blockDim.x;
+                if (t >= n_new) continue;
+                uint32_t E = cE[u];
+                if (cvx[u] < px && d0 < E) E = d0;
+                if (cvy[u] < py && d1 < E) E = d1;
+                if (E != 0xFFFFFFFFu) gex[N + t] = E;
+                else atomicOr(&s_cand[t >> 6], 1ull << (t & 63u));
+            }
+        }
+        __syncthreads();
+        GT_MARK(5);
+        // the coordinates of the nodes that stay on G to its end, in id order (the first kCand of them), for the wave below
+        if (tid < 64u) {
+            const uint32_t c = (uint32_t)__popcll(s_cand[tid]);
+            uint32_t inc = c;
+            for (int off = 1; off < 64; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, off); if ((int)lane >= off) inc += o; }
+            s_wpre[tid] = inc - c;                                               // (the sample prefix is no longer needed)
+        }
+        __syncthreads();
+        for (uint32_t t = tid; t < n_new; t += blockDim.x) {
+            const unsigned long long w = s_cand[t >> 6];
+            if (!((w >> (t & 63u)) & 1ull)) continue;
+            const uint32_t rank = s_wpre[t >> 6] + (uint32_t)__popcll(w & ((1ull << (t & 63u)) - 1ull));
+            if (rank < kCand) { const uint32_t k = s_k[t]; s_cx[rank] = as_global(rc.q_x)[qo + k]; s_cy[rank] = as_global(rc.q_y)[qo + k]; }
+        }
+        __syncthreads();
+        GT_MARK(1);
     }
-    __syncthreads();
-    for (uint32_t t = tid; t < n_new; t += blockDim.x) {
-        const unsigned long long w = s_cand[t >> 6];
-        if (!((w >> (t & 63u)) & 1ull)) continue;
-        const uint32_t rank = s_wpre[t >> 6] + (uint32_t)__popcll(w & ((1ull << (t & 63u)) - 1ull));
-        if (rank < kCand) { const uint32_t k = s_k[t]; s_cx[rank] = as_global(rc.q_x)[qo + k]; s_cy[rank] = as_global(rc.q_y)[qo + k]; }
-    }
-    __syncthreads();
-    GT_MARK(1);
     // the nodes that follow G to its end, in id order: the first extends it, the next ones are tested against the levels added
     // before them and extend it in their turn if they pass them all.  One wave; their coordinates are in LDS (the first kCand of
     // them), the levels this step adds are kept there too (the first kApp): in an ordinary step -- a handful of copies of the goal
     // point -- nothing in the loop waits for memory.
     if (tid < 64u) {
         uint32_t len = glen0, nd_len = n_nd, fd0 = d0, fd1 = d1;
-        KdBox cell = n_nd ? rc.g_nd_box[n_nd - 1u] : g_box_all();  // the goal point's cell at the end of G
+        KdBox cell = g_box_all();                                   // the goal point's cell at the end of G
+        if (FAST && n_nd && n_nd - 1u < kNd) { cell.lox = s_blx[n_nd - 1u]; cell.hix = s_bhx[n_nd - 1u]; cell.loy = s_bly[n_nd - 1u]; cell.hiy = s_bhy[n_nd - 1u]; }   // (staged above: no trip)
+        else if (n_nd) cell = rc.g_nd_box[n_nd - 1u];
         auto gx = as_global(reinterpret_cast<unsigned long long *>(rc.g_x)), gy = as_global(reinterpret_cast<unsigned long long *>(rc.g_y));
         uint32_t c_at = 0;
         for (uint32_t w = 0; w < (n_new + 63u) / 64u; ++w) {

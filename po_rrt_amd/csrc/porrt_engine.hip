@@ -147,6 +147,9 @@ struct porrt_ctx {
     // 4: k_conn2_wg4, everything in one kernel of four-wave workgroups.  "conn_riders_first": k_conn2_riders before (1) or after (0) k_conn2.
     uint32_t opt_conn_wg_waves = 1;
     bool opt_conn_riders_first = true;
+    // "riders_fast" (developer option): 1 = the riders' page filing and goal path in their one-round-trip forms (file_step_fast, g_track_step<2>),
+    // 0 = in the forms they had beside a long connect pass (insert_step_pages<1>, g_track_step<1>).  Same launch geometry, same results.
+    uint32_t opt_riders_fast = 1;
     uint32_t opt_nn_wg_waves = 4;          // "nn_wg_waves": the same choice for k_nn2 (4 or 1 waves per workgroup)
     // "commit_flat": the group kernels' rewire phase 2 with one lane per candidate record, kSpan samples per workgroup (commit_flat_span:
     // k_nn2's commit workgroups and k_commit_flat), 1, or with a group of lanes per sample (commit_rrt_sample, k_commit2), 0.  The same trees.
@@ -782,16 +785,16 @@ void LaunchSeq::launch_step(uint32_t b, uint32_t i0, uint32_t nb, bool prof, siz
             const uint32_t spb = 256u / GLc;
             const dim3 g2((nb + spb - 1) / spb + 2 + lazy, Q);       // + the clone workgroup + the page-filing workgroup (+ the goal path's)
             const size_t dyn = conn2_wg4_lds_bytes(GLc);
-            with_lanes(GLc, [&](auto gl) { hipLaunchKernelGGL(k_conn2_wg4<decltype(gl)::value>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy); });
+            with_lanes(GLc, [&](auto gl) { hipLaunchKernelGGL(k_conn2_wg4<decltype(gl)::value>, g2, dim3(256), dyn, stream, rcp, b, nb, vwords, lazy, cx.opt_riders_fast); });
         } else {
             // one-wave workgroups for the samples; the step's single workgroups as a kernel of their own on the same stream (one more
             // node of the chain under capture), before or after the samples (conn_riders_first)
             const uint32_t spb = 64u / GLc;
             const dim3 g2((nb + spb - 1) / spb, Q), gr(2 + lazy, Q);
             const size_t dyn = conn2_lds_bytes(GLc);
-            if (cx.opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy);
+            if (cx.opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy, cx.opt_riders_fast);
             with_lanes(GLc, [&](auto gl) { hipLaunchKernelGGL(k_conn2<decltype(gl)::value>, g2, dim3(64), dyn, stream, rcp, b, nb, vwords); });
-            if (!cx.opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy);
+            if (!cx.opt_conn_riders_first) hipLaunchKernelGGL(k_conn2_riders, gr, dim3(256), conn2_riders_lds_bytes(), stream, rcp, b, nb, vwords, lazy, cx.opt_riders_fast);
         }
     } else if (lds_bytes) hipLaunchKernelGGL(k_connect_rrt<true>, cgrid, cblock, lds_bytes, stream, rcp, b, nb, vwords);
     else hipLaunchKernelGGL(k_connect_rrt<false>, cgrid, cblock, 0, stream, rcp, b, nb, vwords);
@@ -5180,6 +5183,8 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "n_heavy")) *value = (int64_t)c->counters.n_heavy;        // samples of this context's last grow with more hits than their LDS list holds (served by a whole wave)
     else if (!strcmp(name, "conn_wg_waves")) *value = c->opt_conn_wg_waves;
     else if (!strcmp(name, "conn_riders_first")) *value = c->opt_conn_riders_first ? 1 : 0;
+    else if (!strcmp(name, "riders_fast")) *value = c->opt_riders_fast;
+    else if (!strncmp(name, "tim", 3) && name[3] >= '0' && name[3] <= '9' && atoi(name + 3) < 16) *value = (int64_t)c->counters.tim[atoi(name + 3)];   // developer builds (-DPORRT_TIMING): this context's last growth
     else if (!strcmp(name, "nn_wg_waves")) *value = c->opt_nn_wg_waves;
     else if (!strcmp(name, "commit_flat")) *value = c->opt_commit_flat;
     else if (!strcmp(name, "cand_cap")) *value = c->opt_cand_cap;                     // (grown by a call whose lists overflowed: the call was replayed)
@@ -5248,6 +5253,7 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "early_wave_steps")) c->opt_early_wave = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 64));
     else if (!strcmp(name, "conn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("conn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_conn_wg_waves = (uint32_t)value; }
     else if (!strcmp(name, "conn_riders_first")) c->opt_conn_riders_first = value != 0;
+    else if (!strcmp(name, "riders_fast")) { if (value != 0 && value != 1) { c->set_err("riders_fast: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_riders_fast = (uint32_t)value; }
     else if (!strcmp(name, "nn_wg_waves")) { if (value != 1 && value != 4) { c->set_err("nn_wg_waves: 1 or 4"); return PORRT_ERR_INVALID; } c->opt_nn_wg_waves = (uint32_t)value; }
     else if (!strcmp(name, "commit_flat")) { if (value != 0 && value != 1) { c->set_err("commit_flat: 0 or 1"); return PORRT_ERR_INVALID; } c->opt_commit_flat = (uint32_t)value; }
     else if (!strcmp(name, "kd_group")) c->opt_kd_group = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 8));

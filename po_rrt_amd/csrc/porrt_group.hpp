@@ -666,12 +666,41 @@ __host__ __device__ inline size_t conn2_lds_bytes(uint32_t GL) {
     (void)GL;
     return (64u / 16u) * kHitBytes;
 }
-__host__ __device__ inline size_t conn2_riders_lds_bytes() { return kInsertLds > kGTrackLds ? kInsertLds : kGTrackLds; }
+static_assert(kInsertLds <= kFileLds && kGTrackLds <= kFileLds, "the filing's one-round-trip form is the largest of the riders' scratch areas");
+__host__ __device__ inline size_t conn2_riders_lds_bytes() { return kFileLds; }
 __host__ __device__ inline size_t conn2_wg4_lds_bytes(uint32_t GL) {
     const size_t a = 4u * conn2_lds_bytes(GL);
     static_assert(kGTrackLds <= 4u * (64u / 16u) * kHitBytes, "g_track_step uses the same bytes");
+    static_assert(kFileLds <= 4u * (64u / 16u) * kHitBytes, "file_step_fast uses the same bytes");
     return a > kInsertLds ? a : kInsertLds;
 }
+
+// The riders' roles 0 and 2 in the form option riders_fast chooses: 1 = the forms with their loads in one round trip (file_step_fast, which
+// holds SPT = 4 samples per thread -- K <= 1024 at 256 threads; a larger K keeps insert_step_pages -- and g_track_step<2>), 0 = the forms the
+// riders were written with, when they rode beside a connect pass several times their length.  Same pages up to the order inside a region's
+// pages, same goal path.
+__device__ __forceinline__ void rider_file(const RunConst &rc, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *lds, uint32_t fast) {
+    if (fast && nb <= 4u * 256u) file_step_fast<256u, 4u, true>(rc, b, nb, vwords, lds);
+    else insert_step_pages<1>(rc, b, nb, vwords, lds);
+}
+__device__ __forceinline__ void rider_gtrack(const RunConst &rc, uint32_t b, uint32_t nb, uint32_t vwords, uint8_t *lds, uint32_t fast) {
+    if (fast) g_track_step<2>(rc, b, nb, vwords, lds);
+    else g_track_step<1>(rc, b, nb, vwords, lds);
+}
+// -DPORRT_TIMING=5: how long each of the riders' workgroups takes, per row -- tim[3 role + w] the sum over the steps of window w (10 ns
+// units), tim[9 + w] the steps: w = 0 the first eight steps, 1 the later steps before a copy of the goal point is on the goal path, 2 the
+// steps after (tools/riders_probe.py reads them row by row)
+#if defined(PORRT_TIMING) && PORRT_TIMING == 5
+#define RIDERS_T0() const unsigned long long rt__0 = wall_clock64(); const uint32_t rt__w = b < 8u ? 0u : ((rc.cnt->g_first_dup[0] & rc.cnt->g_first_dup[1]) != 0xFFFFFFFFu ? 2u : 1u)
+#define RIDERS_MARK(role)                                                                                          \
+    do {                                                                                                           \
+        __syncthreads();                                                                                           \
+        if (threadIdx.x == 0) { atomicAdd(&rc.cnt->tim[3u * (role) + rt__w], wall_clock64() - rt__0); if ((role) == 0u) atomicAdd(&rc.cnt->tim[9u + rt__w], 1ull); } \
+    } while (0)
+#else
+#define RIDERS_T0() do {} while (0)
+#define RIDERS_MARK(role) do {} while (0)
+#endif
 
 // (the connect pass needs these rarely: functions of their own, so that their registers are not the step kernel's)
 template <int GL>
@@ -724,13 +753,52 @@ __device__ __forceinline__ void list_scan_wave(const RunConst &rc, uint32_t b, u
     if (over) err |= (uint32_t)ERR_CAND_OVERFLOW;
 }
 
+// the same by the four waves of the clone workgroup together, each its share of the disc (scan_disc): list positions from one LDS counter,
+// `tot` (zeroed and separated from the scan by a barrier by the caller; complete after the next one).  The list's ORDER is then whatever the
+// waves' turns at the counter make it; see clone_workgroup for why nothing depends on it.
+__device__ __forceinline__ void list_scan_waves(const RunConst &rc, uint32_t b, uint32_t N, double T2, uint32_t kh, double pxh, double pyh, uint32_t lane,
+                                                uint32_t wv, uint32_t *tot, uint32_t &err) {
+    auto cid = as_global(rc.cand_id) + cand_off(rc, b, kh);
+    auto cxy = as_global(reinterpret_cast<dbl2 *>(rc.cand_xy)) + cand_off(rc, b, kh);
+    const uint32_t cap = rc.cand_cap;
+    bool over = false;
+    scan_disc(rc, b, pxh, pyh, disc_radius(T2, pxh, pyh), uni(N), lane, [&](double x, double y, int jd, bool ok) {
+        const bool in = ok && dist2(x, y, pxh, pyh) <= T2;
+        const unsigned long long hm = __ballot(in);
+        if (!hm) return;
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(tot, (uint32_t)__popcll(hm));
+        const uint32_t pos = uni(base) + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
+        if (in) {
+            if (pos < cap) {
+                cid[pos] = jd;
+                dbl2 v;
+                v.x = x; v.y = y;
+                cxy[pos] = v;
+            } else {
+                over = true;
+            }
+        }
+    }, 0xFFFFFFFFu, wv, kConnectWaves);
+    if (over) err |= (uint32_t)ERR_CAND_OVERFLOW;
+}
+
+#ifndef PORRT_CLONE_SCAN_WAVES
+#define PORRT_CLONE_SCAN_WAVES 4
+#endif
 // The clone workgroup of k_conn2: the step's copies of the goal point, one search for all of them by the 4-wave team.
 // A function of its own (not inlined): its registers are not the step kernel's.
-__device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc_arg, uint32_t b, uint32_t vwords, uint32_t N, double T2) {
+// fast (option riders_fast): the radius search by all four waves (list_scan_waves), not by the first with three waiting.  The list then
+// comes in another order, and connect_rrt_sample's result does not depend on it: the parent is the minimum of (total cost, id) over the
+// valid entries (a lane's minimum, then the team's argmin: commutative), ties are settled from the SET of tied ids (sums, minima and maxima
+// over them, the pre-order-first of them; the pooled ids of a deferred tie are placed by an atomic counter already), the rewire candidates
+// are written entry by entry at the entry's own place, and the commit pass treats every entry on its own (an atomic minimum per node).
+__device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc_arg, uint32_t b, uint32_t vwords, uint32_t N, double T2, uint32_t fast) {
     const RunConst &rc = rc_const(rc_arg);
     __shared__ double s_d[kConnectWaves];
     __shared__ int s_i[kConnectWaves];
     __shared__ uint32_t s_cid[64], s_ck[64];
+    __shared__ uint32_t s_tot;
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     uint32_t err = 0;
     uint32_t n = rc.cnt->clone_n;
@@ -748,17 +816,31 @@ __device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc_arg
         const uint32_t ti = s_cid[0], tk = s_ck[0];
         s_cid[0] = s_cid[lead]; s_ck[0] = s_ck[lead]; s_cid[lead] = ti; s_ck[lead] = tk;
         rc.cnt->clone_n = 0;                    // for the next step
+        s_tot = 0;
     }
     __syncthreads();
     const uint32_t kh = uni(s_ck[0]), idh = uni(s_cid[0]);
     if (threadIdx.x >= 1 && threadIdx.x < n) as_global(rc.cand_cnt)[cand_cnt_at(rc, b, s_ck[threadIdx.x])] = 0u;     // no rewire candidates of their own
     const double pxh = uni_d(as_global(rc.q_x)[kh]), pyh = uni_d(as_global(rc.q_y)[kh]);
-    if (wv == 0) {
-        list_scan_wave(rc, b, N, T2, kh, pxh, pyh, lane, err);
-        __threadfence();
+    uint32_t hc;
+    if (PORRT_CLONE_SCAN_WAVES == 4 && fast) {
+        list_scan_waves(rc, b, N, T2, kh, pxh, pyh, lane, wv, &s_tot, err);
+        // the list goes from wave to wave of ONE workgroup: a fence of that scope (four fences over the whole device per row and step, each
+        // a write-back of the L2, slowed every workgroup beside this one)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const uint32_t tot = s_tot;
+        if (threadIdx.x == 0) as_global(rc.cand_cnt)[cand_cnt_at(rc, b, kh)] = tot;       // (the commit pass reads it)
+        hc = tot < rc.cand_cap ? tot : rc.cand_cap;
+    } else {
+        if (wv == 0) {
+            list_scan_wave(rc, b, N, T2, kh, pxh, pyh, lane, err);
+            __threadfence();
+        }
+        __syncthreads();
+        hc = cand_count(rc, b, kh);
     }
-    __syncthreads();
-    const uint32_t hc = cand_count(rc, b, kh);
     TableGrid grid;            // the few rays outside the clearance window read the raster in memory
     grid.p = rc.cls; grid.W = rc.W;
     Team<kConnectWaves> tmh;
@@ -947,22 +1029,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_
 // 0 files the new nodes into the region pages, 1 serves the step's copies of the goal point, 2 (lazy) tracks the goal path of the
 // kd order.  They read the snapshot of step b as the samples do and write only what step b + 1 reads, so their place relative
 // to k_conn2 of the same step is free.  Launch index = row * roles + role: the dealing to XCDs of xcd_swizzle_roles.
+// fast (option riders_fast): the roles' short forms -- rider_file, rider_gtrack, clone_workgroup.  Since the connect pass became one-wave
+// workgroups this kernel is a link of the step's chain, and its length is its longest role's chain of memory trips.
 // (The register request of k_conn2_wg4: clone_workgroup is a function of both kernels and is compiled to the larger of their budgets.)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_riders(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_riders(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy,
+                                                                                                                  uint32_t fast) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
     const RunConst &rc = rc_const(rcp + blockIdx.y);
     const uint32_t role = blockIdx.x;
     nb = row_nb(rc, b, nb);
     if (nb == 0) return;
-    if (role == 0) { insert_step_pages<1>(rc, b, nb, vwords, lds_dyn); return; }
-    if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
-    clone_workgroup(rc, b, vwords, as_global(rc.n_at)[b], as_global(rc.t2_at)[b]);
+    RIDERS_T0();
+    if (role == 0) rider_file(rc, b, nb, vwords, lds_dyn, fast);
+    else if (lazy && role == 2u) rider_gtrack(rc, b, nb, vwords, lds_dyn, fast);
+    else clone_workgroup(rc, b, vwords, as_global(rc.n_at)[b], as_global(rc.t2_at)[b], fast);
+    RIDERS_MARK(role);
 }
 
 // The same step as ONE kernel of four-wave workgroups (option conn_wg_waves = 4): the riders are its first 2 + lazy workgroups per
 // row, and a workgroup's lists stay allocated until its slowest wave is through.
 template <int GL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_wg4(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_WAVES, 8))) void k_conn2_wg4(const RunConst *__restrict__ rcp, uint32_t b, uint32_t nb, uint32_t vwords, uint32_t lazy, uint32_t fast) {
     static_assert(GL == 16 || GL == 32 || GL == 64, "group size");
     constexpr uint32_t SPB = 256u / GL;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
@@ -972,8 +1059,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
     const RunConst &rc = rc_const(rcp + by);    // one context per grid row (porrt_grow_batch)
     nb = row_nb(rc, b, nb);
     if (nb == 0) return;                        // (a row that has stopped, or does not run this step)
-    if (role == 0) { insert_step_pages<1>(rc, b, nb, vwords, lds_dyn); return; }    // the page-filing workgroup
-    if (lazy && role == 2u) { g_track_step<1>(rc, b, nb, vwords, lds_dyn); return; }
+    if (role == 0) { rider_file(rc, b, nb, vwords, lds_dyn, fast); return; }    // the page-filing workgroup
+    if (lazy && role == 2u) { rider_gtrack(rc, b, nb, vwords, lds_dyn, fast); return; }
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
     // first round trip: everything that depends on nothing
     const uint32_t N = as_global(rc.n_at)[b];
@@ -981,7 +1068,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
     uint32_t k = 0xFFFFu;
     double px = 0.0, py = 0.0;
     if (role == ns && slot < nb) { k = as_global(rc.bq_k)[slot]; px = as_global(rc.bq_x)[slot]; py = as_global(rc.bq_y)[slot]; }
-    if (role == 1) { clone_workgroup(rc, b, vwords, N, T2); return; }
+    if (role == 1) { clone_workgroup(rc, b, vwords, N, T2, fast); return; }
     conn2_wave<GL>(rc, b, vwords, N, T2, k, px, py, lds_dyn + (threadIdx.x >> 6) * conn2_lds_bytes(GL));
 }
 
