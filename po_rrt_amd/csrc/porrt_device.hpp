@@ -788,6 +788,76 @@ constexpr uint32_t kPage = 64;
 constexpr uint32_t kOccWords = (kRegions + 63u) / 64u;
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 
+// The page arrays of a row as buffers.  A page load through a global pointer adds a 64-bit lane offset to a 64-bit base (the compiler
+// cannot prove that the scaled 32-bit index does not wrap), and "only the filled slots are fetched" puts every load into an exec region of
+// its own with a zeroed destination: in a page round of gscan_disc that is more instructions than the distance test and the compaction
+// together.  A raw buffer load takes the array's base and size from four scalar registers and a 32-bit byte offset from the lane, and
+// an offset at or past the size returns zeros WITHOUT a fetch: no 64-bit arithmetic, no guard, no lane of load work for an empty slot.
+// A lane with nothing to fetch asks for slot kNoSlot, whose byte offset lies past the end of each of the three arrays (the host
+// refuses page arrays of 4 GiB or more: 16 kNoSlot = 2^32 - 16, 8 kNoSlot and 4 kNoSlot are past a half and a quarter of that).
+// What such a lane gets -- zeros, id 0 -- must not be read: the `ok` flag of a visit says whether the lane holds a node.
+// The descriptors are wave-uniform as long as the row is read through rc_const(); built once per wave, before the loops.
+// -DPORRT_PAGE_LOADS=0: the guarded global loads everywhere (the A/B of profiles/page_loads_experiments.txt).
+#ifndef PORRT_PAGE_LOADS
+#define PORRT_PAGE_LOADS 1
+#endif
+constexpr uint32_t kNoSlot = 0x0FFFFFFFu;
+struct PageBuf {
+    __amdgpu_buffer_rsrc_t xy, id, d;
+};
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_of(const void *p, uint32_t bytes) {
+    // dword 3: DATA_FORMAT 32 (untyped loads ignore it, but a zero format is an invalid descriptor); stride 0, no swizzle: raw
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ PageBuf page_buf(const RunConst &rc) {
+    const uint32_t slots = rc.pg_cap * kPage;
+    PageBuf pb;
+    pb.xy = buf_of(rc.pg_xy, slots * 16u);
+    pb.id = buf_of(rc.pg_id, slots * 4u);
+    pb.d = buf_of(rc.pg_d, slots * 8u);
+    return pb;
+}
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ dbl2 page_xy(const PageBuf &pb, uint32_t slot) {
+    return __builtin_bit_cast(dbl2, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(pb.xy, (int)(slot << 4), 0, 0));
+}
+__device__ __forceinline__ int page_id(const PageBuf &pb, uint32_t slot) {
+    return (int)__builtin_amdgcn_raw_buffer_load_b32(pb.id, (int)(slot << 2), 0, 0);
+}
+__device__ __forceinline__ double page_d(const PageBuf &pb, uint32_t slot) {
+    return __builtin_bit_cast(double, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(pb.d, (int)(slot << 3), 0, 0));
+}
+// an element of a global array at a 32-bit BYTE offset from its (scalar) base: one global load with the base in scalar registers and
+// the offset in one vector register, where base[index] extends the index to 64 bits and adds.  For arrays below 4 GiB.
+template <class T>
+__device__ __forceinline__ T g_at(const T *base, uint32_t byte_off) {
+    return *(GPTR(const T))((GPTR(const char))(uintptr_t)base + byte_off);
+}
+// (the address itself, for stores and atomics: node ids are below 2^28 where the page arrays are below 4 GiB, so id * 8 fits)
+template <class T>
+__device__ __forceinline__ GPTR(T) g_ptr(T *base, uint32_t byte_off) {
+    return (GPTR(T))((GPTR(char))(uintptr_t)base + byte_off);
+}
+// a sample's slice of a list array of its row: the row's base (wave-uniform, scalar registers) and ONE 32-bit element offset per sample,
+// where a pointer per lane costs two registers and a 64-bit add per access.  (off + i) * sizeof(T) must stay below 4 GiB: the host
+// refuses neighbour-list arrays that large.
+template <class T>
+struct Row32 {
+    T *base;
+    uint32_t off;
+    __device__ __forceinline__ T __attribute__((address_space(1))) &operator[](uint32_t i) const {
+        return *(GPTR(T))((GPTR(char))(uintptr_t)base + (off + i) * (uint32_t)sizeof(T));
+    }
+};
+#if PORRT_PAGE_LOADS
+template <class T> using HitRow = Row32<T>;
+template <class T> using LdsPtr = T __attribute__((address_space(3))) *;       // (a list in LDS is named as such: ds_* whatever the optimiser infers)
+#else
+template <class T> using HitRow = T __attribute__((address_space(1))) *;
+template <class T> using LdsPtr = T *;
+#endif
+
 __device__ __forceinline__ uint32_t region_of(const RunConst &rc, double x, double y) {
     int cx, cy;
     rep_cell(rc, x, y, kRG, cx, cy);
@@ -809,7 +879,10 @@ __device__ __forceinline__ double disc_radius(double bound_d2, double qx, double
 // share, nshare: the calling wave is one of nshare that scan the same disc together (the clone workgroup): it visits its share of the flat
 // array's blocks, of a sparse group's regions and of the pages (page j of the group's r-th region goes to wave (r + j) % nshare), so that
 // every node is visited by exactly one of them.  Constants at every other call: one wave, everything.
-template <class Visit>
+// BUF: the slots are read through the row's page buffers (PageBuf: no guard, no 64-bit address) -- the clone workgroup of the group
+// kernels asks for it.  The single query's kernels keep the guarded loads: k_step1_rrt once lost a quarter to 15 registers, and its code
+// stays what it was.  What an unfetched lane holds differs (id -1 there, 0 here); `ok` is false for it in both.
+template <bool BUF = false, class Visit>
 __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double qx, double qy, double rho, uint32_t N, uint32_t lane, Visit visit,
                                           uint32_t skip_region = 0xFFFFFFFFu, uint32_t share = 0u, uint32_t nshare = 1u) {
     int cx0, cy0, cx1, cy1;
@@ -818,14 +891,19 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
     const uint32_t x0 = uni((uint32_t)cx0), y0 = uni((uint32_t)cy0);
     const uint32_t w = uni((uint32_t)(cx1 - cx0 + 1)), nreg = w * uni((uint32_t)(cy1 - cy0 + 1));
     if (nreg * 16u > N) {
-        auto gx = as_global(rc.nx), gy = as_global(rc.ny);
+        [[maybe_unused]] auto gx = as_global(rc.nx), gy = as_global(rc.ny);
         for (uint32_t j0 = share * 128u; j0 < N; j0 += nshare * 128u) {
             double x[2], y[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const uint32_t j = j0 + 64u * u + lane;
-                x[u] = gx[j < N ? j : 0u];
-                y[u] = gy[j < N ? j : 0u];
+                if constexpr (BUF) {
+                    x[u] = g_at(rc.nx, (j < N ? j : 0u) * 8u);         // (N < nreg * 16 here: the byte offset fits by far)
+                    y[u] = g_at(rc.ny, (j < N ? j : 0u) * 8u);
+                } else {
+                    x[u] = gx[j < N ? j : 0u];
+                    y[u] = gy[j < N ? j : 0u];
+                }
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -835,8 +913,10 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
     }
     auto gcnt = as_global(rc.rg_cnt) + (b & 1u) * kRegions;
     auto gdir = as_global(rc.rg_dir);
-    auto gxy = as_global(reinterpret_cast<const dbl2 *>(rc.pg_xy));
-    auto gid = as_global(rc.pg_id);
+    [[maybe_unused]] auto gxy = as_global(reinterpret_cast<const dbl2 *>(rc.pg_xy));
+    [[maybe_unused]] auto gid = as_global(rc.pg_id);
+    [[maybe_unused]] PageBuf pb;
+    if constexpr (BUF) pb = page_buf(rc);
     for (uint32_t r0 = 0; r0 < nreg; r0 += 64) {
         const uint32_t r = r0 + lane;
         uint32_t reg = 0, cnt = 0;
@@ -861,10 +941,17 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
                 int id[2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    const uint32_t sl = s0 + u < cnt ? s0 + u : 0u;
-                    v[u] = gxy[(size_t)reg * kPage + sl];
-                    id[u] = gid[(size_t)reg * kPage + sl];
+                    if constexpr (BUF) {
+                        const uint32_t at = s0 + u < cnt ? reg * kPage + s0 + u : kNoSlot;
+                        v[u] = page_xy(pb, at);
+                        id[u] = page_id(pb, at);
+                    } else {
+                        const uint32_t sl = s0 + u < cnt ? s0 + u : 0u;
+                        v[u] = gxy[(size_t)reg * kPage + sl];
+                        id[u] = gid[(size_t)reg * kPage + sl];
+                    }
                 }
+                if constexpr (BUF) __atomic_signal_fence(__ATOMIC_SEQ_CST);       // (the loads stay ahead of the first visit: see gscan_disc)
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     if (s0 + u < cmax) visit(v[u].x, v[u].y, id[u], s0 + u < cnt);
@@ -895,9 +982,16 @@ __device__ __forceinline__ void scan_disc(const RunConst &rc, uint32_t b, double
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {                 // only the filled slots are fetched
                     const bool ld = lane < pc[u];
-                    v[u] = ld ? gxy[(size_t)pg[u] * kPage + lane] : dbl2{0.0, 0.0};
-                    id[u] = ld ? gid[(size_t)pg[u] * kPage + lane] : -1;
+                    if constexpr (BUF) {
+                        const uint32_t at = ld ? pg[u] * kPage + lane : kNoSlot;
+                        v[u] = page_xy(pb, at);
+                        id[u] = page_id(pb, at);
+                    } else {
+                        v[u] = ld ? gxy[(size_t)pg[u] * kPage + lane] : dbl2{0.0, 0.0};
+                        id[u] = ld ? gid[(size_t)pg[u] * kPage + lane] : -1;
+                    }
                 }
+                if constexpr (BUF) __atomic_signal_fence(__ATOMIC_SEQ_CST);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     if (pc[u]) visit(v[u].x, v[u].y, id[u], lane < pc[u]);
@@ -1545,10 +1639,10 @@ static_assert(kLdsHits % 2u == 0u, "kLdsHits");
 constexpr uint32_t kHitBytes = kLdsHits * (4u + 8u + 8u + 8u);
 struct LdsHits {
     static constexpr bool kCompact = true;
-    int *hid;
-    double *hx, *hy, *hd;
-    GPTR(int) out_id;       // compact (id, candidate dist_root) list of the sample, read by commit_rrt_sample
-    GPTR(double) out_val;
+    LdsPtr<int> hid;
+    LdsPtr<double> hx, hy, hd;
+    HitRow<int> out_id;     // compact (id, candidate dist_root) list of the sample, read by commit_rrt_sample
+    HitRow<double> out_val;
     GPTR(uint32_t) out_cnt;
     uint32_t out_cap;
     __device__ __forceinline__ int id(uint32_t a) const { return hid[a]; }
@@ -1560,11 +1654,11 @@ struct LdsHits {
 };
 struct MemHits {
     static constexpr bool kCompact = true;
-    GPTR(int) sid;
-    GPTR(dbl2) sxy;
-    GPTR(double) sd;
-    GPTR(int) out_id;
-    GPTR(double) out_val;
+    HitRow<int> sid;
+    HitRow<dbl2> sxy;
+    HitRow<double> sd;
+    HitRow<int> out_id;
+    HitRow<double> out_val;
     GPTR(uint32_t) out_cnt;
     uint32_t out_cap;
     __device__ __forceinline__ int id(uint32_t a) const { return sid[a]; }
@@ -1872,7 +1966,15 @@ __device__ void connect_rrt_sample(const RunConst &rc, const TeamT &tm, const Li
                     j = a0 == 0 ? j0 : L.id(a);
                     if (nvalid != 0 && cost >= 0.0 && j != best) {
                         const double v = dnew + cost;
+#if PORRT_PAGE_LOADS
+                        // (the group kernels' lists: the node's word at a 32-bit offset off the scalar base; j >= 0 -- a listed neighbour)
+                        if (v < (a0 == 0 ? dA0 : L.dA(a, j))) {
+                            g_atomic_min(g_ptr(reinterpret_cast<unsigned long long *>(swap ? rc.distA : rc.distB), (uint32_t)j * 8u), f64_bits(v));
+                            via = v;
+                        }
+#else
                         if (v < (a0 == 0 ? dA0 : L.dA(a, j))) { g_atomic_min(gdB + j, f64_bits(v)); via = v; }
+#endif
                     }
                 }
                 const unsigned long long hm = tm.ballot(via >= 0.0);

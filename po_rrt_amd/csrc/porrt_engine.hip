@@ -1300,13 +1300,18 @@ int porrt_ctx::grow_once(const double start[2], double max_step, double search_r
         HIPCHK(d_qx.reserve(2 * Kpad)); HIPCHK(d_qy.reserve(2 * Kpad)); HIPCHK(d_qnn.reserve(2 * Kpad)); HIPCHK(d_qvid.reserve(2 * Kpad));      // two halves: pipelined steps (q_stride)
         // region pages: one static page per region + a pool that cannot run out (sum of ceil(n_r / 64) <= N / 64 + regions)
         const uint64_t rg_maxp = Nmax / kPage + 2, pg_cap = 2ull * kRegions + Nmax / kPage + 8;
+        // the searches read the pages as buffers with 32-bit byte offsets (PageBuf): the largest array, 16 B per slot, stays below 4 GiB
+        if (16ull * pg_cap * kPage >= (1ull << 32)) { set_err("n_iter_max too large: a page array of 4 GiB or more"); return PORRT_ERR_CAPACITY; }
         HIPCHK(d_rgcnt.reserve(2 * kRegions)); HIPCHK(d_rgocc.reserve(2 * kOccWords)); HIPCHK(d_rgdir.reserve((size_t)kRegions * rg_maxp));
         HIPCHK(d_pgxy.reserve(2 * (size_t)pg_cap * kPage)); HIPCHK(d_pgid.reserve((size_t)pg_cap * kPage)); HIPCHK(d_pgd.reserve((size_t)pg_cap * kPage)); HIPCHK(d_slotof.reserve(Nmax));
         HIPCHK(d_candcnt.reserve(3 * (size_t)K)); HIPCHK(d_kdbox.reserve(Nmax)); HIPCHK(d_kdlosers.reserve(kClaimMax)); HIPCHK(d_bcscratch.reserve(8 * Nmax + 4096)); HIPCHK(d_bcout.reserve(1)); HIPCHK(d_bccursor.reserve(1)); HIPCHK(d_locbox.reserve(2 * (8 * (size_t)K + 4096))); HIPCHK(d_kdhint.reserve((size_t)kHG * kHG));
         HIPCHK(d_loccur.reserve(2 * (8 * (size_t)K + 4096))); HIPCHK(d_locdcur.reserve(2 * (8 * (size_t)K + 4096))); HIPCHK(d_locgex.reserve(2 * (8 * (size_t)K + 4096))); HIPCHK(d_locflags.reserve(2 * (8 * (size_t)K + 4096)));
         HIPCHK(d_gsnap.reserve((steps_max + 4) * 4)); HIPCHK(d_pendoff.reserve(pend_cap)); HIPCHK(d_pendn.reserve(pend_cap)); HIPCHK(d_pendcur.reserve(pend_cap));
         HIPCHK(d_pendstate.reserve(pend_cap)); HIPCHK(d_pendnew.reserve(pend_cap)); HIPCHK(d_pendpool.reserve(pool_cap)); HIPCHK(d_kdsurv.reserve(Nmax)); HIPCHK(d_gndx.reserve(Nmax)); HIPCHK(d_gndy.reserve(Nmax)); HIPCHK(d_gndbox.reserve(Nmax));
-        HIPCHK(d_kqx.reserve((steps_max + 2) * Kpad)); HIPCHK(d_kqy.reserve((steps_max + 2) * Kpad)); HIPCHK(d_kqvid.reserve((steps_max + 2) * Kpad)); { const size_t np = (opt_pipeline == 4 && stage != 1 && K <= 1024) ? 3u : 2u; HIPCHK(d_candid.reserve(np * (size_t)K * cand_cap)); HIPCHK(d_candxy.reserve(2 * np * (size_t)K * cand_cap)); HIPCHK(d_candval.reserve((np == 3u ? 3u : 1u) * (size_t)K * cand_cap)); }
+        HIPCHK(d_kqx.reserve((steps_max + 2) * Kpad)); HIPCHK(d_kqy.reserve((steps_max + 2) * Kpad)); HIPCHK(d_kqvid.reserve((steps_max + 2) * Kpad)); { const size_t np = (opt_pipeline == 4 && stage != 1 && K <= 1024) ? 3u : 2u;
+          // (the group kernels reach a sample's slice at a 32-bit byte offset off the row's base, Row32: 16 B per entry of cand_xy)
+          if (16ull * np * K * cand_cap >= (1ull << 32)) { set_err("cand_cap too large: a neighbour-list array of 4 GiB or more"); return PORRT_ERR_CAPACITY; }
+          HIPCHK(d_candid.reserve(np * (size_t)K * cand_cap)); HIPCHK(d_candxy.reserve(2 * np * (size_t)K * cand_cap)); HIPCHK(d_candval.reserve((np == 3u ? 3u : 1u) * (size_t)K * cand_cap)); }
         HIPCHK(d_gid.reserve(Nmax));
         HIPCHK(d_perm.reserve((steps_max + 2) * Kpad)); HIPCHK(d_ssx.reserve((steps_max + 2) * Kpad)); HIPCHK(d_ssy.reserve((steps_max + 2) * Kpad));
         HIPCHK(d_bqx.reserve(Kpad)); HIPCHK(d_bqy.reserve(Kpad)); HIPCHK(d_bqk.reserve(Kpad)); HIPCHK(d_t2at.reserve(steps_max + 4));

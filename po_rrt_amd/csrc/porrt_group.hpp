@@ -40,15 +40,24 @@ __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const
     const uint32_t w = (uint32_t)(cx1 - cx0 + 1), nreg = w * (uint32_t)(cy1 - cy0 + 1);
     constexpr int U = (int)kPage / GL;
     if (nreg * 16u > N) {           // young tree: streaming the id-ordered arrays is cheaper than walking empty regions
+#if !PORRT_PAGE_LOADS
         auto gx = as_global(rc.nx), gy = as_global(rc.ny), gdA = as_global(rc.distA);
+#endif
         for (uint32_t j0 = 0; j0 < N; j0 += (uint32_t)(U * GL)) {
             double x[U], y[U], d[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const uint32_t j = j0 + (uint32_t)(GL * u) + gl;
+#if PORRT_PAGE_LOADS
+                const uint32_t o = (j < N ? j : 0u) * 8u;        // (N < nreg * 16 here: the byte offset fits by far)
+                x[u] = g_at(rc.nx, o);
+                y[u] = g_at(rc.ny, o);
+                d[u] = WITHD ? g_at(rc.distA, o) : 0.0;
+#else
                 x[u] = gx[j < N ? j : 0u];
                 y[u] = gy[j < N ? j : 0u];
                 d[u] = WITHD ? gdA[j < N ? j : 0u] : 0.0;
+#endif
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -58,9 +67,13 @@ __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const
     }
     auto gcnt = as_global(rc.rg_cnt) + (b & 1u) * kRegions;
     auto gdir = as_global(rc.rg_dir);
+#if PORRT_PAGE_LOADS
+    const PageBuf pb = page_buf(rc);
+#else
     auto gxy = as_global(reinterpret_cast<const dbl2 *>(rc.pg_xy));
     auto gid = as_global(rc.pg_id);
     auto gpd = as_global(rc.pg_d);
+#endif
     for (uint32_t r0 = 0; r0 < nreg; r0 += (uint32_t)GL) {
         const uint32_t r = r0 + gl;
         uint32_t reg = 0, cnt = 0;
@@ -99,10 +112,22 @@ __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const
                     for (int u = 0; u < U; ++u) {                 // only the filled slots are fetched
                         const uint32_t sl = (uint32_t)(u * GL) + gl;
                         const bool ld = sl < pc[q];
+#if PORRT_PAGE_LOADS
+                        const uint32_t at = ld ? pg[q] * kPage + sl : kNoSlot;       // (a lane past the fill: zeros, and no fetch)
+                        v[q][u] = page_xy(pb, at);
+                        id[q][u] = page_id(pb, at);
+                        d[q][u] = WITHD ? page_d(pb, at) : 0.0;
+#else
                         v[q][u] = ld ? gxy[(size_t)pg[q] * kPage + sl] : dbl2{0.0, 0.0};
                         id[q][u] = ld ? gid[(size_t)pg[q] * kPage + sl] : -1;
                         d[q][u] = (WITHD && ld) ? gpd[(size_t)pg[q] * kPage + sl] : 0.0;
+#endif
                     }
+#if PORRT_PAGE_LOADS
+                // (a compiler fence, no instruction: without a guard around them the first row's loads are otherwise sunk into its visit --
+                // the coordinates behind the "row is not empty" test, id and distance behind the hit test: a trip of their own per round)
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+#endif
 #pragma unroll
                 for (int q = 0; q < R; ++q)
 #pragma unroll
@@ -235,8 +260,12 @@ __device__ __forceinline__ double nn_bound_group(const RunConst &rc, const GTeam
 template <int GL, class Visit>
 __device__ __forceinline__ void gscan_region(const RunConst &rc, const GTeam<GL> &tm, uint32_t reg, uint32_t cnt, Visit visit) {
     auto gdir = as_global(rc.rg_dir);
+#if PORRT_PAGE_LOADS
+    const PageBuf pb = page_buf(rc);
+#else
     auto gxy = as_global(reinterpret_cast<const dbl2 *>(rc.pg_xy));
     auto gid = as_global(rc.pg_id);
+#endif
     constexpr int U = (int)kPage / GL, RP = PORRT_REG_PAGES;
     const uint32_t npages = (cnt + kPage - 1u) / kPage;
     for (uint32_t j0 = 0; j0 < npages; j0 += (uint32_t)RP) {
@@ -258,9 +287,18 @@ __device__ __forceinline__ void gscan_region(const RunConst &rc, const GTeam<GL>
             for (int u = 0; u < U; ++u) {
                 const uint32_t sl = (uint32_t)(u * GL) + tm.gl;
                 const bool ld = sl < pc[q];
+#if PORRT_PAGE_LOADS
+                const uint32_t at = ld ? page[q] * kPage + sl : kNoSlot;
+                v[q][u] = page_xy(pb, at);
+                id[q][u] = page_id(pb, at);
+#else
                 v[q][u] = ld ? gxy[(size_t)page[q] * kPage + sl] : dbl2{0.0, 0.0};
                 id[q][u] = ld ? gid[(size_t)page[q] * kPage + sl] : -1;
+#endif
             }
+#if PORRT_PAGE_LOADS
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);        // (all loads of the round are issued before the first visit: see gscan_disc)
+#endif
 #pragma unroll
         for (int q = 0; q < RP; ++q)
 #pragma unroll
@@ -487,20 +525,28 @@ __device__ __forceinline__ void commit_flat_span(const RunConst &rc, uint32_t cb
         }
         span_prefix_lane(s_prefix, tid, c, incl - s);
     }
+#if !PORRT_PAGE_LOADS
     auto gdA = as_global(rc.distA);
     auto gpd = as_global(rc.pg_d);
     auto gso = as_global(rc.slot_of);
+#endif
     // the new nodes' own dist_root goes to their page slots (filed by insert_step_pages beside the connect pass)
     for (uint32_t t = tid; t < kSpan; t += T)
         if (k0 + t < limit && span_valid(words, t)) {
             const uint32_t id = base + span_rank_in(words, t);
+#if PORRT_PAGE_LOADS
+            *g_ptr(rc.pg_d, g_at(rc.slot_of, id * 4u) * 8u) = g_at(rc.distA, id * 8u);        // (32-bit offsets off the scalar bases, here and below)
+#else
             gpd[gso[id]] = gdA[id];
+#endif
         }
     __syncthreads();
     const uint32_t total = s_prefix[kSpan];
+#if !PORRT_PAGE_LOADS
     auto gcid = as_global(rc.cand_id);
     auto gcval = as_global(rc.cand_val);
     auto gdB = as_global(rc.distB);
+#endif
     // four records per lane in flight, each a chain of dependent loads (record -> distB[j] -> parent[j]); the dense first steps of a
     // run leave tens of thousands of records per row
     constexpr int U = 4;
@@ -513,25 +559,44 @@ __device__ __forceinline__ void commit_flat_span(const RunConst &rc, uint32_t cb
             via[u] = -1.0; j[u] = 0; id[u] = 0;
             if (r < total) {
                 const uint32_t t = span_find(s_prefix, r), a = r - s_prefix[t];       // a < the sample's clamped count <= cand_cap
+#if PORRT_PAGE_LOADS
+                via[u] = g_at(rc.cand_val, ((uint32_t)cand_val_off(rc, cb, k0 + t) + a) * 8u);
+                j[u] = g_at(rc.cand_id, ((uint32_t)cand_off(rc, cb, k0 + t) + a) * 4u);
+#else
                 via[u] = gcval[cand_val_off(rc, cb, k0 + t) + a];
                 j[u] = gcid[cand_off(rc, cb, k0 + t) + a];
+#endif
                 id[u] = (int)(base + span_rank_in(words, t));
             }
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) dB[u] = via[u] >= 0.0 ? gdB[j[u]] : 0.0;            // (the uncompacted list of the goal-point copies' leader holds negative entries)
+        // (the uncompacted list of the goal-point copies' leader holds negative entries: an id is used only behind this test)
+#if PORRT_PAGE_LOADS
+        for (int u = 0; u < U; ++u) dB[u] = via[u] >= 0.0 ? g_at(rc.distB, (uint32_t)j[u] * 8u) : 0.0;
+#else
+        for (int u = 0; u < U; ++u) dB[u] = via[u] >= 0.0 ? gdB[j[u]] : 0.0;
+#endif
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!(via[u] >= 0.0) || f64_bits(via[u]) != f64_bits(dB[u])) continue;
+#if PORRT_PAGE_LOADS
+            auto gpar = g_ptr(rc.parent, (uint32_t)j[u] * 4u);
+#else
             auto gpar = as_global(rc.parent) + j[u];
+#endif
             int old = *gpar;
             while (old < N || id[u] < old) {        // parents from before this step are always < N
                 int expect = old;
                 if (__hip_atomic_compare_exchange_strong(gpar, &expect, id[u], __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
                 old = expect;
             }
+#if PORRT_PAGE_LOADS
+            *g_ptr(rc.distA, (uint32_t)j[u] * 8u) = via[u];
+            *g_ptr(rc.pg_d, g_at(rc.slot_of, (uint32_t)j[u] * 4u) * 8u) = via[u];
+#else
             gdA[j[u]] = via[u];
             gpd[gso[j[u]]] = via[u];
+#endif
         }
     }
 }
@@ -733,7 +798,7 @@ __device__ __forceinline__ void list_scan_wave(const RunConst &rc, uint32_t b, u
     const uint32_t cap = rc.cand_cap;
     uint32_t tot = 0;
     bool over = false;
-    scan_disc(rc, b, pxh, pyh, disc_radius(T2, pxh, pyh), uni(N), lane, [&](double x, double y, int jd, bool ok) {
+    scan_disc<PORRT_PAGE_LOADS != 0>(rc, b, pxh, pyh, disc_radius(T2, pxh, pyh), uni(N), lane, [&](double x, double y, int jd, bool ok) {
         const bool in = ok && dist2(x, y, pxh, pyh) <= T2;
         const unsigned long long hm = __ballot(in);
         const uint32_t pos = tot + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
@@ -762,7 +827,7 @@ __device__ __forceinline__ void list_scan_waves(const RunConst &rc, uint32_t b, 
     auto cxy = as_global(reinterpret_cast<dbl2 *>(rc.cand_xy)) + cand_off(rc, b, kh);
     const uint32_t cap = rc.cand_cap;
     bool over = false;
-    scan_disc(rc, b, pxh, pyh, disc_radius(T2, pxh, pyh), uni(N), lane, [&](double x, double y, int jd, bool ok) {
+    scan_disc<PORRT_PAGE_LOADS != 0>(rc, b, pxh, pyh, disc_radius(T2, pxh, pyh), uni(N), lane, [&](double x, double y, int jd, bool ok) {
         const bool in = ok && dist2(x, y, pxh, pyh) <= T2;
         const unsigned long long hm = __ballot(in);
         if (!hm) return;
@@ -852,9 +917,15 @@ __device__ __attribute__((noinline)) void clone_workgroup(const RunConst &rc_arg
 
 __device__ __forceinline__ MemHits mem_hits(const RunConst &rc, uint32_t b, uint32_t k) {
     MemHits M;
+#if PORRT_PAGE_LOADS
+    M.sid = {rc.cand_id, (uint32_t)cand_off(rc, b, k)};
+    M.sxy = {reinterpret_cast<dbl2 *>(rc.cand_xy), (uint32_t)cand_off(rc, b, k)};
+    M.sd = {rc.cand_val, (uint32_t)cand_val_off(rc, b, k)};
+#else
     M.sid = as_global(rc.cand_id) + cand_off(rc, b, k);
     M.sxy = as_global(reinterpret_cast<dbl2 *>(rc.cand_xy)) + cand_off(rc, b, k);
     M.sd = as_global(rc.cand_val) + cand_val_off(rc, b, k);
+#endif
     M.out_id = M.sid;
     M.out_val = M.sd;
     M.out_cnt = as_global(rc.cand_cnt) + cand_cnt_at(rc, b, k);
@@ -867,8 +938,13 @@ __device__ __forceinline__ MemHits mem_hits(const RunConst &rc, uint32_t b, uint
 // most such samples) they are read back into those lists in one coalesced pass and the three passes of the connect run on LDS.
 template <int GL>
 __device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc_arg, uint32_t b, uint32_t N, uint32_t kh, uint32_t idh, uint32_t toth, int clrh,
-                                                            double pxh, double pyh, uint8_t *wb, uint32_t &err) {
+                                                            double pxh, double pyh, uint8_t *wb, uint32_t &err_out) {
     const RunConst &rc = rc_const(rc_arg);
+#if PORRT_PAGE_LOADS
+    uint32_t err = 0;                       // (the caller's word is a generic address: touched only when there is something to report)
+#else
+    uint32_t &err = err_out;
+#endif
     const uint32_t lane = threadIdx.x & 63u;
     constexpr uint32_t kWaveHits = (64u / (uint32_t)GL) * (kLdsHits * (uint32_t)(GL / 16));
     Team<1> tw;
@@ -880,10 +956,12 @@ __device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc_a
     PORRT_T0();
     if (toth <= kWaveHits) {
         LdsHits Wl;
-        Wl.hx = reinterpret_cast<double *>(wb);
+        // (wb always comes from lds_dyn but arrives here as a generic pointer: LdsPtr names the address space, so the lists are ds_* accesses
+        // and not flat_* ones, which count on both wait counters)
+        Wl.hx = (LdsPtr<double>)wb;
         Wl.hy = Wl.hx + kWaveHits;
         Wl.hd = Wl.hy + kWaveHits;
-        Wl.hid = reinterpret_cast<int *>(Wl.hd + kWaveHits);
+        Wl.hid = (LdsPtr<int>)(Wl.hd + kWaveHits);
         Wl.out_id = Mh.out_id; Wl.out_val = Mh.out_val; Wl.out_cnt = Mh.out_cnt; Wl.out_cap = Mh.out_cap;
         for (uint32_t a0 = 0; a0 < toth; a0 += 256u) {              // four entries per lane in flight
             int jd[4];
@@ -911,6 +989,9 @@ __device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc_a
         connect_rrt_sample(rc, tw, Mh, grid, b, kh, idh, pxh, pyh, toth < cap ? toth : cap, err, nullptr, 0, clrh,
                            [&]() { return wave_nn(rc, b, N, pxh, pyh); });
     }
+#if PORRT_PAGE_LOADS
+    if (err) err_out |= err;
+#endif
 }
 
 #ifndef PORRT_CONN2_WAVES
@@ -946,10 +1027,10 @@ __device__ __forceinline__ void conn2_wave(const RunConst &rc, uint32_t b, uint3
         constexpr uint32_t kHits = kLdsHits * (uint32_t)(GL / 16);
         uint8_t *hb = wl + (lane / (uint32_t)GL) * (kHits * 28u);
         LdsHits L;
-        L.hx = reinterpret_cast<double *>(hb);
+        L.hx = (LdsPtr<double>)hb;
         L.hy = L.hx + kHits;
         L.hd = L.hy + kHits;
-        L.hid = reinterpret_cast<int *>(L.hd + kHits);
+        L.hid = (LdsPtr<int>)(L.hd + kHits);
         const MemHits M = mem_hits(rc, b, k);
         L.out_id = M.out_id; L.out_val = M.out_val; L.out_cnt = M.out_cnt; L.out_cap = M.out_cap;
         PORRT_TACC_B(rc, 0);
