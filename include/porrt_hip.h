@@ -192,7 +192,9 @@ int      porrt_best_cost_batch(porrt_ctx *const *ctxs, uint32_t n_ctx, double *c
  * n_iter draws) or the injected stream.  Results through the getters of a PTO graph: porrt_num_nodes (n_iter + 1, node 0
  * = start), porrt_get_tree (coordinates; parents -1), porrt_num_edges / porrt_get_edges (the forward edges neighbour ->
  * new node in the reference's adjacency order; PTOGraph gets add_edge(from, to, 0) and add_edge(to, from, 0), the third
- * array is what transition_validator returned). */
+ * array is what transition_validator returned).  The edge list starts at 256 edges per node; a roadmap with more (its edges are
+ * counted before they are written) is grown again from the same sampler state with a list of the counted size, up to 2^30 edges
+ * (PORRT_ERR_CAPACITY beyond). */
 int      porrt_grow_prm(porrt_ctx *ctx, const double start[2], double max_step, double search_radius, uint64_t n_iter);
 /* PRM::plan_path (src/prm.rs:111-123) on that roadmap: the kd-tree's nearest nodes of start and goal
  * (nearest_neighbor.rs:48-91), dijkstra from the goal (src/pto_graph.rs:275-303; run as device sweeps to the same

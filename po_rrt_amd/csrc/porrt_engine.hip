@@ -342,6 +342,7 @@ struct porrt_ctx {
     uint64_t host_kd_tag = ~0ull;
     int ensure_edge_order();
     int grow_prm(const double start[2], double max_step, double search_radius, uint64_t n_iter);
+    int grow_prm_once(const double start[2], double max_step, double search_radius, uint64_t n_iter, uint64_t &edge_need);
     MmState mm;                            // porrt_grow_mm_prm: the mode tree and the modes' roadmaps
     GrowScratch mm_scratch;                //   and the device buffers of roadmaps_of_modes, kept across calls
     int grow_mm_prm(const double start[2], const double *initial_belief, uint32_t n_worlds_in, double max_step, double search_radius, uint64_t n_iter_per_belief);
@@ -1928,8 +1929,23 @@ int64_t porrt_ctx::reparent_call(const char *who, bool single, const ReparentGra
     return m;
 }
 
-// PRM::init + PRM::grow_graph (prm.rs:33-109); see porrt_prm.hpp.
+// PRM::init + PRM::grow_graph (prm.rs:33-109); see porrt_prm.hpp.  The edge list holds 256 edges per node to begin with.  The edges
+// are counted before they are written, so a roadmap that has more (samples confined to a window a few radii wide) is grown again
+// from the same sampler state with a list of the counted size.
 int porrt_ctx::grow_prm(const double start[2], double max_step, double search_radius, uint64_t n_iter_) {
+    const SamplerState s0(*this);
+    uint64_t edge_need = 0;
+    int r = grow_prm_once(start, max_step, search_radius, n_iter_, edge_need);
+    if (r == -102) {
+        s0.restore(*this);
+        r = grow_prm_once(start, max_step, search_radius, n_iter_, edge_need);
+        if (r == -102) { set_err("PRM edge list outgrew its counted size"); r = PORRT_ERR_CAPACITY; }
+    }
+    return r;
+}
+
+// one attempt: -102 with edge_need = the roadmap's edges when the list (256 per node, or edge_need if that is more) does not hold them
+int porrt_ctx::grow_prm_once(const double start[2], double max_step, double search_radius, uint64_t n_iter_, uint64_t &edge_need) {
     const uint64_t n_iter = n_iter_;
     if (!has_grid) { set_err("PRM growth needs a grid-backed domain (porrt_set_grid)"); return PORRT_ERR_INVALID; }
     if (!(max_step > 0.0) || !(search_radius > 0.0) || !start) { set_err("bad PRM parameters"); return PORRT_ERR_INVALID; }
@@ -1958,7 +1974,7 @@ int porrt_ctx::grow_prm(const double start[2], double max_step, double search_ra
     }
     double x0 = hx[0], x1 = hx[0], y0 = hy[0], y1 = hy[0];
     for (size_t i = 1; i < N; ++i) { x0 = std::min(x0, hx[i]); x1 = std::max(x1, hx[i]); y0 = std::min(y0, hy[i]); y1 = std::max(y1, hy[i]); }
-    const uint64_t ecap = std::min<uint64_t>((uint64_t)N * 256 + 4096, 1ull << 30);
+    const uint64_t ecap = std::min<uint64_t>(std::max<uint64_t>((uint64_t)N * 256 + 4096, edge_need), 1ull << 30);
     HIPCHK(d_nx.reserve(N)); HIPCHK(d_ny.reserve(N)); HIPCHK(d_distA.reserve(N)); HIPCHK(d_parent.reserve(N)); HIPCHK(d_reachA.reserve(N));
     HIPCHK(d_vid.reserve(N)); HIPCHK(d_finalflag.reserve(N)); HIPCHK(d_finalmask.reserve(N)); HIPCHK(d_radT2.reserve(N + 8));
     HIPCHK(d_cnt.reserve(1)); HIPCHK(d_rc.reserve(1)); HIPCHK(d_cls.reserve(cls_bytes(W, H)));       // classes + clearance plane (build_cls)
@@ -2038,7 +2054,8 @@ int porrt_ctx::grow_prm(const double start[2], double max_step, double search_ra
         bg_scan(prm.d_deg, N, prm.d_tot, prm.d_edge_off, stream);
         HIPCHK(hipMemcpyAsync(&n_edges, prm.d_edge_off + N, sizeof n_edges, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        if (n_edges > ecap) { set_err("PRM edge list outgrew its capacity (256 per node)"); return PORRT_ERR_CAPACITY; }
+        if (n_edges > (1ull << 30)) { set_err("PRM edge list: more than 2^30 edges"); return PORRT_ERR_CAPACITY; }
+        if (n_edges > ecap) { edge_need = n_edges; return -102; }
         hipLaunchKernelGGL(k_prm_connect<true>, wgrid, block, 0, stream, (const RunConst *)d_rc.p, p);
     }
     HIPCHK(hipEventRecord(ev1, stream));

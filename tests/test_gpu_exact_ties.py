@@ -352,9 +352,10 @@ def test_prm_sizes(eng_mod, n_iter):
     assert_same_roadmap(e, o)
 
 
-def test_prm_capacity_error_then_reuse(eng_mod):
-    """1200 points inside one radius make about 720 000 edges against a capacity of N * 256 + 4096 = 311 552: grow_prm raises (the check
-    precedes the fill), and the context then grows a small roadmap as if nothing had happened"""
+def test_prm_beyond_256_edges_per_node_then_reuse(eng_mod):
+    """1200 points inside one radius make about 720 000 edges against a first edge list of N * 256 + 4096 = 311 552: grow_prm counts them
+    before the fill and runs again with a list of that size (it used to end in a capacity error), and the context then grows a small
+    roadmap as usual"""
     pts = X.cluster(1200, (0.0, -0.8), 0.03, 2)
     o = orc.Oracle()
     o.set_grid(cases.load_map("map_benchmark_like"), (-1.0, -1.0), (1.0, 1.0), cases.SHELF)
@@ -364,8 +365,8 @@ def test_prm_capacity_error_then_reuse(eng_mod):
     e = eng_mod.Engine()
     e.set_grid(cases.load_map("map_benchmark_like"), (-1.0, -1.0), (1.0, 1.0), cases.SHELF)
     e.set_samples(pts)
-    with pytest.raises(eng_mod.PorrtError, match="capacity"):
-        e.grow_prm((0.0, -0.8), 0.1, 5.0, len(pts))
+    e.grow_prm((0.0, -0.8), 0.1, 5.0, len(pts))
+    assert_same_roadmap(e, o)
     xy = X.lattice(1 / 16, 1, 300)
     e.set_samples(xy)
     o.set_samples(xy)

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import cases
+from confined_inputs import hits_per_node as _hits_per_node, n_at as _n_at
 from oracle import orc
 from test_gpu_parity import assert_same
 
@@ -159,30 +160,12 @@ def test_fill_levels(eng_mod, fill_set, waves):
 DENSE_ITER = 3000
 
 
-def _n_at(case, steps):
-    return [1] + [_oracle(case, n_iter=s * K).num_nodes() for s in range(1, steps + 1)]
-
-
-def _hits_per_node(case, o, n_at):
-    """radius-search hits of every new node of the oracle's tree: the nodes of its step's snapshot within heuristic_radius(n)
-    (common.rs:357-369; the snapshot's size before insertion, rrt.rs:121)"""
-    x = o.tree()[0]
-    hits = np.zeros(len(x), dtype=int)
-    for s in range(len(n_at) - 1):
-        n0, n1 = n_at[s], n_at[s + 1]
-        r = orc.lib().orc_heuristic_radius(n0, case.max_step, case.search_radius, 2)
-        for i in range(n0, n1):
-            dx, dy = x[i, 0] - x[:n0, 0], x[i, 1] - x[:n0, 1]
-            hits[i] = np.count_nonzero(np.sqrt(dx * dx + dy * dy) <= r)
-    return hits
-
-
 @pytest.fixture(scope="module")
 def dense_set():
     case = cases.cfg2(DENSE_ITER, seed=7)
     o = _oracle(case)
     steps = (DENSE_ITER + K - 1) // K
-    n_at = _n_at(case, steps - 1) + [o.num_nodes()]
+    n_at = _n_at(case, steps - 1, K) + [o.num_nodes()]
     return case, o, n_at, _hits_per_node(case, o, n_at)
 
 
