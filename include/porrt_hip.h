@@ -706,7 +706,13 @@ int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a
  * profiler that serialises kernels), "pipeline", "group_lanes", "kd_lazy", "kd_built_after" (1: a tie of the last grow -- of the batch
  * this context led -- needed the whole kd structure, which was built after its steps), "kd_lca_steps" (this context's own need: 1 + the
- * last step with a tie that took that structure, 0 = none), "compactions" (how often the last batch this context led gathered the
+ * last step with a tie that took that structure, 0 = none), "kd_forms_run" (which forms of the kd side chain the last grow -- of the batch this
+ * context led -- launched, for tests that must know what they covered; a grow that replays a captured sequence reports its capture's.  Bits 0 .. 10: the
+ * instantiation of k_kd_claim -- 0: <2048> and 1: <4096>, one row with the engine's workgroup; 2 .. 9: one workgroup per row, nodes x threads 1024 x 256,
+ * 1024 x 512, 1024 x 1024, 2048 x 256, 2048 x 512, 2048 x 1024, 4096 x 512, 4096 x 1024; 10: a single query's side stream, the new nodes' coordinates in
+ * LDS.  11: k_kd_locate with one thread per node, 12: with one wave per node.  13: a group's hints and the deferred ties rode in the next group's locate
+ * kernel.  14: k_kd_hint and 15: k_kd_hint_fix after a group's claim.  16: k_tie_fix on the side stream after a group, beside the steps.  17: groups
+ * launched after the steps, by "kd_after" or because a tie asked under "kd_lazy"), "compactions" (how often the last batch this context led gathered the
  * members still running), "n_heavy" (samples of this context's last grow with more hits than their LDS list holds: served by a whole wave
  * from the lists in memory), "conn_wg_waves", "conn_riders_first", "riders_fast", "tim0" .. "tim15" (developer builds with -DPORRT_TIMING: the phase
  * timers of this context's last growth, 0 otherwise), "nn_wg_waves", "commit_flat", "cand_cap" (the neighbour-list capacity in force: larger than what was set after a call whose lists overflowed and which was replayed),

@@ -399,6 +399,7 @@ struct porrt_ctx {
     // cached hipGraph of the steps up to n_iter_min
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_key[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t graph_kd_forms = 0;           // LaunchSeq::kd_forms_run of the capture
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -806,27 +807,31 @@ void LaunchSeq::launch_step(uint32_t b, uint32_t i0, uint32_t nb, bool prof, siz
     if (!cx.opt_kd_after && !kd_lazy && b + 1 - kd_b0 >= kd_group) launch_kd_group();
 }
 
-// k_kd_claim of one group: the form by the group's size, the row count and (developer option) kd_claim_threads
-static void launch_kd_claim(hipStream_t st, const RunConst *rcp, uint32_t Q, uint32_t b0, uint32_t ns, uint32_t K, uint32_t vwords, uint32_t threads) {
+// k_kd_claim of one group: the form by the group's size, the row count and (developer option) kd_claim_threads.  Returns the KdForm
+// bit of the instantiation it launched.
+static uint32_t launch_kd_claim(hipStream_t st, const RunConst *rcp, uint32_t Q, uint32_t b0, uint32_t ns, uint32_t K, uint32_t vwords, uint32_t threads) {
     const uint64_t nodes = (uint64_t)ns * K;
     if (Q == 1 && threads == 0) {
-        if (nodes <= 2048u) hipLaunchKernelGGL(k_kd_claim<2048>, dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords);
-        else hipLaunchKernelGGL(k_kd_claim<kClaimMax>, dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords);
-        return;
+        if (nodes <= 2048u) { hipLaunchKernelGGL(k_kd_claim<2048>, dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords); return kKdfClaimOne2048; }
+        hipLaunchKernelGGL(k_kd_claim<kClaimMax>, dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords);
+        return kKdfClaimOneMax;
     }
     if (threads == 0) threads = 256u;
     if (nodes <= 1024u) {
-        if (threads <= 256u) hipLaunchKernelGGL((k_kd_claim<1024, false, 256>), dim3(1, Q), dim3(256), 0, st, rcp, b0, ns, vwords);
-        else if (threads <= 512u) hipLaunchKernelGGL((k_kd_claim<1024, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords);
-        else hipLaunchKernelGGL((k_kd_claim<1024, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
-    } else if (nodes <= 2048u) {
-        if (threads <= 256u) hipLaunchKernelGGL((k_kd_claim<2048, false, 256>), dim3(1, Q), dim3(256), 0, st, rcp, b0, ns, vwords);
-        else if (threads <= 512u) hipLaunchKernelGGL((k_kd_claim<2048, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords);
-        else hipLaunchKernelGGL((k_kd_claim<2048, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
-    } else {
-        if (threads <= 512u) hipLaunchKernelGGL((k_kd_claim<kClaimMax, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords);
-        else hipLaunchKernelGGL((k_kd_claim<kClaimMax, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
+        if (threads <= 256u) { hipLaunchKernelGGL((k_kd_claim<1024, false, 256>), dim3(1, Q), dim3(256), 0, st, rcp, b0, ns, vwords); return kKdfClaimRows1024x256; }
+        if (threads <= 512u) { hipLaunchKernelGGL((k_kd_claim<1024, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords); return kKdfClaimRows1024x512; }
+        hipLaunchKernelGGL((k_kd_claim<1024, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
+        return kKdfClaimRows1024x1024;
     }
+    if (nodes <= 2048u) {
+        if (threads <= 256u) { hipLaunchKernelGGL((k_kd_claim<2048, false, 256>), dim3(1, Q), dim3(256), 0, st, rcp, b0, ns, vwords); return kKdfClaimRows2048x256; }
+        if (threads <= 512u) { hipLaunchKernelGGL((k_kd_claim<2048, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords); return kKdfClaimRows2048x512; }
+        hipLaunchKernelGGL((k_kd_claim<2048, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
+        return kKdfClaimRows2048x1024;
+    }
+    if (threads <= 512u) { hipLaunchKernelGGL((k_kd_claim<kClaimMax, false, 512>), dim3(1, Q), dim3(512), 0, st, rcp, b0, ns, vwords); return kKdfClaimRowsMaxx512; }
+    hipLaunchKernelGGL((k_kd_claim<kClaimMax, false, 1024>), dim3(1, Q), dim3(1024), 0, st, rcp, b0, ns, vwords);
+    return kKdfClaimRowsMaxx1024;
 }
 
 // The kernels of one kd group -- steps [b0, b0 + ns), the last of them with nb_last samples -- on stream st: locate, link, claim and
@@ -836,11 +841,14 @@ static void launch_kd_claim(hipStream_t st, const RunConst *rcp, uint32_t Q, uin
 void LaunchSeq::kd_group_on(hipStream_t st, uint32_t b0, uint32_t ns, uint32_t nb_last, uint32_t wait, uint32_t hint_b0, uint32_t hint_ns, KdClaim claim, KdThen then) {
     const uint32_t per_node = (ns * K + 255) / 256;
     const uint32_t extra = hint_ns ? (hint_ns * K + 255) / 256 + kTieParts : 0;
-    if ((uint64_t)ns * K * Q >= 4096u) hipLaunchKernelGGL(k_kd_locate<1>, dim3(per_node + extra, Q), dim3(256), 0, st, rcp, b0, ns, K, nb_last, vwords, wait, hint_b0, hint_ns);
+    const bool few = (uint64_t)ns * K * Q < 4096u;
+    if (!few) hipLaunchKernelGGL(k_kd_locate<1>, dim3(per_node + extra, Q), dim3(256), 0, st, rcp, b0, ns, K, nb_last, vwords, wait, hint_b0, hint_ns);
     else hipLaunchKernelGGL(k_kd_locate<64>, dim3((ns * K * 64 + 255) / 256 + extra, Q), dim3(256), 0, st, rcp, b0, ns, K, nb_last, vwords, wait, hint_b0, hint_ns);
     hipLaunchKernelGGL(k_kd_link, dim3(per_node, Q), dim3(256), 0, st, rcp, b0, ns, vwords, 0u);
-    if (claim == KdClaim::SingleSide) hipLaunchKernelGGL((k_kd_claim<kClaimMax, true>), dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords);
-    else launch_kd_claim(st, rcp, Q, b0, ns, K, vwords, claim == KdClaim::Plain ? 0u : cx.opt_claim_threads);
+    uint32_t ran = (few ? kKdfLocate64 : kKdfLocate1) | (hint_ns ? kKdfHintsRide : 0u) | (then == KdThen::Hint ? kKdfHint : then == KdThen::HintFix ? kKdfHintFix : 0u);
+    if (claim == KdClaim::SingleSide) { hipLaunchKernelGGL((k_kd_claim<kClaimMax, true>), dim3(1, 1), dim3(1024), 0, st, rcp, b0, ns, vwords); ran |= kKdfClaimSingleSide; }
+    else ran |= launch_kd_claim(st, rcp, Q, b0, ns, K, vwords, claim == KdClaim::Plain ? 0u : cx.opt_claim_threads);
+    kd_forms_run |= ran;
     if (then == KdThen::Hint) hipLaunchKernelGGL(k_kd_hint, dim3(per_node, Q), dim3(256), 0, st, rcp, b0, ns, vwords);
     else if (then == KdThen::HintFix) hipLaunchKernelGGL(k_kd_hint_fix, dim3(per_node + kTieParts, Q), dim3(256), 0, st, rcp, b0, ns, vwords);
 }
@@ -871,6 +879,7 @@ void LaunchSeq::launch_kd_group() {
         (void)hipEventRecord(cx.ev_step_done, stream);
         (void)hipStreamWaitEvent(stream2, cx.ev_step_done, 0);
         hipLaunchKernelGGL(k_tie_fix<256>, dim3(1, Q), dim3(256), 0, stream2, rcp);       // (Q > 1 here)
+        kd_forms_run |= kKdfTieFixBeside;
     }
     // A lagging join: the main stream waits for the group BEFORE this one, which had a whole group of steps to finish.
     // It bounds how far the kd structure may fall behind and keeps a replayed hipGraph from running the side branch last.
@@ -920,6 +929,7 @@ void LaunchSeq::begin(const RunConst *rows, uint32_t n_rows, uint32_t K_, int mo
     opt_group = f.group; pipe_on = f.pipe; lag_on = f.lag; kd_lazy = f.kd_lazy;
     kd_group = kd_group_for(K_, cx.opt_kd_group, n_rows);
     kd_built_after = 0;
+    kd_forms_run = 0;
     lag_near_done = pipe_near_done = 0xFFFFFFFFu;
     kd_last_b = 0; kd_last_nb = 0;
     gt_pend = false; gt_par = 0;
@@ -983,9 +993,11 @@ int LaunchSeq::replay_steps(uint64_t n_iter, double *t_capture) {
         HIPCHK_CTX(&cx, hipGraphInstantiate(&cx.graph_exec, g, nullptr, nullptr, 0));
         (void)hipGraphDestroy(g);
         memcpy(cx.graph_key, key, sizeof key);
+        cx.graph_kd_forms = kd_forms_run;
         if (t_capture) *t_capture += now_s() - t0;
     }
     HIPCHK_CTX(&cx, hipGraphLaunch(cx.graph_exec, cx.stream));
+    kd_forms_run = cx.graph_kd_forms;          // (a replay launches what its capture launched)
     steps_ran((uint32_t)((n_iter + K - 1) / K));
     return PORRT_OK;
 }
@@ -1048,6 +1060,7 @@ void LaunchSeq::join_side() {
     if (cx.opt_kd_after || kd_build_now) {
         // the whole structure now, on the main stream: groups of as many steps as the claim kernel holds, in id order
         const uint32_t g = std::max<uint32_t>(1u, std::min<uint32_t>(8u, kClaimMax / K));
+        if (kd_b0 <= kd_last_b) kd_forms_run |= kKdfBuiltAfter;
         while (kd_b0 <= kd_last_b) {
             const uint32_t ns = std::min<uint32_t>(g, kd_last_b - kd_b0 + 1), last = kd_b0 + ns - 1;
             kd_group_on(stream, kd_b0, ns, last == kd_last_b ? kd_last_nb : K, 0u, 0u, 0u, KdClaim::ByRows, KdThen::Hint);
@@ -5202,6 +5215,7 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "kd_lca_steps")) *value = (int64_t)c->counters.lca_next;      // this context's own need: 1 + the last step with a tie that took the structure
     else if (!strcmp(name, "compactions")) *value = c->n_compactions;               // how often the last batch this context led gathered its running rows
     else if (!strcmp(name, "kd_built_after")) *value = c->seq.kd_built_after;           // 1: a tie of the last grow needed the whole kd structure, built after the steps
+    else if (!strcmp(name, "kd_forms_run")) *value = c->seq.kd_forms_run;               // KdForm bits (porrt_launch.hpp): the forms of the kd side chain the last grow launched
     else if (!strcmp(name, "n_heavy")) *value = (int64_t)c->counters.n_heavy;        // samples of this context's last grow with more hits than their LDS list holds (served by a whole wave)
     else if (!strcmp(name, "conn_wg_waves")) *value = c->opt_conn_wg_waves;
     else if (!strcmp(name, "conn_riders_first")) *value = c->opt_conn_riders_first ? 1 : 0;

@@ -32,6 +32,30 @@ enum class KdClaim { ByRows, SingleSide, Plain };
 enum class KdThen { Nothing, Hint, HintFix };
 using LaunchRows = std::pair<const RunConst *, uint32_t>;      // a RunConst array (one row of the grid per entry) and its rows
 
+// Which forms of the kd side chain a launch sequence launched: the bits of LaunchSeq::kd_forms_run (view "kd_forms_run", documented
+// in porrt_hip.h).  Host bookkeeping for the tests: no launch depends on it.
+enum KdForm : uint32_t {
+    kKdfClaimOne2048 = 1u << 0,         // k_kd_claim<2048>                      (one row, the engine's workgroup size)
+    kKdfClaimOneMax = 1u << 1,          // k_kd_claim<kClaimMax>
+    kKdfClaimRows1024x256 = 1u << 2,    // k_kd_claim<CAP, false, TPB>, one workgroup per row: CAP x TPB
+    kKdfClaimRows1024x512 = 1u << 3,
+    kKdfClaimRows1024x1024 = 1u << 4,
+    kKdfClaimRows2048x256 = 1u << 5,
+    kKdfClaimRows2048x512 = 1u << 6,
+    kKdfClaimRows2048x1024 = 1u << 7,
+    kKdfClaimRowsMaxx512 = 1u << 8,
+    kKdfClaimRowsMaxx1024 = 1u << 9,
+    kKdfClaimSingleSide = 1u << 10,     // k_kd_claim<kClaimMax, true>: a single query's side stream
+    kKdfLocate1 = 1u << 11,             // k_kd_locate<1>: one thread per node
+    kKdfLocate64 = 1u << 12,            // k_kd_locate<64>: one wave per node
+    kKdfHintsRide = 1u << 13,           // a group's hints and the deferred ties rode in the next group's locate kernel
+    kKdfHint = 1u << 14,                // k_kd_hint after a group's claim
+    kKdfHintFix = 1u << 15,             // k_kd_hint_fix after a group's claim (kd_inline: on the main stream)
+    kKdfTieFixBeside = 1u << 16,        // k_tie_fix<256> on the side stream after a group, beside the steps
+    kKdfBuiltAfter = 1u << 17,          // groups launched after the steps on the main stream (kd_after, or kd_lazy when a tie asked)
+    kKdfAll = (1u << 18) - 1u
+};
+
 struct LaunchSeq {
     porrt_ctx &cx;
     explicit LaunchSeq(porrt_ctx &c) : cx(c) {}
@@ -44,6 +68,7 @@ struct LaunchSeq {
     bool pipe_on = false, lag_on = false, kd_lazy = false;
     uint32_t kd_group = 1;             // steps per kd insertion
     int kd_built_after = 0;            // 1: a tie of this sequence needed the whole kd structure, built after the steps
+    uint32_t kd_forms_run = 0;         // KdForm bits of what this sequence launched (a replayed capture: of what the capture launched)
     // ---- advanced per step
     uint32_t commit_pend_b = 0xFFFFFFFFu, commit_pend_nb = 0;      // step whose rewire phase 2 rides in the next search kernel
     uint32_t lag_near_done = 0xFFFFFFFFu, pipe_near_done = 0xFFFFFFFFu;    // one kernel per step / pipelined: the step whose search (and filing) is already launched

@@ -211,6 +211,57 @@ def rrt_decimal_case():
     return c
 
 
+# ---------------------------------------------------------------------------------------------------------------------- kd forms
+# The inputs of tests/test_gpu_kd_forms.py (the kd tie-order side chain in every form) and of their CPU side,
+# tests/test_kd_forms_inputs_cpu.py.  A key is (stream, seed, K, n_iter_min, n_iter_max):
+#   "lattice":    rrt_lattice_case() fed lattice(1/16, seed, n_iter_max), cycled past its 961 points: ties between different places;
+#   "chain":      cases.empty_space from (-0.9, -0.9) fed staircase(n): a kd-tree that is (nearly) one chain, in which nearly every
+#                 new node of a group bids for the same child slot; ties between copies at one place;
+#   "duplicates": cfg2 fed _dup_samples of test_gpu_parity_r3.py (exact copies of other samples): equal-cost parents off the goal path.
+KDF_SEEDS = tuple(range(8))
+KDF_CLAIM = {128: (1, 2000), 256: (4, 2500), 512: (4, 4500), 1024: (4, 9000)}      # K: (kd_group, n_iter): two full groups and a short one at least
+KDF_LOCATE64 = (64, (3, 0), 2000)          # K, the seeds of its two rows, n_iter: 8 steps * 64 * 2 rows < 4096 nodes a group
+KDF_VARIANT_K, KDF_VARIANT_ITERS, KDF_VARIANT_SEEDS = 256, 2500, tuple(range(9))
+KDF_CHAIN_K, KDF_CHAIN_ITERS = 256, 3000
+KDF_SINGLE = (("lattice", SINGLE_SEED, 64, 2000), ("lattice", SINGLE_SEED, 1024, 9000), ("chain", 0, KDF_CHAIN_K, KDF_CHAIN_ITERS))
+KDF_ROWS_K = 128
+KDF_SEQ_ITERS, KDF_SEQ_K, KDF_SEQ_CHECKED = 3000, 256, (0, 4)          # (N_ITER and K of test_gpu_launch_sequences.py, the contexts it compares)
+KDF_DUP_SAMPLES, KDF_DUP_K = 4000, 512
+KDF_DUP_ITERS = KDF_DUP_SAMPLES - KDF_DUP_SAMPLES // 100 - 5           # (every 100th iteration takes the goal point and draws nothing)
+
+
+def kd_forms_inputs(stream, seed, n_iter_min, n_iter_max):
+    """(case, injected samples) of a key"""
+    import cases
+    if stream == "lattice":
+        c, xy = rrt_lattice_case(), lattice(1 / 16, seed, n_iter_max)
+    elif stream == "chain":
+        c, xy = cases.empty_space(), staircase(n_iter_max)
+        c.update(name="empty_staircase", start=(-0.9, -0.9))
+    elif stream == "duplicates":
+        from test_gpu_parity_r3 import _dup_samples
+        c, xy = cases.cfg2(), _dup_samples(KDF_DUP_SAMPLES, 20 + seed)
+    else:
+        raise ValueError(stream)
+    c.update(n_iter_min=n_iter_min, n_iter_max=n_iter_max)
+    return c, xy
+
+
+def kd_forms_keys():
+    """every key the GPU file grows an oracle for, once each, in a fixed order"""
+    keys = []
+    for K, (_, n) in sorted(KDF_CLAIM.items()):
+        keys += [("lattice", s, K, n, n) for s in KDF_SEEDS]
+    K, seeds, n = KDF_LOCATE64
+    keys += [("lattice", s, K, n, n) for s in seeds]
+    keys += [("lattice", s, KDF_VARIANT_K, KDF_VARIANT_ITERS, KDF_VARIANT_ITERS) for s in KDF_VARIANT_SEEDS]
+    keys += [(st, s, K, n, n) for st, s, K, n in KDF_SINGLE]
+    keys += [("lattice", s, KDF_ROWS_K, ROW_MIN[s], ROW_MAX[s]) for s in KDF_SEEDS]
+    keys += [("lattice", s, KDF_SEQ_K, a, KDF_SEQ_ITERS) for s in KDF_SEQ_CHECKED for a in (KDF_SEQ_ITERS, 1000)]
+    keys += [("duplicates", s, KDF_DUP_K, KDF_DUP_ITERS, KDF_DUP_ITERS) for s in KDF_SEEDS]
+    return list(dict.fromkeys(keys))
+
+
 PTO_ITERS = 2500
 
 

@@ -4,7 +4,9 @@ The other GPU tests grow a fresh context (or the same form twice) per launch for
 growths that alternates batches and single grows and changes the form from one to the next -- group kernels, one kernel per step,
 the goal path on the side stream, the kd chain beside the steps and on the main stream, pipelined pairs, rows with plans of
 their own, the persistent step loop -- so that whatever one sequence leaves behind (a pending rewire commit, a kd group counter,
-an event still marked pending, rows switched to a compacted array) would show in the trees of the next.
+an event still marked pending, rows switched to a compacted array) would show in the trees of the next.  (What the kd chain leaves
+behind shows only where two parents tie bit for bit, which these inputs never make: tests/test_gpu_kd_forms.py runs SEQUENCE on
+lattice streams, where they do.)
 """
 import numpy as np
 import pytest

@@ -345,7 +345,8 @@ def test_engine_options_do_not_change_results(eng_mod, opts):
     """the developer options measured in DESIGN.md section 8 (the whole kd structure beside the steps instead of the goal path alone
     -- kd_lazy = 0, with its variants: after the steps, hints riding in the locate kernel, group sizes, claim workgroup sizes; kd_lazy = 2, the
     old name of what is now a single query's default too: the goal path's workgroup in its step kernel --, the first steps' connect pass with one wave per sample): same
-    trees from a batch of nine and from a single query"""
+    trees from a batch of nine and from a single query.  (These inputs hold no two parents of bit-equal cost, so no run here consults
+    the kd structure: the forms are read on tie-making streams in tests/test_gpu_kd_forms.py.)"""
     cs = [cases.cfg2(12000, seed=30 + s) for s in range(9)]
     engs = [cases.configure(eng_mod.Engine(), c) for c in cs]
     for e in engs:
