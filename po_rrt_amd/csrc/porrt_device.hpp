@@ -203,6 +203,138 @@ struct BestCost {
 };
 
 typedef float flt2 __attribute__((ext_vector_type(2)));
+// -DPORRT_STEP_TRIPS=0: the run constants in the order they grew in, and the step kernels' set-up loads where they were (the A/B of
+// profiles/step_trips_experiments.txt).  1: the fields the step kernels (k_nn2, k_conn2, k_conn2_riders) read in every wave lie at the
+// front of a row, in the order of the phases that read them, and the large tables behind everything else; the kernels ask for a
+// phase's fields together (rc_hold) and for the vector loads of a phase that depend on the same values in one trip.
+#ifndef PORRT_STEP_TRIPS
+#define PORRT_STEP_TRIPS 1
+#endif
+// (its pieces one by one, for the measurements: the layout and RC_HOLD go with PORRT_STEP_TRIPS itself, the merged trips of k_nn2's search
+// and of the connect pass's set-up each have a switch of their own that follows it)
+#ifndef PORRT_STEP_TRIPS_NN2
+#define PORRT_STEP_TRIPS_NN2 PORRT_STEP_TRIPS
+#endif
+#ifndef PORRT_STEP_TRIPS_CONN2
+#define PORRT_STEP_TRIPS_CONN2 PORRT_STEP_TRIPS
+#endif
+#if PORRT_STEP_TRIPS
+struct RunConst {
+    // ---- the hot block: what the step kernels read in every wave, 64-byte lines in the order of their phases (a row starts on a line:
+    // the size is a multiple of 64 and the arrays of rows come from hipMalloc).  The fields are described at their places below (#else).
+    // lines 0-1: a step's preamble, the samples of k_nn2, the pixel of a state
+    uint32_t *sched_nb, *sched_i0;
+    uint32_t *n_at;
+    double *t2_at;
+    uint16_t *perm;
+    double *ssx, *ssy;
+    uint32_t part_stride, q_stride;
+    double max_step;
+    int has_grid, domain;
+    uint32_t W, H;
+    double low0, low1, ppm;
+    const uint8_t *cls;
+    const uint8_t *clr;
+    // lines 2-3: the bound pyramid and the region pages (the unsteered test, both searches, the filing)
+    double bx0, by0, binv_w, binv_h;
+    flt2 *rep_f;
+    int *rep;
+    uint32_t *rg_cnt;
+    unsigned long long *rg_occ;
+    uint32_t *rg_dir;
+    double *pg_xy;
+    int *pg_id;
+    double *pg_d;
+    uint32_t rg_maxp, pg_cap;
+    uint32_t *slot_of;
+    double *nx, *ny;
+    // lines 4-6: the hand-over from k_nn2 to the connect pass, the lists, the new node, the rewire commit
+    uint16_t *bq_k;
+    double *bq_x, *bq_y;
+    unsigned long long *valid_mask;
+    double *distA, *distB;
+    int *parent;
+    Counters *cnt;
+    uint32_t *cand_cnt;
+    int *cand_id;
+    double *cand_val;
+    double *cand_xy;
+    uint32_t cand_cap, cand_K;
+    uint32_t cand_par3, kd_lazy;
+    double *q_x, *q_y;
+    int *q_nn;
+    int *q_vid;
+    double *kq_x, *kq_y;
+    int *kq_vid;
+    // lines 6-9: the goal, the rays outside the clearance window, equal costs (kd order, deferred parents)
+    int goal_kind;
+    uint32_t G;
+    double gp_x, gp_y;
+    double g_l1;
+    uint8_t *final_flag;
+    unsigned long long *final_mask;
+    const uint32_t *sat;
+    double zone_x, zone_y, visibility;
+    KdRec *kd_rec;
+    int *kd_up;
+    uint32_t *kd_depth;
+    uint32_t *kd_gexit;
+    int *pend_new, *pend_pool;
+    uint32_t *pend_off, *pend_n, *pend_cur, *pend_state;
+    uint32_t pend_cap, pool_cap;
+    // lines 9-10: the goal path of the kd order (the riders), the radius table
+    double *g_x, *g_y;
+    int *g_id;
+    uint32_t *g_nd;
+    double *g_nd_x, *g_nd_y;
+    KdBox *g_nd_box;
+    uint32_t g_cap, tile_R;
+    const double *rad_T2;
+    // ---- everything else
+    unsigned long long *reachA, *reachB;
+    uint8_t *vid;
+    double *sx, *sy;
+    uint32_t *sworld;
+    const double *inj_xy;
+    unsigned long long inj_base, inj_n;
+    uint32_t *e_from, *e_to, *e_tv;
+    uint32_t e_cap;
+    uint32_t loc_stride;
+    KdBox *kd_box;
+    KdBox *loc_box;
+    KdMove *kd_losers;
+    int *bc_scratch;
+    uint32_t *bc_cursor;
+    BestCost *bc_out;
+    uint32_t bc_cap;
+    int mode;
+    unsigned long long *kd_hint;
+    int *loc_cur;
+    uint32_t *loc_dcur, *loc_gex, *loc_flags;
+    uint32_t *g_snap;
+    int n_validities;
+    int root_vid;
+    unsigned long long all_worlds;
+    double s_low0, s_low1, s_up0, s_up1;
+    double start_x, start_y;
+    unsigned long long root_reach;
+    unsigned long long rng_st_lo, rng_st_hi, rng_inc_lo, rng_inc_hi;
+    struct PcgJump *jump;
+    RunConst *self;
+    uint32_t *zero0;
+    unsigned long long zero_words;
+    uint32_t sched_min, sched_max, sched_K, sched_steps;
+    uint32_t sched_max_nodes;
+    uint32_t hint_max;
+    // ---- the large tables, behind everything: a wave that reads one of them reads a few entries
+    unsigned long long validities[65];
+    double gcx[64], gcy[64];
+    unsigned long long gmask[64];
+    double w2g_x[64], w2g_y[64];
+    unsigned long long pad_[6];
+};
+static_assert(sizeof(RunConst) % 64 == 0, "a row of an array of rows starts on a cache line");
+#else
 struct RunConst {
     // node SoA
     double *nx, *ny;
@@ -333,6 +465,7 @@ struct RunConst {
     uint32_t hint_max;                  // kd_hint_block: cells covering more hint squares leave the hints alone (a batch of many rows)
     uint32_t kd_lazy;                   // 1: only the goal path of the kd-tree is kept beside the steps (g_track_step); see there
 };
+#endif
 
 // Pointers read out of RunConst have no known address space, so hipcc emits flat_* accesses and drains both
 // memory counters around each of them.  Everything lives in hipMalloc'ed HBM: viewing a pointer as global
@@ -384,6 +517,57 @@ __device__ __forceinline__ const RunConst &rc_const(const RunConst *p) {
 #endif
 }
 __device__ __forceinline__ const RunConst &rc_const(const RunConst &rc) { return rc_const(&rc); }
+
+// RC_HOLD(key, a, b, ...): the named fields of a row (read through rc_const) are asked for HERE, together, and are in scalar registers
+// behind it.  Left alone the compiler sinks every scalar load of a field to the block that uses it -- a trip to the scalar cache and a
+// wait per block, one behind the other ahead of a phase's first vector load.  An empty asm statement takes the fields as scalar inputs
+// and hands out `key` -- a wave-uniform 32-bit value that everything behind it needs, the step index as a rule -- unchanged: the key's
+// users cannot run ahead of it, and it cannot run ahead of the fields' loads; later reads of the same fields are the same loads to the
+// compiler.  (Not volatile and without a memory clobber: to the compiler it touches no memory, so uniform loads behind it stay scalar.)
+// No instruction of its own; up to 28 values, each of 4 or 8 bytes.  Without PORRT_STEP_TRIPS (or PORRT_RC_SCALAR: the values would not
+// be scalar) it is nothing.
+template <class T>
+__device__ __forceinline__ auto rc_bits(T v) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "a field of one or two registers");
+    if constexpr (sizeof(T) == 8) return __builtin_bit_cast(unsigned long long, v);
+    else return __builtin_bit_cast(uint32_t, v);
+}
+#define PORRT_HS1(a) "s"(::porrt::rc_bits(a))
+#define PORRT_HS2(a, ...) PORRT_HS1(a), PORRT_HS1(__VA_ARGS__)
+#define PORRT_HS3(a, ...) PORRT_HS1(a), PORRT_HS2(__VA_ARGS__)
+#define PORRT_HS4(a, ...) PORRT_HS1(a), PORRT_HS3(__VA_ARGS__)
+#define PORRT_HS5(a, ...) PORRT_HS1(a), PORRT_HS4(__VA_ARGS__)
+#define PORRT_HS6(a, ...) PORRT_HS1(a), PORRT_HS5(__VA_ARGS__)
+#define PORRT_HS7(a, ...) PORRT_HS1(a), PORRT_HS6(__VA_ARGS__)
+#define PORRT_HS8(a, ...) PORRT_HS1(a), PORRT_HS7(__VA_ARGS__)
+#define PORRT_HS9(a, ...) PORRT_HS1(a), PORRT_HS8(__VA_ARGS__)
+#define PORRT_HS10(a, ...) PORRT_HS1(a), PORRT_HS9(__VA_ARGS__)
+#define PORRT_HS11(a, ...) PORRT_HS1(a), PORRT_HS10(__VA_ARGS__)
+#define PORRT_HS12(a, ...) PORRT_HS1(a), PORRT_HS11(__VA_ARGS__)
+#define PORRT_HS13(a, ...) PORRT_HS1(a), PORRT_HS12(__VA_ARGS__)
+#define PORRT_HS14(a, ...) PORRT_HS1(a), PORRT_HS13(__VA_ARGS__)
+#define PORRT_HS15(a, ...) PORRT_HS1(a), PORRT_HS14(__VA_ARGS__)
+#define PORRT_HS16(a, ...) PORRT_HS1(a), PORRT_HS15(__VA_ARGS__)
+#define PORRT_HS17(a, ...) PORRT_HS1(a), PORRT_HS16(__VA_ARGS__)
+#define PORRT_HS18(a, ...) PORRT_HS1(a), PORRT_HS17(__VA_ARGS__)
+#define PORRT_HS19(a, ...) PORRT_HS1(a), PORRT_HS18(__VA_ARGS__)
+#define PORRT_HS20(a, ...) PORRT_HS1(a), PORRT_HS19(__VA_ARGS__)
+#define PORRT_HS21(a, ...) PORRT_HS1(a), PORRT_HS20(__VA_ARGS__)
+#define PORRT_HS22(a, ...) PORRT_HS1(a), PORRT_HS21(__VA_ARGS__)
+#define PORRT_HS23(a, ...) PORRT_HS1(a), PORRT_HS22(__VA_ARGS__)
+#define PORRT_HS24(a, ...) PORRT_HS1(a), PORRT_HS23(__VA_ARGS__)
+#define PORRT_HS25(a, ...) PORRT_HS1(a), PORRT_HS24(__VA_ARGS__)
+#define PORRT_HS26(a, ...) PORRT_HS1(a), PORRT_HS25(__VA_ARGS__)
+#define PORRT_HS27(a, ...) PORRT_HS1(a), PORRT_HS26(__VA_ARGS__)
+#define PORRT_HS28(a, ...) PORRT_HS1(a), PORRT_HS27(__VA_ARGS__)
+#define PORRT_HS_PICK(a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12, a13, a14, a15, a16, a17, a18, a19, a20, a21, a22, a23, a24, a25, a26, a27, a28, N, ...) \
+    PORRT_HS##N
+#if PORRT_STEP_TRIPS && PORRT_RC_SCALAR
+#define RC_HOLD(key, ...)                                                                                                                         \
+    asm("" : "+s"(key) : PORRT_HS_PICK(__VA_ARGS__, 28, 27, 26, 25, 24, 23, 22, 21, 20, 19, 18, 17, 16, 15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1)(__VA_ARGS__))
+#else
+#define RC_HOLD(key, ...) do {} while (0)
+#endif
 
 // what a kernel launched for step b with (i0, nb) does for THIS row
 __device__ __forceinline__ uint32_t row_nb(const RunConst &rc, uint32_t b, uint32_t nb_arg) {
@@ -594,6 +778,19 @@ __device__ __forceinline__ int state_class(const RunConst &rc, double x, double 
     if (i >= rc.H || j >= rc.W) { *err |= ERR_RASTER; return CLS_HIGH; }
     int c = as_global(rc.cls)[i * rc.W + j];
     if (c == CLS_BAD) { *err |= ERR_RASTER; return CLS_HIGH; }
+    return c == CLS_HIGH0 ? CLS_HIGH : c;
+}
+// The same in two halves, for a caller that has other loads to issue beside the pixel's: `issue` asks for the byte of the state's pixel
+// whether or not the state lies on the raster (pixel 0 stands in for a state outside: a byte that exists, one load in every lane and no
+// branch around it) and says in `inside` which it was; `finish` makes of the byte what state_class returns, with the same errors.
+__device__ __forceinline__ int state_class_issue(const RunConst &rc, double x, double y, bool &inside) {
+    uint32_t i, j;
+    to_pixel(rc, x, y, i, j);
+    inside = i < rc.H && j < rc.W;
+    return as_global(rc.cls)[inside ? i * rc.W + j : 0u];
+}
+__device__ __forceinline__ int state_class_finish(int c, bool inside, uint32_t *err) {
+    if (!inside || c == CLS_BAD) { *err |= ERR_RASTER; return CLS_HIGH; }
     return c == CLS_HIGH0 ? CLS_HIGH : c;
 }
 
@@ -1365,6 +1562,27 @@ __device__ __forceinline__ uint32_t rank_before_lanes(const RunConst &rc, uint32
         r += (uint32_t)__popcll(v);
     }
     if (PORRT_DPP && stride == 16u) {          // (a compile-time constant at every call: the group size)
+        r += dpp_u32<kDppRowRor + 8>(r); r += dpp_u32<kDppRowRor + 4>(r); r += dpp_u32<kDppRowRor + 2>(r); r += dpp_u32<kDppRowRor + 1>(r);
+        return r;
+    }
+    for (uint32_t off = stride >> 1; off > 0; off >>= 1) r += (uint32_t)__shfl_xor((int)r, (int)off);
+    return r;
+}
+
+// The same from words the lanes hold already (loaded beside other things): v[u] of lane `lane` is word u * stride + lane of the step's
+// mask, for the words up to k's own (anything beyond is ignored).  NW * stride words: the caller checks that the mask has no more.
+template <uint32_t NW>
+__device__ __forceinline__ uint32_t rank_of_lane_words(const unsigned long long (&v)[NW], uint32_t k, uint32_t lane, uint32_t stride) {
+    const uint32_t wk = k >> 6;
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < NW; ++u) {
+        const uint32_t w = u * stride + lane;
+        unsigned long long x = w <= wk ? v[u] : 0ull;
+        if (w == wk) x &= (1ull << (k & 63u)) - 1ull;
+        r += (uint32_t)__popcll(x);
+    }
+    if (PORRT_DPP && stride == 16u) {
         r += dpp_u32<kDppRowRor + 8>(r); r += dpp_u32<kDppRowRor + 4>(r); r += dpp_u32<kDppRowRor + 2>(r); r += dpp_u32<kDppRowRor + 1>(r);
         return r;
     }

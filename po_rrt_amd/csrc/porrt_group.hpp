@@ -29,9 +29,12 @@ namespace porrt {
 // pages of R regions per round (lane <-> region for the counts), 64 / GL coalesced loads per page in flight.
 // (A dense walk -- all regions as one virtual array, slots found by a binary search over the prefix sums held across
 // the group -- was measured: the dependent cross-lane reads cost more than the idle lanes at region ends.)
-template <int GL, int R, bool WITHD, class Visit>
+// beside(): called once, by all lanes, behind the first loads of the search (the counts of the first round's regions; in a young tree
+// ahead of the stream) and ahead of everything that waits for them: the place for what the caller has in flight from before the call.
+struct GscanNothingBeside { __device__ __forceinline__ void operator()() const {} };
+template <int GL, int R, bool WITHD, class Visit, class Beside = GscanNothingBeside>
 __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const GTeam<GL> &tm, double qx, double qy, double rho, uint32_t N, Visit visit,
-                                           uint32_t skip_region = 0xFFFFFFFFu) {
+                                           uint32_t skip_region = 0xFFFFFFFFu, Beside beside = Beside()) {
     const uint32_t gl = tm.gl;
     int cx0, cy0, cx1, cy1;
     rep_cell(rc, qx - rho, qy - rho, kRG, cx0, cy0);
@@ -43,6 +46,7 @@ __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const
 #if !PORRT_PAGE_LOADS
         auto gx = as_global(rc.nx), gy = as_global(rc.ny), gdA = as_global(rc.distA);
 #endif
+        beside();
         for (uint32_t j0 = 0; j0 < N; j0 += (uint32_t)(U * GL)) {
             double x[U], y[U], d[U];
 #pragma unroll
@@ -82,6 +86,7 @@ __device__ __forceinline__ void gscan_disc(const RunConst &rc, uint32_t b, const
             reg = (y0 + ry) * kRG + x0 + (r - ry * w);
             cnt = reg == skip_region ? 0u : gcnt[reg];
         }
+        if (r0 == 0) beside();
         uint32_t page = reg;                                     // the first page of a region is static
         for (uint32_t lvl = 0;; ++lvl) {                         // page level: slots [64 lvl, 64 lvl + 64) of every region
             const uint32_t have = cnt > lvl * kPage ? cnt - lvl * kPage : 0u;
@@ -632,12 +637,17 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_N
         PORRT_TACC_A(rc, 4);
         return;
     }
+    // the fields of the search, asked for together ahead of the samples' loads (the scalar loads would otherwise come block by block)
+    RC_HOLD(b, rc.sched_nb, rc.part_stride, rc.n_at, rc.t2_at, rc.perm, rc.ssx, rc.ssy, rc.max_step, rc.has_grid, rc.W, rc.H, rc.low0, rc.low1, rc.ppm,
+            rc.cls, rc.bx0, rc.by0, rc.binv_w, rc.binv_h, rc.rep_f);
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
     if (slot >= row_nb(rc, b, nb)) return;
     PORRT_T0();
     const size_t so = (size_t)b * rc.part_stride + slot;
     const uint32_t k = as_global(rc.perm)[so];
+#if !PORRT_STEP_TRIPS_NN2
     const uint32_t N = as_global(rc.n_at)[b];
+#endif
     const double sqx = as_global(rc.ssx)[so], sqy = as_global(rc.ssy)[so];
     (void)i0;
     // Most samples of a grown tree are not steered: steer() (common.rs:215-225) moves the sample only if the L1 distance to
@@ -651,19 +661,49 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_N
     // ... and within the step's search radius, so that the radius search of k_conn2 finds it too (a sample without any neighbour
     // needs the nearest node after all)
     const double lim = 0.7 * rc.max_step, t2b = as_global(rc.t2_at)[b];
+#if PORRT_STEP_TRIPS_NN2
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);        // (the threshold rides with the samples: left alone its load sinks to its use, a trip of its own)
+    const uint32_t N = as_global(rc.n_at)[b];       // (needed by the search of a sample that is not proven unsteered: asked for there)
+#endif
     const double lim2 = lim * lim < t2b ? lim * lim : t2b;
     // the class of the sample's own pixel, asked for now: most samples are not steered, and their validity would otherwise be a
     // trip to the raster of its own at the end
     uint32_t err = 0;
     int cls_own = CLS_FREE;
+#if !PORRT_STEP_TRIPS_NN2
     if (rc.has_grid) cls_own = state_class(rc, sqx, sqy, &err);
+#endif
     // The cells carry their node's position rounded to f32 (rep_f): every node they name is older than this step (the pyramid is
     // written by the connect kernels of the steps before), so a cell that is not empty is a node of the snapshot, and its true position
     // lies within perr of the rounded one -- the test is made that much stricter.  (An empty cell is a NaN: no comparison holds.)
     const double perr = 1.3e-7 * (fabs(sqx) + fabs(sqy) + 2.0 * lim);
     const double limf = lim - perr, limf2 = limf > 0.0 ? (limf * limf < t2b ? limf * limf : t2b * (1.0 - 1e-6)) : -1.0;
     (void)lim2;
+#if PORRT_STEP_TRIPS_NN2
+    // ... beside the finest cells: both depend on the sample alone, so they are one trip to memory, not two.  The byte is looked at
+    // behind the cells' loads (the fence keeps the compiler from moving either load to its use), and it is asked for behind everything
+    // that waits for the samples' trip: a wait in between would have to wait for the byte too.
+    // (The empty statement says so for the paths that have not waited yet: with or without a raster the samples are in registers here.)
+    bool cls_in = false;
+    asm volatile("" ::"v"(sqx), "v"(sqy), "v"(t2b));
+    if (rc.has_grid) cls_own = state_class_issue(rc, sqx, sqy, cls_in);
+    {                                                // the finest cells
+        int cx, cy;
+        const int G = rep_dim(0);
+        rep_cell(rc, sqx, sqy, G, cx, cy);
+        flt2 pf = {__builtin_nanf(""), __builtin_nanf("")};        // (a lane without a cell holds an empty one)
+        if (tm.gl < 9u) {
+            const int x = cx + (int)(tm.gl % 3u) - 1, y = cy + (int)(tm.gl / 3u) - 1;
+            if (x >= 0 && y >= 0 && x < G && y < G) pf = as_global(rc.rep_f)[rep_off(0) + y * G + x];
+        }
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        if (rc.has_grid) cls_own = state_class_finish(cls_own, cls_in, &err);
+        easy = tm.ballot(dist2((double)pf.x, (double)pf.y, sqx, sqy) <= limf2) != 0ull;
+    }
+    for (int l = 1; l < 2 && !easy; ++l) {           // then, for a thin tree, the 3x3 cells of the next level
+#else
     for (int l = 0; l < 2 && !easy; ++l) {           // the finest cells; then, for a thin tree, the 3x3 cells of the next level
+#endif
         int cx, cy;
         const int G = rep_dim(l);
         rep_cell(rc, sqx, sqy, G, cx, cy);
@@ -699,6 +739,9 @@ __global__ __launch_bounds__(WV * 64) __attribute__((amdgpu_waves_per_eu(PORRT_N
         valid = cls == CLS_FREE && !err;                         // RTTFuncs adapter (tamp_rrt.rs:40-42)
     }
     PORRT_TACC_A(rc, 2);
+    // the fields of the stores, asked for together (six waits on the scalar cache one behind the other otherwise)
+    RC_HOLD(b, rc.q_x, rc.q_y, rc.kq_x, rc.kq_y, rc.kq_vid, rc.q_nn, rc.q_vid, rc.goal_kind, rc.gp_x, rc.gp_y, rc.bq_x, rc.bq_y, rc.bq_k, rc.valid_mask,
+            rc.cnt, rc.part_stride);
     if (tm.gl == 0) {
         as_global(rc.q_x)[k] = tx;
         as_global(rc.q_y)[k] = ty;
@@ -997,6 +1040,10 @@ __device__ __attribute__((noinline)) void heavy_sample_wave(const RunConst &rc_a
 #ifndef PORRT_CONN2_WAVES
 #define PORRT_CONN2_WAVES 4
 #endif
+// the fields of a connect wave's set-up and of its search's first round, asked for together at the kernel's start
+#define CONN2_HOLD(rc, b)                                                                                                                          \
+    RC_HOLD(b, rc.sched_nb, rc.n_at, rc.t2_at, rc.bq_k, rc.bq_x, rc.bq_y, rc.valid_mask, rc.has_grid, rc.W, rc.H, rc.low0, rc.low1, rc.ppm, rc.clr,  \
+            rc.cand_cap, rc.bx0, rc.by0, rc.binv_w, rc.binv_h, rc.rg_cnt, rc.rg_dir, rc.rg_maxp, rc.pg_cap, rc.pg_xy, rc.pg_id, rc.pg_d)
 // One wave's samples of the connect pass (64 / GL of them, GL lanes each): radius search into the sample's LDS list, choice of the
 // parent, rewire candidates; a sample with more hits than its list holds is then served by the whole wave.  `wl`: the wave's lists
 // ((64 / GL) x kLdsHits (GL / 16) hits).  Nothing in here synchronises beyond the wave, so the waves of a workgroup are independent.
@@ -1017,12 +1064,47 @@ __device__ __forceinline__ void conn2_wave(const RunConst &rc, uint32_t b, uint3
     grid.p = rc.cls; grid.W = rc.W;
     if (act) {
         // second round trip: the new node's id and the clearance around its pixel, beside the region counts of the search
+#if PORRT_STEP_TRIPS_CONN2
+        // (in fact: the words of the step's valid mask -- K <= 2048 is at most 32 words, kVW per lane -- and the pixel's byte are asked for
+        // here and looked at in the search, behind the loads of its first counts (gscan_disc's beside): left to the compiler each of the
+        // three was a trip of its own.  The byte of pixel 0 stands in for a state outside the raster, as in state_class_issue.)
+        asm("" : "+v"(px), "+v"(py));                  // (the sample is in registers here on every path: no later wait has to count for it)
+        constexpr uint32_t kVW = GL == 16 ? 2u : 1u;
+        const bool words_held = vwords <= kVW * (uint32_t)GL;
+        unsigned long long vw[kVW] = {};
+        if (words_held) {
+#pragma unroll
+            for (uint32_t u = 0; u < kVW; ++u) {
+                const uint32_t w = u * (uint32_t)GL + tm.gl;
+                vw[u] = w <= (k >> 6) ? as_global(rc.valid_mask)[(size_t)b * vwords + w] : 0ull;
+            }
+        } else {
+            id = N + rank_before_lanes(rc, b, vwords, k, tm.gl, (uint32_t)GL);
+        }
+        bool clr_in = false;
+        if (rc.has_grid) {
+            uint32_t bi, bj;
+            to_pixel(rc, px, py, bi, bj);
+            clr_in = bi < rc.H && bj < rc.W;
+            clr_b = as_global(rc.clr)[clr_in ? bi * rc.W + bj : 0u];
+        }
+        // (An empty statement that takes the loaded values in and hands them out again: what is computed from them cannot be moved ahead
+        // of it -- out of the search's loop, where the wait for them would come before the counts are asked for --, and the loads cannot
+        // be moved behind it.)
+        const auto beside = [&]() {
+            if constexpr (kVW == 2u) asm volatile("" : "+v"(vw[0]), "+v"(vw[1]), "+v"(clr_b)::"memory");
+            else asm volatile("" : "+v"(vw[0]), "+v"(clr_b)::"memory");
+            if (words_held) id = N + rank_of_lane_words(vw, k, tm.gl, (uint32_t)GL);
+            if (!clr_in) clr_b = 0;
+        };
+#else
         id = N + rank_before_lanes(rc, b, vwords, k, tm.gl, (uint32_t)GL);
         if (rc.has_grid) {
             uint32_t bi, bj;
             to_pixel(rc, px, py, bi, bj);
             if (bi < rc.H && bj < rc.W) clr_b = as_global(rc.clr)[bi * rc.W + bj];
         }
+#endif
         // a sample's list: the wave's LDS share split between its 64 / GL samples (80 hits at 16 lanes per sample, 320 at 64)
         constexpr uint32_t kHits = kLdsHits * (uint32_t)(GL / 16);
         uint8_t *hb = wl + (lane / (uint32_t)GL) * (kHits * 28u);
@@ -1044,7 +1126,11 @@ __device__ __forceinline__ void conn2_wave(const RunConst &rc, uint32_t b, uint3
                 else err |= (uint32_t)ERR_CAND_OVERFLOW;
             }
             tot += (uint32_t)__popcll(hm);
+#if PORRT_STEP_TRIPS_CONN2
+        }, 0xFFFFFFFFu, beside);
+#else
         });
+#endif
         __builtin_amdgcn_wave_barrier();
         PORRT_TACC_B(rc, 1);
         if (tot <= kHits) {
@@ -1094,6 +1180,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2_
     uint32_t bx = blockIdx.x, by = blockIdx.y;
     xcd_swizzle(bx, by);
     const RunConst &rc = rc_const(rcp + by);    // one context per grid row (porrt_grow_batch)
+    CONN2_HOLD(rc, b);
     nb = row_nb(rc, b, nb);
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
     if (bx * SPB >= nb) return;                 // (a row that has stopped, does not run this step, or runs a shorter one)
@@ -1143,6 +1230,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PORRT_CONN2
     if (role == 0) { rider_file(rc, b, nb, vwords, lds_dyn, fast); return; }    // the page-filing workgroup
     if (lazy && role == 2u) { rider_gtrack(rc, b, nb, vwords, lds_dyn, fast); return; }
     const uint32_t slot = bx * SPB + threadIdx.x / GL;
+    if (role == ns) CONN2_HOLD(rc, b);
     // first round trip: everything that depends on nothing
     const uint32_t N = as_global(rc.n_at)[b];
     const double T2 = as_global(rc.t2_at)[b];              // rad_T2[N], rrt.rs:121: the size before insertion
