@@ -186,6 +186,7 @@ struct porrt_ctx {
     uint32_t opt_cand_cap = 2048;
     uint64_t edge_per_node = 256, tie_pool_mult = 16;      // pool sizes: grown and the run replayed when one overflows (as the neighbour lists)
     uint64_t tie_pool_ids = 0;             // "tie_pool_ids" (test seam): the deferred-tie pool in ids, 0 = max(2^20, tie_pool_mult * n_iter_max)
+    uint64_t batch_steps = 0;              // member of a porrt_grow_batch whose rows follow plans of their own: the steps of the longest plan (0 otherwise)
     // ---- device buffers
     DevBuf<double> d_nx, d_ny, d_distA, d_distB, d_sx, d_sy, d_qx, d_qy, d_pgxy, d_pgd, d_candxy, d_candval, d_radT2, d_inj, d_ssx, d_ssy, d_bqx, d_bqy, d_t2at;
     DevBuf<int> d_parent, d_qnn, d_qvid, d_pgid, d_candid, d_gid, d_kdup;
@@ -1264,6 +1265,7 @@ int porrt_ctx::grow(const double start[2], double max_step, double search_radius
     if (n_iter_max + 2 >= 0x7FFFFFF0ull) { set_err("n_iter_max too large"); return PORRT_ERR_INVALID; }
     if (const char *e = bad_step_lengths(max_step, search_radius)) { set_err(e); return PORRT_ERR_INVALID; }
     about_to_grow();
+    batch_steps = 0;
     const SamplerState s0(*this);
     bool host_samples = false;
     for (int attempt = 0; attempt < 12; ++attempt) {
@@ -1298,7 +1300,9 @@ int porrt_ctx::grow_once(const double start[2], double max_step, double search_r
 
     // ---- capacities
     const uint64_t Nmax = n_iter_max + 2;
-    const uint64_t steps_max = n_iter_max / K + 4;
+    // (the per-step arrays of a batch's row are indexed by the batch's steps, also after the row has ended: k_row_sched carries
+    // n_at and sched_nb on to the last step of the longest plan, and the step kernels read sched_nb there)
+    const uint64_t steps_max = std::max<uint64_t>(n_iter_max / K, batch_steps) + 4;
     const uint32_t vwords = (K + 63) / 64;
     const uint32_t Kpad = vwords * 64;       // sample stride of the per-chunk arrays (multiple of the wave size)
     const uint32_t cand_cap = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(opt_cand_cap, 64), Nmax);
@@ -3163,6 +3167,7 @@ static int grow_batch(porrt_ctx *const *cs, uint32_t n, const double *starts, do
         for (uint32_t q = 0; q < n; ++q) {
             hipStream_t own = cs[q]->stream;
             cs[q]->stream = L->stream;          // the members' preparation is queued on the leader's stream: no host sync
+            cs[q]->batch_steps = sched ? B_pot : 0u;
             int r = cs[q]->grow_once(starts + 2 * q, max_step, search_radius, nmax[q], nmax[q], K, mode, false, 1);
             cs[q]->stream = own;
             if (r) { if (cs[q] != L) L->set_err(cs[q]->err); return r; }
