@@ -1,7 +1,8 @@
 // Grows a belief-space graph and expands it over the reachable beliefs with the C++ mirror of the reference interface
 // (cf. src/pto.rs:466-490, test_plan_on_map1_2_goals: grow_graph, then build_belief_graph) and prints digests the tests
 // compare with the CPU oracle.
-// usage: plan_pto <map.pgm> <zone_ids.pgm> <n_iter> <batch_K> <seed>
+// With a sixth argument it ends as the reference's test does (pto.rs:313-317): the picture of the graph, the zones' observability and the policy.
+// usage: plan_pto <map.pgm> <zone_ids.pgm> <n_iter> <batch_K> <seed> [out.png]
 #include "../include/porrt.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -44,10 +45,21 @@ int main(int argc, char **argv) {
         for (double d : pto.expected_costs_to_goals) { uint64_t u; std::memcpy(&u, &d, 8); hd = fnv(hd, u); }
         size_t n_policy = 0, n_leafs = 0;
         uint64_t hpol = 1469598103934665603ull;
+        Policy policy;
         if (pto.expected_costs_to_goals[0] < 1e300) {
-            Policy policy = pto.extract_policy();
+            policy = pto.extract_policy();
             n_policy = policy.nodes.size(); n_leafs = policy.leafs.size();
             for (auto &pn : policy.nodes) { hpol = fnv(hpol, pn.original_node_id); hpol = fnv(hpol, pn.parent ? *pn.parent : ~0ull); }
+        }
+        if (argc > 6) {                              // pto.rs:313-317
+            auto m2 = m;
+            m2.resize(5);
+            m2.draw_full_graph(pto);
+            m2.draw_zones_observability();
+            m2.draw_policy(policy);
+            m2.save(argv[6]);
+            const auto di = m2.draw_info();
+            std::printf("picture %s: the policy's call drew %llu lines, %llu fragments\n", argv[6], (unsigned long long)di.lines, (unsigned long long)di.fragments);
         }
         std::printf("costs %016llx policy_nodes %zu leafs %zu policy %016llx ", (unsigned long long)hd, n_policy, n_leafs, (unsigned long long)hpol);
         std::printf("complete %d nodes %zu beliefs %zu belief_nodes %zu edges %zu types %016llx children %016llx parents %016llx compatible %zu\n",

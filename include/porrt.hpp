@@ -2,7 +2,9 @@
 // on top of the C ABI (porrt_hip.h).  Names, argument meaning and error behaviour follow cambyse/po-rrt:
 //   ContinuousSampler / DiscreteSampler   src/sample_space.rs:6-60
 //   SquareGoal / ObservationGoal          src/common.rs:304-350, src/rrt.rs:325-341
-//   MapShelfDomain / Map                  src/map_shelves_io.rs:65-148, src/map_io.rs:67-161 (open, add_zones)
+//   MapShelfDomain / Map                  src/map_shelves_io.rs:65-148, src/map_io.rs:67-161 (open, add_zones); the drawing functions
+//                                         resize / draw_tree / draw_full_graph / draw_policy / draw_path / draw_zones_observability / save
+//                                         (map_shelves_io.rs:276-457, map_io.rs:303-479) on a device canvas
 //   RRTNode / RRTTree / RRT::plan(_several)  src/rrt.rs:14-62, 84-100, 183-246
 //   PTO::grow_graph + PTOGraph + Reachability  src/pto.rs:55-139, src/pto_graph.rs:171-207, src/pto_reachability.rs
 // The reference is Rust; this image has no Rust toolchain, so the compiled host is C++ (INTEGRATION.md has the
@@ -16,6 +18,7 @@
 #include <cctype>
 #include <cstdint>
 #include <fstream>
+#include <memory>
 #include <optional>
 #include <sstream>
 #include <stdexcept>
@@ -88,7 +91,66 @@ struct GridDomain {                  // common part of MapShelfDomain / Map
     bool has_zones = false;
     GridDomain(Raster r, State l, State u, int d) : img(std::move(r)), low(l), up(u), domain(d) {}
     void add_zones(const std::string &path, double visibility) { zones = Raster::open(path); visibility_distance = visibility; has_zones = true; }
+
+    // ---- drawing functions (map_shelves_io.rs:276-457, map_io.rs:303-479), on a device canvas (porrt_canvas_*): the pictures are bit for
+    // bit the reference's.  Ours: the canvas is made at the first draw call (on draw_device), so resize must come before the drawing (it
+    // throws afterwards; the reference would resize the drawn image), where every
+    // driver of the reference has it (pto.rs:313-317: m.resize(5); m.draw_full_graph(&graph); m.draw_zones_observability();
+    // m.draw_policy(&policy); m.save(path)).  A planner is passed where the reference passes the graph or tree it holds (&pto.graph,
+    // &rrt.rrttree): its nodes stay on the device.  Planner: RRT for draw_tree; PTO or PRM for draw_full_graph.
+    using Color = std::array<uint8_t, 3>;
+    int draw_device = 0;
+    void resize(uint32_t factor) {
+        if (canvas_) throw std::runtime_error("resize: call it before the first draw call");
+        if (!factor) throw std::runtime_error("resize: factor 0");
+        draw_factor_ *= factor;                  // (Nearest at f1 then f2 is Nearest at f1 * f2; the reference rounds ppm at every call, so after
+                                                 //  SEVERAL resize calls its ppm can differ from ppm * (f1 * f2) in the last bit: call it once, as the drivers do)
+    }
+    template <class Planner> void draw_tree(const Planner &rrt) { draw_check(porrt_canvas_draw_tree(canvas(), rrt.context().get())); }
+    template <class Planner> void draw_full_graph(const Planner &planner) { draw_check(porrt_canvas_draw_full_graph(canvas(), planner.context().get())); }
+    template <class Policy_> void draw_policy(const Policy_ &policy) {
+        std::vector<double> xy;
+        std::vector<int64_t> parent;
+        for (const auto &n : policy.nodes) { xy.push_back(n.state[0]); xy.push_back(n.state[1]); parent.push_back(n.parent ? (int64_t)*n.parent : -1); }
+        draw_check(porrt_canvas_draw_policy(canvas(), xy.data(), parent.data(), parent.size()));
+    }
+    void draw_path(const std::vector<State> &path, Color color) {
+        std::vector<double> xy;
+        for (const State &s : path) { xy.push_back(s[0]); xy.push_back(s[1]); }
+        draw_check(porrt_canvas_draw_path(canvas(), xy.data(), path.size(), color.data()));
+    }
+    void draw_zones_observability() { draw_check(porrt_canvas_draw_zones_observability(canvas())); }
+    void save(const std::string &path) { draw_check(porrt_canvas_save_png(canvas(), path.c_str())); }
+    struct porrt_draw_info draw_info() { struct porrt_draw_info i; draw_check(porrt_canvas_get_info(canvas(), &i)); return i; }
+
+private:
+    uint32_t draw_factor_ = 1;
+    std::shared_ptr<porrt_canvas> canvas_;
+    void draw_check(int rc) const { if (rc < 0) throw std::runtime_error(porrt_canvas_last_error(canvas_.get())); }
+    porrt_canvas *canvas() {
+        if (!canvas_) {
+            porrt_ctx *c = porrt_create(draw_device);
+            if (!c) throw std::runtime_error("porrt_create failed: no usable HIP device (there is no CPU fallback)");
+            porrt_canvas *cv = nullptr;
+            if (porrt_set_grid(c, img.px.data(), img.W, img.H, low.data(), up.data(), domain) >= 0 &&
+                (!has_zones || porrt_set_zones(c, zones.px.data(), visibility_distance) >= 0))
+                cv = porrt_canvas_create(c, draw_factor_);
+            const std::string msg = porrt_last_error(c);
+            porrt_destroy(c);                      // (the canvas outlives the context it was made from)
+            if (!cv) throw std::runtime_error(msg);
+            canvas_ = std::shared_ptr<porrt_canvas>(cv, porrt_canvas_destroy);
+        }
+        return canvas_.get();
+    }
 };
+// the reference's colour table (map_shelves_io.rs:25-48)
+namespace colors {
+using Color = GridDomain::Color;
+constexpr Color BLACK{0, 0, 0}, WHITE{255, 255, 255}, RED{255, 0, 0}, LIME{0, 255, 0}, BLUE{0, 0, 255}, YELLOW{255, 255, 0}, CYAN{0, 255, 255},
+    MAGENTA{255, 0, 255}, MAROON{128, 0, 0}, OLIVE{128, 128, 0}, GREEN{0, 128, 0}, PURPLE{128, 0, 128}, TEAL{0, 128, 128}, NAVY{0, 0, 128},
+    GRAY1{30, 30, 30}, GRAY2{60, 60, 60}, GRAY3{90, 90, 90}, GRAY4{120, 120, 120}, GRAY5{150, 150, 150}, GRAY6{180, 180, 180},
+    GRAY7{210, 210, 210}, GRAY8{240, 240, 240};
+}
 struct MapShelfDomain : GridDomain { // map_shelves_io.rs:80-114
     MapShelfDomain(Raster r, State l, State u) : GridDomain(std::move(r), l, u, PORRT_DOMAIN_SHELF) {}
     static MapShelfDomain open(const std::string &path, State l, State u) { return MapShelfDomain(Raster::open(path), l, u); }
@@ -143,6 +205,7 @@ private:
 // nullptr = the default RTTFuncs (everything valid, rrt.rs:64-76).
 class RRT {
 public:
+    const Context &context() const { return ctx_; }          // (the drawing functions of MapShelfDomain / Map read the graph on its device)
     uint32_t batch_K = 1024;         // samples per GPU step; 1 = the reference's sequential loop
     RRT(const ContinuousSampler &s, const MapShelfDomain *fns, int device = 0) : ctx_(device) {
         if (fns) ctx_.set_domain(*fns);
@@ -328,6 +391,7 @@ struct RefinmentStrategy {
 
 class PTO {
 public:
+    const Context &context() const { return ctx_; }          // (the drawing functions of MapShelfDomain / Map read the graph on its device)
     uint32_t batch_K = 256;
     PTOGraph graph;
     size_t n_it = 0;
@@ -684,6 +748,7 @@ inline std::vector<std::vector<uint32_t>> policy_graph(const std::vector<std::ve
 // once; growing an existing roadmap further is a new call with the full iteration count on a sampler reset to its seed).
 class PRM {
 public:
+    const Context &context() const { return ctx_; }          // (the drawing functions of MapShelfDomain / Map read the graph on its device)
     PTOGraph graph;
     size_t n_it = 0;
     PRM(const ContinuousSampler &cs, const GridDomain &fns, int device = 0) : ctx_(device) {

@@ -700,7 +700,11 @@ int porrt_get_metrics(const porrt_ctx *ctx, porrt_metrics *out);
  * 0 .. 2^31 - 1, default 4096) is a bound of the same kind: no entry of the measured graphs came near it.  "policy_max_nodes" (porrt_bg_extract_policies,
  * porrt_mm_extract_policies: a policy that would have more nodes is status 4, 1 .. 2^24, default 1 << 16) is one too.
  * "refine_short_lds" (the batch refiner, default 1: the pieces of <= 256 nodes run in a launch of their own whose waves take 4 KiB
- * of LDS instead of 16; 0 = every piece in one launch; the results are the same bits). */
+ * of LDS instead of 16; 0 = every piece in one launch; the results are the same bits).
+ * "draw_max_fragments" (a canvas made after it is set: the fragments of one pass of a draw call, 1 .. 2^30, default 2^24 -- two arrays of
+ * 8-byte records, 256 MiB; a call with more runs in several passes over consecutive lines, a single longer line in a pass of its own) and
+ * "draw_heavy_cap" (a pixel with more records than this in a pass is ordered by one wave -- up to 64 records -- or by a workgroup through LDS
+ * instead of by one lane, 1 .. 1024, default 16; the workgroup sorts 1024 records a trip) are TEST SEAMS at small values, like cand_cap: the image is the same bits. */
 int porrt_set_option(porrt_ctx *ctx, const char *name, int64_t value);
 /* what was in force: "launch_mode" (the last porrt_grow_batch led by this context: 0 = one launch sequence, G = G sequences side by
  * side on streams chosen by measurement, -G = G sequences on the contexts' own streams -- the probe found no parallel set, e.g. under a
@@ -816,6 +820,74 @@ uint64_t porrt_graph_file_num_validities(const porrt_graph_file *g);
 uint64_t porrt_graph_file_num_worlds(const porrt_graph_file *g);
 int      porrt_graph_file_get(const porrt_graph_file *g, double *xy, uint64_t *node_validity, uint64_t *child_off, uint64_t *child_id,
                               uint64_t *child_validity, uint64_t *parent_off, uint64_t *parent_id, uint64_t *parent_validity, uint8_t *validities);
+
+/* ---- the reference's figures, drawn on the device: the drawing half of MapShelfDomain / Map (map_shelves_io.rs:276-457; map_io.rs:303-479
+ * is the same text with one other alpha), the tail of every driver and integration test of the reference: m.resize(5); m.draw_full_graph(..);
+ * m.draw_zones_observability(); m.draw_policy(..); m.save(path) (pto.rs:313-317), or draw_tree / draw_path (rrt.rs:299-303).
+ * Canvas: the context's occupancy raster as RGB8 (Map::build: ImageLuma8 -> to_rgb8, the three channels equal), resized by
+ * image::imageops::resize(.., FilterType::Nearest) at an integer factor -- block replication, dst(j, i) = src(j / f, i / f) -- with
+ * ppm *= factor as f64 (one rounding; factor 1 leaves it alone), low unchanged and the resized height in to_pixel_coordinates (:276-286).  It
+ * also takes the context's zone positions and visibility distance, and its options "draw_max_fragments" and "draw_heavy_cap", as they stand at
+ * porrt_canvas_create.  It lives on the context's device and outlives the context; it may be drawn on from any context of that device with the
+ * same raster geometry (W, H, low, ppm, domain kind), PORRT_ERR_INVALID otherwise.
+ * draw_line(a, b, color, alpha: f32) (:359-375): both ends through to_pixel_coordinates (the growth's saturating `as u32`), cast `as f32` with
+ * (i, j) as (x, y), line_drawing::XiaolinWu::<f32, i32> over them; a pair outside the image is skipped, a pair inside blends per channel
+ *     ((1.0 - a) * old as f32 + a * new as f32) as u8,   a = alpha * line_alpha,
+ * in f32 without contraction, truncated and saturated.  The result at a pixel depends on the ORDER in which a call's lines reach it, so every
+ * call is an ordered list of lines composited in exactly the reference's order (porrt_draw.hpp: count, scan, scatter, a resolve that orders each
+ * pixel's records by the line's place and applies them in that order): bit for bit the sequential loop's image.
+ *     call                          lines, in draw order                                                          colour        alpha
+ *     draw_tree (:313-321)          nodes in id order; a node with a parent gives parent -> node                   TEAL          0.3
+ *     draw_full_graph (:389-400)    nodes in id order; each node's children in push order (the lists             GRAY5         0.25 shelf domain,
+ *                                   porrt_graph_save_json writes; both directions: a PRM roadmap's reverse                      0.15 door domain
+ *                                   edge is in the lists the reference holds, prm.rs:96-103); from -> to                         (map_io.rs:420)
+ *     draw_policy (:323-341)        nodes in id order; a node with more than one child first a circle of         NAVY circle,  1.0
+ *                                   radius 0.025, then a line to each child (children in ascending id: the        BLACK lines
+ *                                   order extract_policy and recompose number them in)
+ *     draw_path (:288-292)          consecutive states                                                            caller's      1.0
+ *     draw_zones_observability      one circle of radius visibility_distance per zone position, zone order        TEAL          1.0
+ *       (:452-456)
+ *     draw_circle (:377-387)        50 segments between xy + r * (cos, sin)(k * 2 pi / 50), k = 0 .. 50: the 51 points are made on the host
+ *                                   with its libm, never on the device
+ * XiaolinWu and the Nearest resize are third-party arithmetic recalled from the crates, as Bresenham is (README, parity paragraph).
+ * Ours, not the reference's: a line with a non-finite coordinate is PORRT_ERR_INVALID and the canvas is left unchanged (the reference casts NaN to
+ * pixel 0 and draws); a line with a pixel end beyond 2^24 is PORRT_ERR_INVALID and the canvas is left unchanged (the reference would walk billions
+ * of pixels, and f32 no longer holds the integers); a canvas of more than 16384 pixels a side is PORRT_ERR_CAPACITY, as is a call of 2^31 lines.
+ * Whatever a call refuses it refuses before it touches the image.
+ * porrt_canvas_create returns NULL on failure: porrt_last_error(ctx) has the text and porrt_get_option(ctx, "draw_create_status") the code
+ * (factor 0 or no grid: PORRT_ERR_INVALID; over the cap: PORRT_ERR_CAPACITY).  On its first use a canvas checks the device's f32 divide (the
+ * gradient dy / dx) against the host's on 65536 quotients of integers up to 2^24; if one differs, gradients go through the f64 divide, which
+ * porrt_selftest checks and which rounds an f32 quotient correctly (porrt_draw_info.gradient_by_f64).
+ * porrt_canvas_draw_tree and porrt_canvas_draw_full_graph make their lines on the device from the context's resident arrays: no node or edge
+ * array is downloaded.  porrt_canvas_draw_full_graph needs the context's adjacency lists (the ones porrt_get_edges and the belief-graph build use);
+ * when the context has not made them for this graph yet, this call makes and caches them, with the kd pre-order ranks built on the device whatever
+ * option "host_ranks" says (a few flag words come back per 32 levels of the kd-tree, nothing else) -- that first call is slower.
+ * The two calls take `const porrt_ctx *` because the context's results are not changed; they do fill its caches (the adjacency order) and
+ * porrt_canvas_create writes its error text and "draw_create_status": like every call on a context they must not run beside another call on it.
+ * porrt_canvas_get_rgb: H * W * 3 bytes, row-major from the top.  porrt_canvas_save_png / porrt_write_png: 8-bit RGB PNG with stored deflate
+ * blocks (no compression, no zlib): the same pixels as the reference's m.save(path), not the same bytes.  porrt_write_png needs no device.
+ * porrt_canvas_get_info: the last draw call -- lines (places in the order, the nodes without parent of draw_tree included), fragments (pixel
+ * visits inside the image), passes, the most records one pixel held in one pass, the pixels not resolved by a single lane (heavy_pixels) and
+ * those of them that one wave resolved (wave_pixels: at most 64 records; the others took a workgroup), both summed over the passes,
+ * and seconds: the whole call on the host clock, and HIP events around the count (with the per-line scan), the pixel scan, the scatter and
+ * the resolve, summed over the passes. */
+typedef struct porrt_canvas porrt_canvas;
+struct porrt_draw_info { uint64_t lines, fragments, passes, heaviest_pixel, heavy_pixels, wave_pixels, gradient_by_f64; double s_total, s_count, s_scan, s_scatter, s_resolve; };
+porrt_canvas *porrt_canvas_create(const porrt_ctx *ctx, uint32_t factor);   /* Map::open + resize(factor) */
+void porrt_canvas_destroy(porrt_canvas *canvas);
+const char *porrt_canvas_last_error(const porrt_canvas *canvas);
+int  porrt_canvas_size(const porrt_canvas *canvas, uint32_t *W, uint32_t *H);
+int  porrt_canvas_draw_lines(porrt_canvas *canvas, const double *ab /* n*4: a, b */, uint64_t n, const uint8_t rgb[3], float alpha);
+int  porrt_canvas_draw_path(porrt_canvas *canvas, const double *xy /* n*2 */, uint64_t n, const uint8_t rgb[3]);
+int  porrt_canvas_draw_circles(porrt_canvas *canvas, const double *xy /* n*2 */, uint64_t n, double radius, const uint8_t rgb[3]);
+int  porrt_canvas_draw_tree(porrt_canvas *canvas, const porrt_ctx *ctx);          /* the tree of ctx's last porrt_grow(mode PORRT_MODE_RRT) */
+int  porrt_canvas_draw_full_graph(porrt_canvas *canvas, const porrt_ctx *ctx);    /* its PTO graph or PRM roadmap */
+int  porrt_canvas_draw_zones_observability(porrt_canvas *canvas);
+int  porrt_canvas_draw_policy(porrt_canvas *canvas, const double *xy /* n*2 */, const int64_t *parent /* -1 = root */, uint64_t n);
+int  porrt_canvas_get_rgb(const porrt_canvas *canvas, uint8_t *rgb /* H*W*3 */);
+int  porrt_canvas_save_png(const porrt_canvas *canvas, const char *path);
+int  porrt_write_png(const char *path, const uint8_t *rgb, uint32_t W, uint32_t H);
+int  porrt_canvas_get_info(const porrt_canvas *canvas, struct porrt_draw_info *out);
 
 /* ---- the one exchange of a query-sharded job (the reference is one process and has no
  * counterpart).  Queries are independent: query q runs on rank q mod world, nothing is communicated

@@ -6,5 +6,5 @@ behind a C ABI (include/porrt_hip.h, libporrt_hip.so: hand-written HIP for gfx95
 query-sharded job (RCCL); `sharding` holds the query partition.  The C++ mirror of the reference's
 RRT / PTO / PRM interface is include/porrt.hpp.
 """
-from .engine import (DOMAIN_DOOR, DOMAIN_SHELF, INCOMPLETE, MODE_PTO, MODE_RRT, OK, Comm, Engine, PorrtError,  # noqa: F401
-                     conditional_dijkstra, exchange_decide, extract_policies_explicit, load_library)
+from .engine import (DOMAIN_DOOR, DOMAIN_SHELF, INCOMPLETE, MODE_PTO, MODE_RRT, OK, Canvas, Comm, Engine, PorrtError,  # noqa: F401
+                     colors, conditional_dijkstra, exchange_decide, extract_policies_explicit, load_library)

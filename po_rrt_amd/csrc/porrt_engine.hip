@@ -75,6 +75,12 @@ struct Arena {
 #include "porrt_policy.hpp"
 #include "porrt_launch.hpp"
 
+// the canvas's defaults and limits (porrt_draw.hpp, included after the context it reads)
+namespace porrt {
+constexpr uint32_t kDrawHeavyCapDefault = 16, kDrawHeavyCapLimit = 1024;
+constexpr uint64_t kDrawMaxFragmentsDefault = 1ull << 24, kDrawMaxFragmentsLimit = 1ull << 30;     // 8-byte records, twice: 256 MiB at the default
+}
+
 // the device side of a roadmap pass (roadmaps_of_modes, porrt_mm_plan_batch): slots of the context's mm_scratch
 struct MmRoadmapDev {
     double *x, *y;
@@ -184,6 +190,11 @@ struct porrt_ctx {
     bool opt_dp_sweeps = false;            // "dp_sweeps": expected costs by whole-graph sweeps instead of layer by layer
     uint64_t opt_dp_wide_rows = kDpWideRows;   // "dp_wide_rows": a level of the layered costs with N * W >= this sweeps wide (0 = every level)
     uint32_t opt_cand_cap = 2048;
+    // the canvas (porrt_draw.hpp) takes both at porrt_canvas_create.  "draw_max_fragments": the fragments of one pass of a draw call (its two
+    // record arrays hold 16 bytes a fragment); "draw_heavy_cap": a pixel with more records than this is resolved by a workgroup, not a lane
+    uint64_t opt_draw_max_fragments = kDrawMaxFragmentsDefault;
+    uint32_t opt_draw_heavy_cap = kDrawHeavyCapDefault;
+    int draw_create_status = 0;            // "draw_create_status": the code of the last porrt_canvas_create on this context (0: it returned a canvas)
     uint64_t edge_per_node = 256, tie_pool_mult = 16;      // pool sizes: grown and the run replayed when one overflows (as the neighbour lists)
     uint64_t tie_pool_ids = 0;             // "tie_pool_ids" (test seam): the deferred-tie pool in ids, 0 = max(2^20, tie_pool_mult * n_iter_max)
     uint64_t batch_steps = 0;              // member of a porrt_grow_batch whose rows follow plans of their own: the steps of the longest plan (0 otherwise)
@@ -341,7 +352,7 @@ struct porrt_ctx {
     EdgeOrderState eo;                     // adjacency order of the last PTO graph / roadmap (device)
     std::shared_ptr<void> host_kd;         // the kd-tree of the node coordinates on the host (pre-order ranks, nearest nodes)
     uint64_t host_kd_tag = ~0ull;
-    int ensure_edge_order();
+    int ensure_edge_order(bool ranks_on_device = false);
     int grow_prm(const double start[2], double max_step, double search_radius, uint64_t n_iter);
     int grow_prm_once(const double start[2], double max_step, double search_radius, uint64_t n_iter, uint64_t &edge_need);
     MmState mm;                            // porrt_grow_mm_prm: the mode tree and the modes' roadmaps
@@ -1746,13 +1757,13 @@ static HostKd *host_kd_of(porrt_ctx *c) {                            // built on
 // The pre-order rank of every node in the kd-tree of the coordinates (sequential KdTree::add in id order,
 // nearest_neighbor.rs:29-46) -- from the host's kd-tree, or (option host_ranks = 0) made on the device --, then the edge order and
 // the adjacency lists on the device (porrt_edges.hpp).
-int porrt_ctx::ensure_edge_order() {
+int porrt_ctx::ensure_edge_order(bool ranks_on_device) {
     if (eo.tag == results_tag) return PORRT_OK;
     HIPCHK(hipSetDevice(device));
     const size_t N = n_nodes;
     std::string e;
     int r;
-    if (opt_host_ranks) {                    // (the default; option "host_ranks" = 0 makes them on the device, below)
+    if (opt_host_ranks && !ranks_on_device) {      // (the default; option "host_ranks" = 0 -- or a caller that keeps the nodes on the device: the canvas -- makes them on the device, below)
         if ((r = download(DL_TREE))) return r;
         const HostKd *kd = host_kd_of(this);
         const std::vector<int> &ch0 = kd->left, &ch1 = kd->right;
@@ -5251,6 +5262,9 @@ int porrt_get_option(const porrt_ctx *c, const char *name, int64_t *value) {
     else if (!strcmp(name, "refine_short_lds")) *value = c->opt_refine_short_lds ? 1 : 0;
     else if (!strcmp(name, "reparent_max_tree_nodes")) *value = c->opt_reparent_max_tree_nodes;
     else if (!strcmp(name, "reparent_max_pops_per_node")) *value = c->opt_reparent_max_pops_per_node;
+    else if (!strcmp(name, "draw_max_fragments")) *value = (int64_t)c->opt_draw_max_fragments;
+    else if (!strcmp(name, "draw_heavy_cap")) *value = c->opt_draw_heavy_cap;
+    else if (!strcmp(name, "draw_create_status")) *value = c->draw_create_status;
     else if (!strcmp(name, "dp_wide_levels")) *value = c->dp.valid ? (int64_t)c->dp.wide_levels : 0; // bit k: its level k swept wide
     else return PORRT_ERR_INVALID;
     return PORRT_OK;
@@ -5311,6 +5325,8 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
     else if (!strcmp(name, "mm_plan_batch_max_nodes")) { if (value < 1 || value > (int64_t)kMmBatchNodesLimit) { c->set_err("mm_plan_batch_max_nodes: 1 .. 2^31 - 2"); return PORRT_ERR_INVALID; } c->opt_mm_plan_batch_max_nodes = (uint64_t)value; }
     else if (!strcmp(name, "policy_graph_max_pivots")) { if (value < 0 || value > (int64_t)0x7FFFFFFF) { c->set_err("policy_graph_max_pivots: 0 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_policy_graph_max_pivots = (uint32_t)value; }
     else if (!strcmp(name, "qmdp_max_states")) { if (value < 1 || value > (int64_t)0x7FFFFFFF) { c->set_err("qmdp_max_states: 1 .. 2^31 - 1"); return PORRT_ERR_INVALID; } c->opt_qmdp_max_states = (uint32_t)value; }
+    else if (!strcmp(name, "draw_max_fragments")) { if (value < 1 || value > (int64_t)kDrawMaxFragmentsLimit) { c->set_err("draw_max_fragments: 1 .. 2^30"); return PORRT_ERR_INVALID; } c->opt_draw_max_fragments = (uint64_t)value; }
+    else if (!strcmp(name, "draw_heavy_cap")) { if (value < 1 || value > (int64_t)kDrawHeavyCapLimit) { c->set_err("draw_heavy_cap: 1 .. 1024"); return PORRT_ERR_INVALID; } c->opt_draw_heavy_cap = (uint32_t)value; }
     else { c->set_err(std::string("unknown option ") + name); return PORRT_ERR_INVALID; }
     // a captured launch sequence has the options of its capture in it: the next grow captures again
     if (strcmp(name, "profile") && c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
@@ -5321,3 +5337,4 @@ int porrt_set_option(porrt_ctx *c, const char *name, int64_t value) {
 
 #include "porrt_exchange.hpp"
 #include "porrt_formats.hpp"
+#include "porrt_draw.hpp"

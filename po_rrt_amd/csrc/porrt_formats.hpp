@@ -10,7 +10,11 @@
 //   porrt_graph_*_json    PTOGraph save / load (src/pto_graph.rs:22-118): serde_json's pretty form of
 //                         {"nodes": [{"state": [..], "validity_id": n, "parents": [{"id", "validity_id"}..], "children": [..]}..],
 //                          "validities": [[bool..]..]}, floats in serde_json's (ryu) shortest round-trip notation.
+//   porrt_write_png       what m.save(path) leaves (map_shelves_io.rs:84-86): an 8-bit RGB PNG.  Signature, IHDR, one IDAT holding a zlib
+//                         stream of STORED deflate blocks (at most 65535 bytes each; filter byte 0 before every row), IEND; CRC-32 per
+//                         chunk, Adler-32 over the rows.  No compression and no zlib: the contract is the same pixels, not the same bytes.
 #pragma once
+#include <algorithm>
 #include <cctype>
 #include <charconv>
 #include <cmath>
@@ -351,6 +355,75 @@ inline bool parse_graph(const std::string &text, GraphFile &g) {
     return true;
 }
 
+// ---- PNG
+inline uint32_t crc32_update(uint32_t c, const uint8_t *p, size_t n) {
+    struct Table { uint32_t t[256]; };
+    static const Table table = [] {                               // (a function-local static: made once, whichever thread comes first)
+        Table tb;
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t v = i;
+            for (int k = 0; k < 8; ++k) v = (v & 1u) ? 0xEDB88320u ^ (v >> 1) : v >> 1;
+            tb.t[i] = v;
+        }
+        return tb;
+    }();
+    for (size_t i = 0; i < n; ++i) c = table.t[(c ^ p[i]) & 0xFFu] ^ (c >> 8);
+    return c;
+}
+inline void put_be32(std::vector<uint8_t> &o, uint32_t v) { o.push_back((uint8_t)(v >> 24)); o.push_back((uint8_t)(v >> 16)); o.push_back((uint8_t)(v >> 8)); o.push_back((uint8_t)v); }
+// one chunk: length, type, data, CRC-32 over type and data
+inline bool png_chunk(FILE *f, const char type[4], const std::vector<uint8_t> &data) {
+    std::vector<uint8_t> head;
+    put_be32(head, (uint32_t)data.size());
+    head.insert(head.end(), type, type + 4);
+    uint32_t c = crc32_update(0xFFFFFFFFu, (const uint8_t *)type, 4);
+    c = crc32_update(c, data.data(), data.size()) ^ 0xFFFFFFFFu;
+    std::vector<uint8_t> tail;
+    put_be32(tail, c);
+    return fwrite(head.data(), 1, head.size(), f) == head.size() && (data.empty() || fwrite(data.data(), 1, data.size(), f) == data.size()) &&
+           fwrite(tail.data(), 1, tail.size(), f) == tail.size();
+}
+// the zlib stream of the filtered rows (filter 0), in stored blocks
+inline std::vector<uint8_t> png_stored_stream(const uint8_t *rgb, uint32_t W, uint32_t H) {
+    const size_t row = 3 * (size_t)W, raw_n = (row + 1) * H;
+    std::vector<uint8_t> raw;
+    raw.reserve(raw_n);
+    for (uint32_t i = 0; i < H; ++i) { raw.push_back(0); raw.insert(raw.end(), rgb + row * i, rgb + row * (i + 1)); }
+    std::vector<uint8_t> z;
+    z.reserve(raw_n + 5 * (raw_n / 65535 + 1) + 6);
+    z.push_back(0x78); z.push_back(0x01);                        // deflate, 32 KiB window; (0x7801 % 31 == 0)
+    uint32_t s1 = 1, s2 = 0;                                     // Adler-32, reduced often enough that the sums stay below 2^32
+    for (size_t at = 0; at < raw_n || at == 0;) {
+        const size_t len = std::min<size_t>(65535, raw_n - at);
+        z.push_back(at + len >= raw_n ? 1 : 0);                  // BFINAL, BTYPE 00
+        z.push_back((uint8_t)(len & 0xFF)); z.push_back((uint8_t)(len >> 8));
+        z.push_back((uint8_t)(~len & 0xFF)); z.push_back((uint8_t)((~len >> 8) & 0xFF));
+        z.insert(z.end(), raw.begin() + (std::ptrdiff_t)at, raw.begin() + (std::ptrdiff_t)(at + len));
+        for (size_t k = at; k < at + len;) {
+            const size_t end = std::min(at + len, k + 5552);
+            for (; k < end; ++k) { s1 += raw[k]; s2 += s1; }
+            s1 %= 65521u; s2 %= 65521u;
+        }
+        at += len;
+        if (at >= raw_n) break;
+    }
+    put_be32(z, (s2 << 16) | s1);
+    return z;
+}
+inline int write_png(const char *path, const uint8_t *rgb, uint32_t W, uint32_t H) {
+    if (!path || !rgb || !W || !H) return PORRT_ERR_INVALID;
+    if (((3 * (uint64_t)W + 1) * H) >= (1ull << 31) - (1u << 20)) return PORRT_ERR_CAPACITY;      // one IDAT chunk holds the whole stream
+    const std::vector<uint8_t> z = png_stored_stream(rgb, W, H);
+    std::vector<uint8_t> ihdr;
+    put_be32(ihdr, W); put_be32(ihdr, H);
+    ihdr.push_back(8); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);       // 8 bits, colour type 2 (RGB), deflate, filter method 0, no interlace
+    FILE *f = fopen(path, "wb");
+    if (!f) return PORRT_ERR_IO;
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    const bool ok = fwrite(sig, 1, 8, f) == 8 && png_chunk(f, "IHDR", ihdr) && png_chunk(f, "IDAT", z) && png_chunk(f, "IEND", std::vector<uint8_t>());
+    return (fclose(f) == 0 && ok) ? PORRT_OK : PORRT_ERR_IO;
+}
+
 } // namespace porrt_fmt
 
 struct porrt_graph_file { porrt_fmt::GraphFile g; };
@@ -377,6 +450,10 @@ int porrt_read_pgm(const char *path, uint8_t *out, uint32_t *W, uint32_t *H) {
         if (!porrt_fmt::read_file(path, bytes)) return PORRT_ERR_IO;          // "Impossible to open image"
         return porrt_read_pgm_mem(bytes.data(), bytes.size(), out, W, H);
     });
+}
+
+int porrt_write_png(const char *path, const uint8_t *rgb, uint32_t W, uint32_t H) {
+    return abi_guard([&]() -> int { return porrt_fmt::write_png(path, rgb, W, H); });
 }
 
 static int graph_write_json_impl(const char *path, uint64_t n_nodes, const double *xy, const uint64_t *node_validity, const uint64_t *child_off,

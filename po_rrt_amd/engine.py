@@ -59,6 +59,9 @@ SYMBOLS = [
     "porrt_plan_belief_space_batch", "porrt_plan_batch_get_policies", "porrt_plan_batch_get_expected_costs", "porrt_plan_batch_info",
     "porrt_mm_plan_batch", "porrt_mm_plan_batch_get_policies", "porrt_mm_plan_batch_get_expected_costs", "porrt_mm_plan_batch_get_plan",
     "porrt_mm_plan_batch_info",
+    "porrt_canvas_create", "porrt_canvas_destroy", "porrt_canvas_last_error", "porrt_canvas_size", "porrt_canvas_draw_lines", "porrt_canvas_draw_path",
+    "porrt_canvas_draw_circles", "porrt_canvas_draw_tree", "porrt_canvas_draw_full_graph", "porrt_canvas_draw_zones_observability",
+    "porrt_canvas_draw_policy", "porrt_canvas_get_rgb", "porrt_canvas_save_png", "porrt_write_png", "porrt_canvas_get_info",
 ]
 
 
@@ -160,6 +163,23 @@ class MmPlanBatchInfo(C.Structure):
                                           "belief_edges", "finals", "policies_ok", "policy_nodes", "upload_bytes")] + \
                [(k, C.c_double) for k in ("ms_wall", "ms_host", "ms_points", "ms_roadmaps", "ms_belief_graph", "ms_costs", "ms_policies", "ms_refine",
                                           "ms_device")]
+
+
+class DrawInfo(C.Structure):
+    _fields_ = [("lines", C.c_uint64), ("fragments", C.c_uint64), ("passes", C.c_uint64), ("heaviest_pixel", C.c_uint64),
+                ("heavy_pixels", C.c_uint64), ("wave_pixels", C.c_uint64), ("gradient_by_f64", C.c_uint64), ("s_total", C.c_double), ("s_count", C.c_double),
+                ("s_scan", C.c_double), ("s_scatter", C.c_double), ("s_resolve", C.c_double)]
+
+
+class colors:
+    """the reference's colour table (map_shelves_io.rs:25-48, map_io.rs the same)"""
+    BLACK, WHITE = (0, 0, 0), (255, 255, 255)
+    RED, LIME, BLUE = (255, 0, 0), (0, 255, 0), (0, 0, 255)
+    YELLOW, CYAN, MAGENTA = (255, 255, 0), (0, 255, 255), (255, 0, 255)
+    MAROON, OLIVE, GREEN = (128, 0, 0), (128, 128, 0), (0, 128, 0)
+    PURPLE, TEAL, NAVY = (128, 0, 128), (0, 128, 128), (0, 0, 128)
+    GRAY1, GRAY2, GRAY3, GRAY4 = (30, 30, 30), (60, 60, 60), (90, 90, 90), (120, 120, 120)
+    GRAY5, GRAY6, GRAY7, GRAY8 = (150, 150, 150), (180, 180, 180), (210, 210, 210), (240, 240, 240)
 
 
 class TreeDeviceView(C.Structure):
@@ -366,6 +386,21 @@ def load_library():
     sig("porrt_mm_plan_batch_get_expected_costs", C.c_int, vp, C.c_uint32, vp)
     sig("porrt_mm_plan_batch_get_plan", C.c_int, vp, C.c_uint32, C.POINTER(MmBatchPlan))
     sig("porrt_mm_plan_batch_info", C.c_int, vp, C.POINTER(MmPlanBatchInfo))
+    sig("porrt_canvas_create", vp, vp, C.c_uint32)
+    sig("porrt_canvas_destroy", None, vp)
+    sig("porrt_canvas_last_error", C.c_char_p, vp)
+    sig("porrt_canvas_size", C.c_int, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+    sig("porrt_canvas_draw_lines", C.c_int, vp, _f64p, C.c_uint64, _u8p, C.c_float)
+    sig("porrt_canvas_draw_path", C.c_int, vp, _f64p, C.c_uint64, _u8p)
+    sig("porrt_canvas_draw_circles", C.c_int, vp, _f64p, C.c_uint64, C.c_double, _u8p)
+    sig("porrt_canvas_draw_tree", C.c_int, vp, vp)
+    sig("porrt_canvas_draw_full_graph", C.c_int, vp, vp)
+    sig("porrt_canvas_draw_zones_observability", C.c_int, vp)
+    sig("porrt_canvas_draw_policy", C.c_int, vp, _f64p, _i64p, C.c_uint64)
+    sig("porrt_canvas_get_rgb", C.c_int, vp, _u8p)
+    sig("porrt_canvas_save_png", C.c_int, vp, C.c_char_p)
+    sig("porrt_write_png", C.c_int, C.c_char_p, _u8p, C.c_uint32, C.c_uint32)
+    sig("porrt_canvas_get_info", C.c_int, vp, C.POINTER(DrawInfo))
     _LIB = L
     return L
 
@@ -705,6 +740,10 @@ class Engine:
         call = self._l.porrt_tamp_shortcut_paths_resident if resident else self._l.porrt_tamp_shortcut_paths
         self._chk(call(self._c, xy.ctypes.data, off, len(arrs), out.ctypes.data))
         return [out[int(off[k]):int(off[k + 1])].copy() for k in range(len(arrs))]
+
+    def canvas(self, factor=1):
+        """Map::open + resize(factor): the occupancy raster as an RGB canvas on this engine's device (porrt_canvas_create)"""
+        return Canvas(self, factor)
 
     def get_option(self, name):
         v = C.c_int64(0)
@@ -1401,6 +1440,94 @@ class Engine:
         m = Metrics()
         self._chk(self._l.porrt_get_metrics(self._c, C.byref(m)))
         return {k: getattr(m, k) for k, _ in Metrics._fields_}
+
+
+def _rgb(c):
+    return np.ascontiguousarray(np.asarray(c, dtype=np.uint8).reshape(3))
+
+
+class Canvas:
+    """One porrt_canvas: the drawing half of MapShelfDomain / Map (map_shelves_io.rs:276-457) on the device.  Every method forwards to one
+    exported symbol; the image is bit for bit the reference's sequential loop's."""
+
+    def __init__(self, engine, factor=1):
+        self._l = engine._l
+        self._c = self._l.porrt_canvas_create(engine._c, int(factor))
+        if not self._c:
+            raise PorrtError(engine.get_option("draw_create_status"), self._l.porrt_last_error(engine._c).decode())
+
+    def close(self):
+        if getattr(self, "_c", None):
+            self._l.porrt_canvas_destroy(self._c)
+            self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise PorrtError(rc, self._l.porrt_canvas_last_error(self._c).decode())
+        return rc
+
+    def size(self):
+        """(W, H)"""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._l.porrt_canvas_size(self._c, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def draw_lines(self, ab, color, alpha=1.0):
+        """draw_line(a, b, color, alpha) for every row (ax, ay, bx, by) of ab, in row order"""
+        ab = _f64(ab).reshape(-1, 4)
+        self._chk(self._l.porrt_canvas_draw_lines(self._c, ab, ab.shape[0], _rgb(color), float(alpha)))
+
+    def draw_path(self, xy, color):
+        xy = _f64(xy).reshape(-1, 2)
+        self._chk(self._l.porrt_canvas_draw_path(self._c, xy, xy.shape[0], _rgb(color)))
+
+    def draw_circles(self, xy, radius, color):
+        xy = _f64(xy).reshape(-1, 2)
+        self._chk(self._l.porrt_canvas_draw_circles(self._c, xy, xy.shape[0], float(radius), _rgb(color)))
+
+    def draw_tree(self, engine):
+        self._chk(self._l.porrt_canvas_draw_tree(self._c, engine._c))
+
+    def draw_full_graph(self, engine):
+        self._chk(self._l.porrt_canvas_draw_full_graph(self._c, engine._c))
+
+    def draw_zones_observability(self):
+        self._chk(self._l.porrt_canvas_draw_zones_observability(self._c))
+
+    def draw_policy(self, xy, parent):
+        xy = _f64(xy).reshape(-1, 2)
+        parent = np.ascontiguousarray(parent, dtype=np.int64)
+        self._chk(self._l.porrt_canvas_draw_policy(self._c, xy, parent, xy.shape[0]))
+
+    def rgb(self):
+        w, h = self.size()
+        out = np.zeros((h, w, 3), dtype=np.uint8)
+        self._chk(self._l.porrt_canvas_get_rgb(self._c, out))
+        return out
+
+    def save_png(self, path):
+        self._chk(self._l.porrt_canvas_save_png(self._c, os.fsencode(path)))
+
+    def info(self):
+        """the last draw call: lines, fragments, passes, heaviest_pixel, heavy_pixels, wave_pixels, gradient_by_f64 and seconds per stage"""
+        i = DrawInfo()
+        self._chk(self._l.porrt_canvas_get_info(self._c, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in DrawInfo._fields_}
+
+
+def write_png(path, rgb):
+    """porrt_write_png: an H x W x 3 uint8 array as an 8-bit RGB PNG (host code, no device)"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    h, w, _ = rgb.shape
+    rc = load_library().porrt_write_png(os.fsencode(path), rgb.reshape(-1), w, h)
+    if rc < 0:
+        raise PorrtError(rc, "porrt_write_png(%s)" % path)
 
 
 def conditional_dijkstra(xy, belief_row, beliefs, types, children, parents, finals, device=0):
