@@ -272,7 +272,16 @@ uint64_t porrt_bg_get_dp_sweep_rows(const porrt_ctx *ctx);
 int64_t  porrt_bg_extract_policy(porrt_ctx *ctx, uint64_t *original_ids, int64_t *parents, uint8_t *is_leaf, uint64_t cap, double *expected_costs);
 /* conditional_dijkstra on an explicit belief graph given as host arrays (the form of the reference's own tests,
  * belief_graph.rs:502-567): node i has state xy[2i..], belief vector beliefs[belief_row[i]], type types[i]
- * (1 Action, 2 Observation), children / parents as CSR in add_edge order.  No context needed. */
+ * (1 Action, 2 Observation), children / parents as CSR in add_edge order.  No context needed.
+ * parent_* must be the transpose of child_* (BeliefGraph::add_edge pushes both): the reference relaxes an action node from
+ * the parents list of the node it popped, the device pulls it from its own children list, and a graph in which the two
+ * lists disagree has no defined answer.  A node whose type is neither 1 nor 2, or an observation node with a child of
+ * transition probability 0, is the reference's panic (PORRT_ERR_INVALID) only if one of its children gets a finite cost;
+ * otherwise it is never relaxed and stays at +inf.
+ * Every array is checked on the host before a device is looked for; PORRT_ERR_INVALID when n == 0 or n >= 2^32 - 1, a
+ * required array is NULL (finals with n_final > 0; child_ids / parent_ids when their offsets announce entries),
+ * n_belief_rows == 0 or n_worlds == 0, child_off[0] or parent_off[0] != 0, an offset array decreases,
+ * belief_row[i] >= n_belief_rows, or a child id, parent id or final >= n. */
 int      porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const uint32_t *belief_row, const double *beliefs,
                                     uint32_t n_belief_rows, uint32_t n_worlds, const uint8_t *types,
                                     const uint64_t *child_off, const uint32_t *child_ids, const uint64_t *parent_off, const uint32_t *parent_ids,

@@ -4694,15 +4694,20 @@ int porrt_mm_get_dp_info(const porrt_ctx *c, uint32_t *levels, uint32_t *launche
 int porrt_conditional_dijkstra(int device, uint64_t n, const double *xy, const uint32_t *belief_row, const double *beliefs, uint32_t n_belief_rows,
                                uint32_t n_worlds, const uint8_t *types, const uint64_t *child_off, const uint32_t *child_ids,
                                const uint64_t *parent_off, const uint32_t *parent_ids, const uint64_t *finals, uint64_t n_final, double *dist) {
-    if (!n || !xy || !belief_row || !beliefs || !types || !child_off || !parent_off || !dist || (n_final && !finals) || n >= 0xFFFFFFFFull)
+    if (!n || !xy || !belief_row || !beliefs || !types || !child_off || !parent_off || !dist || (n_final && !finals) || n >= 0xFFFFFFFFull ||
+        !n_belief_rows || !n_worlds)
         return PORRT_ERR_INVALID;
+    // every array is checked here, on the host, before a device is looked for: the kernels index with what the lists hold
+    if (child_off[0] != 0 || parent_off[0] != 0) return PORRT_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i)
+        if (belief_row[i] >= n_belief_rows || child_off[i + 1] < child_off[i] || parent_off[i + 1] < parent_off[i]) return PORRT_ERR_INVALID;
+    const uint64_t nc = child_off[n], np = parent_off[n];
+    if ((nc && !child_ids) || (np && !parent_ids)) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < np; ++k) if (parent_ids[k] >= n) return PORRT_ERR_INVALID;
+    for (uint64_t k = 0; k < n_final; ++k) if (finals[k] >= n) return PORRT_ERR_INVALID;
     return abi_guard([&]() -> int {
         if (hipSetDevice(device) != hipSuccess) return (int)PORRT_ERR_DEVICE;
-        for (uint64_t i = 0; i < n; ++i) if (belief_row[i] >= n_belief_rows) return (int)PORRT_ERR_INVALID;
-        for (uint64_t k = 0; k < n_final; ++k) if (finals[k] >= n) return (int)PORRT_ERR_INVALID;
-        const uint64_t nc = child_off[n], np = parent_off[n];
-        for (uint64_t k = 0; k < nc; ++k) if (child_ids[k] >= n) return (int)PORRT_ERR_INVALID;
-        for (uint64_t k = 0; k < np; ++k) if (parent_ids[k] >= n) return (int)PORRT_ERR_INVALID;
         std::vector<double> hx(n), hy(n);
         for (uint64_t i = 0; i < n; ++i) { hx[i] = xy[2 * i]; hy[i] = xy[2 * i + 1]; }
         DeviceUploads dev;

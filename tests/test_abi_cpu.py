@@ -99,3 +99,39 @@ def test_conditional_dijkstra_rejects_bad_arguments_before_the_device(lib):
         assert call(1, null) == -1, null
     assert call(1, 8, n_final=1) == -1                               # finals announced but not given
     assert call(0xFFFFFFFF) == -1                                    # more nodes than a 32-bit id holds: refused before any array is read
+
+    # a well-formed graph of three nodes (0 -> 1 -> 2, final 2), then one thing wrong at a time: every check of the arrays is made on the
+    # host, so each answer is -1 here, where any call that got as far as the device would answer PORRT_ERR_DEVICE (-4)
+    u32, u64 = np.uint32, np.uint64
+    good = dict(n=3, xy=np.zeros(6), brow=np.array([0, 1, 0], dtype=u32), bel=np.array([[0.5, 0.5], [1.0, 0.0]]), rows=2, nw=2,
+                types=np.ones(3, dtype=np.uint8), coff=np.array([0, 1, 2, 2], dtype=u64), cid=np.array([1, 2], dtype=u32),
+                poff=np.array([0, 0, 1, 2], dtype=u64), pid=np.array([0, 1], dtype=u32), fin=np.array([2], dtype=u64), n_final=1, dist=np.zeros(3))
+
+    def graph_call(**changes):
+        a = dict(good, **changes)
+        p = lambda x: None if x is None else x.ctypes.data
+        return raw(0, a["n"], p(a["xy"]), p(a["brow"]), p(a["bel"]), a["rows"], a["nw"], p(a["types"]), p(a["coff"]), p(a["cid"]), p(a["poff"]),
+                   p(a["pid"]), p(a["fin"]), a["n_final"], p(a["dist"]))
+    import torch
+    if not torch.cuda.is_available():
+        assert graph_call() == -4                                    # the well-formed graph passes every check and stops at the missing device
+    bad = {
+        "child_off[0] != 0": dict(coff=np.array([1, 1, 2, 2], dtype=u64)),
+        "parent_off[0] != 0": dict(poff=np.array([1, 1, 1, 2], dtype=u64)),
+        "child_off decreases": dict(coff=np.array([0, 2, 1, 2], dtype=u64)),
+        "parent_off decreases": dict(poff=np.array([0, 2, 1, 2], dtype=u64)),
+        "child_off decreases at its end": dict(coff=np.array([0, 1, 2, 1], dtype=u64)),
+        "child_ids NULL with entries announced": dict(cid=None),
+        "parent_ids NULL with entries announced": dict(pid=None),
+        "n_worlds == 0": dict(nw=0),
+        "n_belief_rows == 0": dict(rows=0),
+        "belief_row out of range": dict(brow=np.array([0, 2, 0], dtype=u32)),
+        "child id out of range": dict(cid=np.array([1, 3], dtype=u32)),
+        "parent id out of range": dict(pid=np.array([3, 1], dtype=u32)),
+        "final out of range": dict(fin=np.array([3], dtype=u64)),
+    }
+    for what, change in bad.items():
+        assert graph_call(**change) == -1, what
+    # NULL id arrays are fine while the offsets announce nothing
+    if not torch.cuda.is_available():
+        assert graph_call(coff=np.zeros(4, dtype=u64), cid=None, poff=np.zeros(4, dtype=u64), pid=None) == -4

@@ -62,6 +62,8 @@ def sweep_fixpoint(xy, bvec, beliefs, types, coff, cid, finals):
         changed = False
         for u in range(n):
             ch = cid[int(coff[u]):int(coff[u + 1])]
+            if len(ch) == 0:                 # relaxed only when a child is popped: a node without children never is
+                continue
             if types[u] == 1:
                 alt = np.inf
                 for v in ch:
